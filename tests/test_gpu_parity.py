@@ -717,7 +717,7 @@ def test_bench_two_rank_control_flow_on_one_gpu(launcher):
     port = 29600 + os.getpid() % 300
     head = [sys.executable] if launcher == "self-spawn" else [
         sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port)]
-    out = subprocess.run(head + [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--log-rows", "14", "--no-cpu-baseline",
+    out = subprocess.run(head + [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--log-rows", "14", "--full", "--no-cpu-baseline",
                                  "--no-extra-legs", "--sustained-seconds", "0.5"],
                          cwd=root, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]

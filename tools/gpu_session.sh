@@ -57,7 +57,7 @@ run_tests() {  # label, env...
   env "$@" timeout 1500 python -m pytest tests -m gpu -x -q "${k[@]}" > "$OUT/pytest_$lab.log" 2>&1
   echo "pytest[$lab] rc=$? $(tail -1 "$OUT/pytest_$lab.log")" | tee -a "$OUT/summary.txt"
 }
-B="python bench.py --no-cpu-baseline"
+B="python bench.py --full --no-cpu-baseline"
 run_leg() {  # label rep leg env...
   local lab=$1 rep=$2 leg=$3; shift 3
   local f="$OUT/${lab}_rep${rep}.${leg}.json"
@@ -65,7 +65,7 @@ run_leg() {  # label rep leg env...
     three)      env "$@" $B --no-extra-legs $BENCH > "$f" 2>>"$OUT/$lab.err";;
     lone)       env "$@" $B --no-extra-legs --inflight 1 --no-kernel-events --sustained-seconds 0 $BENCH > "$f" 2>>"$OUT/$lab.err";;
     lonek)      env "$@" VGPU_PROF_QUOTIENT_BY_CHIP=1 $B --no-extra-legs --inflight 1 --sustained-seconds 0 $BENCH > "$f" 2>>"$OUT/$lab.err";;  # one proof in flight WITH per-launch events: exclusive per-kernel times (kernel_ms_per_step), quotient launches named by chip
-    full)       [ "$rep" = 1 ] && env "$@" python bench.py > "$f" 2>>"$OUT/$lab.err";;
+    full)       [ "$rep" = 1 ] && env "$@" python bench.py --full > "$f" 2>>"$OUT/$lab.err";;
     c3)         env "$@" $B --no-extra-legs --workload c3 --steps 6 --warmup 2 --sustained-seconds 0 > "$f" 2>>"$OUT/$lab.err";;
     c4)         env "$@" $B --no-extra-legs --workload c4 --sustained-seconds 0 > "$f" 2>>"$OUT/$lab.err";;
     poseidon)   env "$@" $B --no-extra-legs --mmcs poseidon --steps 6 --warmup 2 --sustained-seconds 0 > "$f" 2>>"$OUT/$lab.err";;
@@ -121,7 +121,7 @@ for leg in legs:
 P
 [ $MICRO = 1 ] && python tools/microbench.py > "$OUT/microbench.txt" 2>"$OUT/microbench.err"
 if [ $TIMELINE = 1 ]; then
-  ( cd /tmp && rocprofv3 --kernel-trace --stats -d "$OUT/stats1" -o run -- python "$ROOT/bench.py" --no-cpu-baseline --no-extra-legs --inflight 1 --steps 4 --warmup 1 --sustained-seconds 0 > "$OUT/stats1.json" 2> "$OUT/stats1.err" )
+  ( cd "$TMPDIR" && rocprofv3 --kernel-trace --stats -d "$OUT/stats1" -o run -- python "$ROOT/bench.py" --full --no-cpu-baseline --no-extra-legs --inflight 1 --steps 4 --warmup 1 --sustained-seconds 0 > "$OUT/stats1.json" 2> "$OUT/stats1.err" )
   python tools/summarize_prof.py "$TAG" "$OUT/summary" && rm -rf "$OUT/stats1"
 fi
 [ $PROFILE = 1 ] && bash tools/profile_round.sh "$TAG"

@@ -10,7 +10,7 @@ OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-B="python $ROOT/bench.py --no-cpu-baseline"
+B="python $ROOT/bench.py --full --no-cpu-baseline"
 Q="--sustained-seconds 0"  # the profiled passes run the contract region only (a 6 s sustained region under rocprofv3 would be all trace)
 # bench line alone first (no profiler attached)
 $B > "$OUT/bench_default.json" 2> "$OUT/bench_default.err"
@@ -26,7 +26,7 @@ rocprofv3 --kernel-trace --pmc SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VA
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o run -- $P > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_write" -o run -- $P > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
 # full default bench line (with the CPU baseline leg) and the other single-GPU configs
-python $ROOT/bench.py > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"
+python $ROOT/bench.py --full > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"
 for w in c3 c4; do $B --workload $w --steps 6 --warmup 2 > "$OUT/bench_$w.json" 2> /dev/null; done
 $B --mmcs poseidon --steps 4 --warmup 1 > "$OUT/bench_poseidon.json" 2> "$OUT/bench_poseidon.err"
 # BASELINE.json configs[3] to the letter: the ALU / range-check heavy program with the Poseidon Merkle tree

@@ -153,15 +153,15 @@ def main():
     # databases themselves are too big to travel back, the summaries are not
     dst = sys.argv[2] if len(sys.argv) > 2 else os.path.join(ROOT, "profiles")
     os.makedirs(dst, exist_ok=True)
-    for leg, cmd in (("stats1", "python bench.py --no-cpu-baseline --no-extra-legs --inflight 1 --steps 10 --warmup 1"),
-                     ("stats2", "python bench.py --no-cpu-baseline --no-extra-legs --steps 24 --warmup 3")):
+    for leg, cmd in (("stats1", "python bench.py --full --no-cpu-baseline --no-extra-legs --inflight 1 --steps 10 --warmup 1"),
+                     ("stats2", "python bench.py --full --no-cpu-baseline --no-extra-legs --steps 24 --warmup 3")):
         p = db_of(os.path.join(src, leg))
         if p:
             kernel_stats(p, os.path.join(dst, "%s_kernel_stats_%s.csv" % (tag, "inflight1" if leg == "stats1" else "default")), "rocprofv3 --kernel-trace --stats -- " + cmd + "   (MI355X)")
     p = db_of(os.path.join(src, "stats1"))
     if p:
         try:
-            timeline(p, os.path.join(dst, "%s_timeline_inflight1.txt" % tag), "rocprofv3 --kernel-trace -- python bench.py --no-cpu-baseline --no-extra-legs --inflight 1 --steps 10 --warmup 1   (MI355X)")
+            timeline(p, os.path.join(dst, "%s_timeline_inflight1.txt" % tag), "rocprofv3 --kernel-trace -- python bench.py --full --no-cpu-baseline --no-extra-legs --inflight 1 --steps 10 --warmup 1   (MI355X)")
         except sqlite3.Error as e:
             print("timeline failed:", e)
     for f in ("bench_default.json", "bench_inflight1.json", "bench_full.json", "bench_c3.json", "bench_c4.json", "bench_poseidon.json", "bench_c4_poseidon.json", "stats1.json", "stats2.json"):
