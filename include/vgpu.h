@@ -240,6 +240,26 @@ int32_t vgpu_verify_multi_batches(const vgpu_config_t* cfg, const uint32_t* comm
  * preprocessed traces.  Returns VGPU_OK when the proof is accepted, VGPU_ERR_INVALID_ARG with the reason in vgpu_last_error when not. */
 int32_t vgpu_verify(const vgpu_config_t* cfg, const vgpu_machine_t* machine, const uint32_t* preprocessed_commit, const uint32_t* proof_words,
                     uint64_t n_words);
+/* ---- Batched Machine::verify on the device (vgpu_verify's verdicts over many proofs; kernels/verify.hip).  A verifier handle is apart from
+ * vgpu_prover_t: a verify-only host builds no prover tables.  cfg: device, log_blowup, num_queries, pow_bits, hash_kind, observe_final_poly,
+ * poseidon_rc (what vgpu_verify reads, plus the device); the machine description is copied.  The parse, the transcript, the proof of work,
+ * every shape check, the out-of-domain constraint check and the cumulative sums run on at most 16 host threads; every Merkle opening, the
+ * reduced openings and the FRI fold of every query run on the device.  Proofs are checked in chunks of at most chunk_words proof words
+ * (default 2^25, about 150 MiB of device buffer; a larger single proof is a chunk of its own), so a batch of any size runs in bounded HBM. */
+typedef struct vgpu_verifier vgpu_verifier_t;
+int32_t vgpu_verifier_create(const vgpu_config_t* cfg, const vgpu_machine_t* machine, vgpu_verifier_t** out);
+void vgpu_verifier_destroy(vgpu_verifier_t* v);
+int32_t vgpu_verifier_set_chunk_words(vgpu_verifier_t* v, uint64_t chunk_words);
+/* Machine::verify of n_proofs proofs (flat VPF1 words each).  preprocessed_commits: n_proofs x 8 words (proof i's preprocessed commitment,
+ * the same rule as vgpu_verify's argument), or NULL for a machine without preprocessed traces.  status[i] = VGPU_OK or VGPU_ERR_INVALID_ARG:
+ * exactly vgpu_verify's verdict on proof i, and vgpu_verifier_message(v, i) its message.  The call itself fails only on a device or
+ * allocation error. */
+int32_t vgpu_verify_batch(vgpu_verifier_t* v, const uint32_t* const* proofs, const uint64_t* n_words, const uint32_t* preprocessed_commits,
+                          uint32_t n_proofs, int32_t* status);
+/* the rejection message of proof i of the last batch ("" when accepted): its byte length, copied (NUL-terminated) when out has room */
+int64_t vgpu_verifier_message(const vgpu_verifier_t* v, uint32_t i, char* out, uint64_t cap);
+/* wall time of the last batch: host stages (plans, packing, verdicts, constraints) and device stage (upload, kernels, flags back), ms */
+void vgpu_verifier_timing(const vgpu_verifier_t* v, double* host_ms, double* device_ms);
 /* pcs.commit_batches / commit_shifted_batches on the HOST (the same LDE and MMCS conventions as vgpu_commit_batches, plain O(n log n)
  * code): for the small matrices a verifier commits itself.  mats[i]: canonical row-major heights[i] x widths[i]. */
 int32_t vgpu_host_commit_root(const vgpu_config_t* cfg, const uint32_t* const* mats, const uint64_t* heights, const uint64_t* widths, uint32_t n_mats,

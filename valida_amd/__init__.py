@@ -61,6 +61,10 @@ def lib():
         L.vgpu_proof_debug_perm_trace.restype = ctypes.c_int64
         L.vgpu_proof_debug_quotient.restype = ctypes.c_int64
         L.vgpu_prover_profile.restype = ctypes.c_int64
+        L.vgpu_verifier_message.restype = ctypes.c_int64
+        L.vgpu_verifier_message.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint64]
+        L.vgpu_verifier_timing.argtypes = [ctypes.c_void_p, ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_double)]
+        L.vgpu_verifier_timing.restype = None
         L.vgpu_shader_clock_probe.argtypes = [ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]
         L.vgpu_shader_clock_probe.restype = ctypes.c_int32
         for name in ("vgpu_air_constant", "vgpu_air_variable", "vgpu_air_is_first_row", "vgpu_air_is_last_row", "vgpu_air_is_transition", "vgpu_air_add",
@@ -620,6 +624,60 @@ def verify(machine, rc, proof_words, preprocessed_commit=None, **cfg_kw):
         pcv, pc = _u32(preprocessed_commit)
     code = lib().vgpu_verify(ctypes.byref(cfg), machine._h, pc, pwp, ctypes.c_uint64(pw.size))
     return None if code == 0 else lib().vgpu_last_error().decode()
+
+
+class Verifier:
+    """Machine::verify of many proofs at once on one MI355X (vgpu_verify_batch): every Merkle opening, reduced opening and FRI fold on the
+    device, the transcript, shapes and out-of-domain constraints on at most 16 host threads.  Same verdicts and messages as verify()."""
+
+    def __init__(self, machine, rc, device=0, **cfg_kw):
+        cfg = _config(rc, **cfg_kw)
+        cfg.device = device
+        self.machine = machine  # keeps the handle alive (the description is copied, but a caller may expect the pair)
+        self._h = ctypes.c_void_p()
+        _check(lib().vgpu_verifier_create(ctypes.byref(cfg), machine._h, ctypes.byref(self._h)))
+
+    def set_chunk_words(self, words):
+        """Proof words per device chunk (default 2^25): a batch is checked in chunks of at most this many words."""
+        _check(lib().vgpu_verifier_set_chunk_words(self._h, ctypes.c_uint64(int(words))))
+
+    def verify_batch(self, proofs, preprocessed_commits=None):
+        """proofs: list of word arrays; preprocessed_commits: one 8-word array per proof, or None for a machine without preprocessed traces.
+        Returns one entry per proof: None if accepted, else the rejection message (as verify())."""
+        n = len(proofs)
+        keep = [np.ascontiguousarray(p, dtype=np.uint32) for p in proofs]
+        ptrs = (c_u32p * max(n, 1))(*[k.ctypes.data_as(c_u32p) for k in keep])
+        nw = (ctypes.c_uint64 * max(n, 1))(*[k.size for k in keep])
+        pc = None
+        if preprocessed_commits is not None:
+            assert len(preprocessed_commits) == n
+            pcv, pc = _u32(np.concatenate([np.asarray(c, dtype=np.uint32).ravel() for c in preprocessed_commits]) if n else np.zeros(8, np.uint32))
+        status = (ctypes.c_int32 * max(n, 1))()
+        _check(lib().vgpu_verify_batch(self._h, ptrs, nw, pc, ctypes.c_uint32(n), status))
+        out = []
+        for i in range(n):
+            if status[i] == 0:
+                out.append(None)
+                continue
+            m = int(lib().vgpu_verifier_message(self._h, ctypes.c_uint32(i), None, ctypes.c_uint64(0)))
+            buf = ctypes.create_string_buffer(m + 1)
+            lib().vgpu_verifier_message(self._h, ctypes.c_uint32(i), buf, ctypes.c_uint64(m + 1))
+            out.append(buf.value.decode())
+        return out
+
+    def timing(self):
+        """(host ms, device ms) of the last verify_batch call."""
+        h, d = ctypes.c_double(), ctypes.c_double()
+        lib().vgpu_verifier_timing(self._h, ctypes.byref(h), ctypes.byref(d))
+        return h.value, d.value
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            try:
+                lib().vgpu_verifier_destroy(self._h)
+            except TypeError:  # interpreter shutdown
+                pass
+            self._h = None
 
 
 def host_commit_root(matrices, rc, coset_shifts=None, **cfg_kw):

@@ -22,6 +22,7 @@ SOURCES = [
     "kernels/quotient.hip",
     "kernels/open.hip",
     "kernels/tracegen.hip",
+    "kernels/verify.hip",
     "host/prover.cpp",
     "host/sharded_prover.cpp",
     "capi.cpp",

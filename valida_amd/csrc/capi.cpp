@@ -14,6 +14,7 @@
 #include "host/sharded_prover.hpp"
 #include "host/verifier.hpp"
 #include "host/machine_verifier.hpp"
+#include "host/verify_batch.hpp"
 #include "host/poseidon_opt.hpp"
 #include "host/prover.hpp"
 #include "workload/basic_vm.hpp"
@@ -627,6 +628,95 @@ int32_t vgpu_verify(const vgpu_config_t* cfg, const vgpu_machine_t* machine, con
         Poseidon16 perm(cfg->poseidon_rc);
         verify_machine_proof(machine->desc, fri_of(cfg), perm, preprocessed_commit, proof_words, (size_t)n_words);
     })
+}
+// ---- batched Machine::verify: host/verify_batch.hpp's host half, this device stage (one buffer per chunk up, kernels/verify.hip, flags back)
+struct vgpu_verifier {
+    MachineDesc machine;
+    FriParams fri;
+    std::unique_ptr<Poseidon16> perm;
+    int device = 0;
+    hipStream_t stream = nullptr;
+    uint32_t* pos_dev = nullptr;
+    bool pos_sparse = false;
+    uint32_t* buf_dev = nullptr;  // grown to the largest chunk
+    uint64_t buf_words = 0;
+    uint64_t chunk_words = VERIFY_CHUNK_WORDS_DEFAULT;
+    std::vector<std::string> messages;
+    double host_ms = 0, device_ms = 0;
+    ~vgpu_verifier() {
+        (void)hipSetDevice(device);
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (buf_dev) (void)hipFree(buf_dev);
+        if (pos_dev) (void)hipFree(pos_dev);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+    std::vector<uint32_t> run(const VerifyChunk& c) {
+        VG_HIP_CHECK(hipSetDevice(device));
+        const uint64_t need = c.total_words() + c.n_flags;
+        if (need > buf_words) {
+            if (buf_dev) { VG_HIP_CHECK(hipFree(buf_dev)); buf_dev = nullptr; buf_words = 0; }
+            if (hipMalloc((void**)&buf_dev, need * 4) != hipSuccess) { (void)hipGetLastError(); buf_dev = nullptr; throw std::bad_alloc(); }
+            buf_words = need;
+        }
+        uint32_t* flags_dev = buf_dev + c.total_words();
+        for (const VerifyChunk::Span& sp : c.spans) VG_HIP_CHECK(hipMemcpyAsync(buf_dev + sp.at, sp.words, sp.n * 4, hipMemcpyHostToDevice, stream));
+        VG_HIP_CHECK(hipMemcpyAsync(buf_dev + c.proof_words, c.buf.data(), c.buf.size() * 4, hipMemcpyHostToDevice, stream));
+        vk::launch_verify_chunk(stream, c.args(buf_dev, flags_dev, fri.hash_kind, pos_dev, pos_sparse));
+        VG_HIP_CHECK(hipGetLastError());
+        std::vector<uint32_t> flags(c.n_flags);
+        VG_HIP_CHECK(hipMemcpyAsync(flags.data(), flags_dev, (size_t)c.n_flags * 4, hipMemcpyDeviceToHost, stream));
+        VG_HIP_CHECK(hipStreamSynchronize(stream));
+        return flags;
+    }
+};
+
+int32_t vgpu_verifier_create(const vgpu_config_t* cfg, const vgpu_machine_t* machine, vgpu_verifier_t** out) {
+    VG_TRY({
+        if (!cfg || !machine || !out) throw std::invalid_argument("null argument");
+        if (cfg->hash_kind > 1) throw std::invalid_argument("unknown hash kind");
+        std::unique_ptr<vgpu_verifier> v(new vgpu_verifier());
+        v->machine = machine->desc;
+        v->fri = fri_of(cfg);
+        v->perm.reset(new Poseidon16(cfg->poseidon_rc));
+        v->device = cfg->device;
+        VG_HIP_CHECK(hipSetDevice(v->device));
+        VG_HIP_CHECK(hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking));
+        const std::vector<uint32_t> pos = poseidon_device_image(cfg->poseidon_rc, *v->perm, v->pos_sparse);
+        VG_HIP_CHECK(hipMalloc((void**)&v->pos_dev, pos.size() * 4));
+        VG_HIP_CHECK(hipMemcpy(v->pos_dev, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
+        *out = v.release();
+    })
+}
+void vgpu_verifier_destroy(vgpu_verifier_t* v) { delete v; }
+int32_t vgpu_verifier_set_chunk_words(vgpu_verifier_t* v, uint64_t chunk_words) {
+    VG_TRY({
+        if (!v || !chunk_words) throw std::invalid_argument("null verifier or zero chunk size");
+        v->chunk_words = chunk_words;
+    })
+}
+int32_t vgpu_verify_batch(vgpu_verifier_t* v, const uint32_t* const* proofs, const uint64_t* n_words, const uint32_t* preprocessed_commits, uint32_t n_proofs,
+                          int32_t* status) {
+    VG_TRY({
+        if (!v || (n_proofs && (!proofs || !n_words || !status))) throw std::invalid_argument("null argument");
+        for (uint32_t i = 0; i < n_proofs; i++) if (!proofs[i]) throw std::invalid_argument("null proof");
+        v->messages.assign(n_proofs, std::string());
+        const auto res = verify_machine_batch(v->machine, v->fri, *v->perm, proofs, n_words, preprocessed_commits, n_proofs,
+                                              [v](const VerifyChunk& c) { return v->run(c); }, v->chunk_words, &v->host_ms, &v->device_ms);
+        for (uint32_t i = 0; i < n_proofs; i++) {
+            status[i] = res[i].ok ? VGPU_OK : VGPU_ERR_INVALID_ARG;
+            v->messages[i] = res[i].msg;
+        }
+    })
+}
+int64_t vgpu_verifier_message(const vgpu_verifier_t* v, uint32_t i, char* out, uint64_t cap) {
+    if (!v || i >= v->messages.size()) return fail(VGPU_ERR_INVALID_ARG, "bad verifier or proof index");
+    const std::string& m = v->messages[i];
+    if (out && cap > m.size()) memcpy(out, m.c_str(), m.size() + 1);
+    return (int64_t)m.size();
+}
+void vgpu_verifier_timing(const vgpu_verifier_t* v, double* host_ms, double* device_ms) {
+    if (host_ms) *host_ms = v ? v->host_ms : 0;
+    if (device_ms) *device_ms = v ? v->device_ms : 0;
 }
 int32_t vgpu_host_commit_root(const vgpu_config_t* cfg, const uint32_t* const* mats, const uint64_t* heights, const uint64_t* widths, uint32_t n_mats,
                               const uint32_t* coset_shifts, uint32_t root[8]) {

@@ -11,6 +11,7 @@
 // Preprocessed openings are not part of a proof (lib.rs:612-613, :641): an AIR or interaction that reads a preprocessed column cannot be
 // verified out of domain — the reference's verifier would index an empty slice; here the proof is rejected with that reason.
 #pragma once
+#include "fri_params.hpp"
 #include "machine.hpp"
 #include "verifier.hpp"
 
@@ -187,16 +188,26 @@ inline void verify_chip_constraints(const AirDesc& air, const ChipOpenings& o, c
     if (acc != z_h * quotient) throw std::invalid_argument("verify: chip " + air.name + ": out-of-domain constraint mismatch (folded constraints != Z_H(zeta) * quotient(zeta))");
 }
 
-// Machine::verify over the flat "VPF1" proof words (DESIGN.md "Proof wire format").  preprocessed_commit: 8 canonical words, or null for a
-// machine without preprocessed traces.  Throws std::invalid_argument with the reason when the proof is rejected.
-inline void verify_machine_proof(const MachineDesc& machine, const FriParams& fri, const Poseidon16& perm16, const uint32_t* preprocessed_commit, const uint32_t* words,
-                                 size_t n_words) {
+// Machine::verify in three parts: plan_machine_proof (parse, transcript, shapes: no hashing) -> the FRI plan's per-query checks
+// (check_fri_plan on the host, or the batched device verifier, host/verify_batch.hpp) -> finish_machine_proof (every chip's constraints out
+// of domain, the cumulative sums).  Each throws std::invalid_argument with the reason when the proof is rejected.
+struct MachinePlan {
+    std::vector<ChipOpenings> chips;
+    Ext5 alpha, zeta, rnd[3];
+    FriPlan fri;  // over the proof's tail; fri_off: the word of the proof where it starts
+    size_t fri_off = 0;
+};
+
+inline MachinePlan plan_machine_proof(const MachineDesc& machine, const FriParams& fri, const Poseidon16& perm16, const uint32_t* preprocessed_commit,
+                                      const uint32_t* words, size_t n_words) {
     const size_t NC = machine.airs.size();
+    MachinePlan mp;
     WordCursor r{words, n_words};
     if (r.u() != 0x31465056u) throw std::invalid_argument("verify: not a VPF1 proof");
     if (r.u() != NC) throw std::invalid_argument("verify: wrong number of chip proofs");
     const Digest8 main_commit = r.d(), perm_commit = r.d(), quot_commit = r.d();
-    std::vector<ChipOpenings> chips(NC);
+    std::vector<ChipOpenings>& chips = mp.chips;
+    chips.resize(NC);
     auto vec = [&](std::vector<Ext5>& v) { v.resize(r.len(5)); for (auto& e : v) e = r.e(); };
     for (auto& c : chips) {
         c.log_degree = r.u();
@@ -213,12 +224,11 @@ inline void verify_machine_proof(const MachineDesc& machine, const FriParams& fr
             if (a.prep_width > 0) throw std::invalid_argument("verify: chip " + a.name + " has a preprocessed trace: the preprocessed commitment is required (vgpu_host_commit_root)");
     if (preprocessed_commit) ch.observe_digest(preprocessed_commit);
     ch.observe_digest(main_commit.data());
-    Ext5 rnd[3];
-    for (auto& x : rnd) x = ch.sample_ext();
+    for (auto& x : mp.rnd) x = ch.sample_ext();
     ch.observe_digest(perm_commit.data());
-    const Ext5 alpha = ch.sample_ext();
+    mp.alpha = ch.sample_ext();
     ch.observe_digest(quot_commit.data());
-    const Ext5 zeta = ch.sample_ext();
+    const Ext5 zeta = mp.zeta = ch.sample_ext();
     std::vector<VerifyRoundIn> rounds(3);
     rounds[0].commit = main_commit; rounds[1].commit = perm_commit; rounds[2].commit = quot_commit;
     for (size_t i = 0; i < NC; i++) {
@@ -236,12 +246,25 @@ inline void verify_machine_proof(const MachineDesc& machine, const FriParams& fr
         rounds[2].values.push_back({c.quotient_chunks});
         // verify_multi_batches compares these against the opened rows' widths: a wrong count must be its rejection, not an exception type of ours
     }
-    HostMmcs mmcs{fri.hash_kind, &perm16};
-    verify_multi_batches(rounds, words + r.pos, n_words - r.pos, ch, fri.log_blowup, fri.num_queries, fri.pow_bits, fri.observe_final_poly, mmcs);
-    for (size_t i = 0; i < NC; i++) verify_chip_constraints(machine.airs[i], chips[i], zeta, alpha, rnd);
+    mp.fri_off = r.pos;
+    mp.fri = plan_multi_batches(rounds, words + r.pos, n_words - r.pos, ch, fri.log_blowup, fri.num_queries, fri.pow_bits, fri.observe_final_poly);
+    return mp;
+}
+
+inline void finish_machine_proof(const MachineDesc& machine, const MachinePlan& mp) {
+    for (size_t i = 0; i < machine.airs.size(); i++) verify_chip_constraints(machine.airs[i], mp.chips[i], mp.zeta, mp.alpha, mp.rnd);
     Ext5 sum = Ext5::zero();
-    for (auto& c : chips) sum += c.cumulative_sum;
+    for (auto& c : mp.chips) sum += c.cumulative_sum;
     if (!sum.is_zero()) throw std::invalid_argument("verify: the chips' cumulative sums do not cancel");  // lib.rs:1052-1061
+}
+
+// Machine::verify over the flat "VPF1" proof words (DESIGN.md "Proof wire format").  preprocessed_commit: 8 canonical words, or null for a
+// machine without preprocessed traces.  Throws std::invalid_argument with the reason when the proof is rejected.
+inline void verify_machine_proof(const MachineDesc& machine, const FriParams& fri, const Poseidon16& perm16, const uint32_t* preprocessed_commit, const uint32_t* words,
+                                 size_t n_words) {
+    const MachinePlan mp = plan_machine_proof(machine, fri, perm16, preprocessed_commit, words, n_words);
+    check_fri_plan(mp.fri, HostMmcs{fri.hash_kind, &perm16});
+    finish_machine_proof(machine, mp);
 }
 
 }  // namespace vhost

@@ -9,16 +9,11 @@
 #include <algorithm>
 #include <functional>
 #include <memory>
+#include "fri_params.hpp"
 #include "runtime.hpp"
 
 namespace vhost {
 
-struct FriParams {
-    unsigned log_blowup = 1, num_queries = 40, pow_bits = 8;
-    bool observe_final_poly = false;
-    bool interpret_air = false;  // quotient: force the register-program interpreter even for the in-tree chips
-    int hash_kind = 0;           // MMCS hash: 0 Keccak-256 (reference), 1 Poseidon-16 sponge / truncated permutation (north-star variant)
-};
 
 // A committed matrix given by one device pointer per column (height words each): what the sharded commit hashes — its columns
 // arrive from different ranks and are used where they landed.

@@ -4,6 +4,7 @@
 #include "device_common.hpp"
 #include "profiler.hpp"
 #include "../air/symbolic.hpp"
+#include "verify_args.hpp"
 
 namespace vk {
 
@@ -59,6 +60,8 @@ void launch_intt(hipStream_t st, DMatView m, const DeviceTables& tb);
 void launch_coset_ntt(hipStream_t st, DMatView coeffs, DMatView dst, uint64_t dst_row0, Fp shift, const DeviceTables& tb);
 // natural-order evaluations -> committed (bit-reversed) LDE in 3 fused passes (1 for heights <= 2^12); lt: build_lde_tables(k, log_blowup, shift)
 void launch_lde_natural(hipStream_t st, DMatView nat, DMatView lde, int log_blowup, const DeviceTables& tb, const LdeTables& lt, DMatView s1, DMatView s2);
+// verify.hip: the per-query checks of a chunk of Machine::verify plans (k_verify_open, k_verify_fold, k_verify_tree in that order on `st`)
+void launch_verify_chunk(hipStream_t st, const VerifyChunkArgs& a);
 // merkle.hip
 void launch_keccak_leaves(hipStream_t st, const uint32_t* const* cols_dev, int n_elems, uint64_t n_rows, uint32_t* digests);
 void launch_keccak_leaves_strided(hipStream_t st, const uint32_t* base, uint64_t stride, int n_elems, uint64_t n_rows, uint32_t* digests);

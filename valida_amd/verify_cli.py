@@ -1,12 +1,16 @@
 """`valida verify` for proofs of this backend (the reference's CLI: basic/src/bin/valida.rs, verify sub-command): Machine::verify of the
 product — vgpu_verify — over a proof file.  Host-only: runs anywhere the library loads, no device, no oracle.
 
-    python -m valida_amd.verify_cli PROOF --program fib --n 25 [--log-blowup 1] [--queries 40] [--pow-bits 8] [--poseidon-mmcs]
-                                          [--constants splitmix|cli] [--try-conventions]
+    python -m valida_amd.verify_cli PROOF [PROOF ...] --program fib --n 25 [--log-blowup 1] [--queries 40] [--pow-bits 8] [--poseidon-mmcs]
+                                          [--constants splitmix|cli] [--device D] [--try-conventions]
 
 PROOF: the CBOR image the reference writes (`ciborium::into_writer(&proof, ..)`, either setting of the two encoding switches) or raw
 little-endian VPF1 words.  The program selects the preprocessed traces (ROM, range table) whose commitment the verifier recomputes
 (basic/src/lib.rs:791-804): fib N | alu ITERS | left_imm_ops | signed_inequality | loadfp | static_data.  Exit status 0 = accepted.
+
+Several PROOF files: each is checked (one line per file, prefixed with its name); exit status 0 when every one is accepted.
+--device D: the batched verifier on GPU D (vgpu_verify_batch: Merkle openings, reduced openings and FRI folds on the device) instead of
+the host-only vgpu_verify; the same verdicts and messages.
 
 --constants cli: the Poseidon round constants of the reference's CLI (Pcg64 from Seeder::from("validia seed"), basic/src/bin/valida.rs:364-365;
 valida_amd/cli_constants.py) instead of this repository's SplitMix64 set.
@@ -26,7 +30,7 @@ FORMS = {1: 'field elements as {"value": <Montgomery word>}', 2: "field elements
 
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("proof")
+    ap.add_argument("proof", nargs="+")
     ap.add_argument("--program", default="fib")
     ap.add_argument("--n", type=int, default=25)
     ap.add_argument("--log-blowup", type=int, default=1)
@@ -34,13 +38,12 @@ def main(argv=None):
     ap.add_argument("--pow-bits", type=int, default=8)
     ap.add_argument("--poseidon-mmcs", action="store_true", help="the proof was committed with the Poseidon-16 MMCS (hash_kind 1)")
     ap.add_argument("--constants", choices=["splitmix", "cli"], default="splitmix")
+    ap.add_argument("--device", type=int, default=None, help="verify on this GPU (vgpu_verify_batch)")
     ap.add_argument("--try-conventions", action="store_true")
     args = ap.parse_args(argv)
 
     import valida_amd as va
 
-    raw = open(args.proof, "rb").read()
-    is_words = raw[:4] == (0x31465056).to_bytes(4, "little") and len(raw) % 4 == 0
     w = va.Workload.fib(args.n) if args.program == "fib" else va.Workload.alu(args.n) if args.program == "alu" else va.Workload.named(args.program)
     hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256
     machine = va.Machine.basic()
@@ -50,16 +53,39 @@ def main(argv=None):
         prep_commit = va.host_commit_root([m for _, m in w.preprocessed()], rc, log_blowup=args.log_blowup, hash_kind=hash_kind)
         return va.verify(machine, rc, words, prep_commit, **cfg)
 
-    if not args.try_conventions:
-        try:
-            words = np.frombuffer(raw, dtype="<u4").astype(np.uint32) if is_words else va.proof_from_cbor(raw)
-        except va.VgpuError as e:
-            print("REJECTED: " + str(e))
-            return 1
-        msg = check(words, va.poseidon_round_constants(source=args.constants))
-        print("accepted" if msg is None else "REJECTED: " + msg)
-        return 0 if msg is None else 1
+    def load(path):
+        raw = open(path, "rb").read()
+        is_words = raw[:4] == (0x31465056).to_bytes(4, "little") and len(raw) % 4 == 0
+        return raw, is_words
 
+    if not args.try_conventions:
+        rc = va.poseidon_round_constants(source=args.constants)
+        verdicts = {}  # path -> None | message
+        words_of = {}
+        for path in args.proof:
+            raw, is_words = load(path)
+            try:
+                words_of[path] = np.frombuffer(raw, dtype="<u4").astype(np.uint32) if is_words else va.proof_from_cbor(raw)
+            except va.VgpuError as e:
+                verdicts[path] = str(e)
+        todo = [p for p in args.proof if p in words_of]
+        if args.device is not None and todo:
+            cfg = dict(log_blowup=args.log_blowup, num_queries=args.queries, pow_bits=args.pow_bits, hash_kind=hash_kind)
+            prep_commit = va.host_commit_root([m for _, m in w.preprocessed()], rc, log_blowup=args.log_blowup, hash_kind=hash_kind)
+            res = va.Verifier(machine, rc, device=args.device, **cfg).verify_batch([words_of[p] for p in todo], [prep_commit] * len(todo))
+            verdicts.update(zip(todo, res))
+        else:
+            for p in todo:
+                verdicts[p] = check(words_of[p], rc)
+        for p in args.proof:
+            msg = verdicts[p]
+            line = "accepted" if msg is None else "REJECTED: " + msg
+            print(line if len(args.proof) == 1 else "%s: %s" % (p, line))
+        return 0 if all(verdicts[p] is None for p in args.proof) else 1
+
+    if len(args.proof) != 1:
+        ap.error("--try-conventions takes one PROOF")
+    raw, is_words = load(args.proof[0])
     # ---- first contact ----
     decoded = {}
     if is_words:
