@@ -415,8 +415,12 @@ int32_t vgpu_fabric_selftest(const vgpu_fabric_t* fabric, uint32_t n_words, uint
  * (cpu/src/lib.rs:56-77), MemoryChip::operations: BTreeMap<clk, Vec<Operation>> flattened in (clk, issue) order
  * (memory/src/lib.rs:25-60), and each ALU chip's Vec<Operation> (alu_u32/src/add/mod.rs:26-36).  Words cross the
  * ABI as the u32 value of the big-endian Word (machine/src/core.rs:9). ---- */
+/* cpu Operation (cpu/src/lib.rs:40-54).  The last four are appended (their order is not the reference's enum order): LOADU8 / LOADS8
+ * (cpu/src/lib.rs:493-601: a read of the pointer, a read of its word, the write), STOREU8 (:646-697: three reads — the third read_or_init,
+ * memory/src/lib.rs:107-120, which logs a Read of 0 for a never-written cell — then the write; channel 1 keeps the last of the later reads,
+ * :253-296, so the second read reaches no channel), READ_ADVICE (:398-436: one write, the advice byte or u32::MAX at the end of the tape). */
 enum { VGPU_CPU_STORE32 = 0, VGPU_CPU_LOAD32, VGPU_CPU_JAL, VGPU_CPU_JALV, VGPU_CPU_BEQ, VGPU_CPU_BNE, VGPU_CPU_IMM32, VGPU_CPU_BUS,
-       VGPU_CPU_BUS_LEFT_IMM, VGPU_CPU_STOP, VGPU_CPU_LOADFP };   /* cpu Operation (cpu/src/lib.rs:40-54) */
+       VGPU_CPU_BUS_LEFT_IMM, VGPU_CPU_STOP, VGPU_CPU_LOADFP, VGPU_CPU_LOAD_U8, VGPU_CPU_LOAD_S8, VGPU_CPU_STORE_U8, VGPU_CPU_READ_ADVICE };
 typedef struct vgpu_cpu_op {
     uint32_t pc, fp, opcode;
     int32_t operands[5];
@@ -444,6 +448,8 @@ typedef struct vgpu_oplog_desc {
 } vgpu_oplog_desc_t;
 typedef struct vgpu_oplog vgpu_oplog_t;
 int32_t vgpu_oplog_upload(vgpu_prover_t* p, const vgpu_oplog_desc_t* log, vgpu_oplog_t** out);
+/* the checks vgpu_oplog_upload makes, without a device: VGPU_OK, or VGPU_ERR_INVALID_ARG with the reason in vgpu_last_error() */
+int32_t vgpu_oplog_validate(const vgpu_oplog_desc_t* log);
 void vgpu_oplog_free(vgpu_oplog_t* log);
 /* Any chip of the BasicMachine — all fourteen Chip::generate_trace as kernels: cpu, program, mem, add, sub, lt, bitwise, mul, div, shift,
  * com, output from their logs (the last five exactly as incomplete as the reference fills them: div / com rows carry only the opcode
@@ -474,6 +480,19 @@ int32_t vgpu_workload_main_trace(const vgpu_workload_t* w, uint32_t chip, const 
 void vgpu_workload_oplog(const vgpu_workload_t* w, vgpu_oplog_desc_t* out);
 /* k = 0: program ROM (chip 1), k = 1: range table (chip 12) */
 int32_t vgpu_workload_preprocessed(const vgpu_workload_t* w, uint32_t k, uint32_t* chip, const uint32_t** data, uint64_t* height, uint64_t* width);
+/* A Valida executable (basic/src/bin/valida.rs:340-354): load_executable_file (elf/src/lib.rs:19-120) — raw machine code, 24-byte little-endian
+ * records (ProgramROM::from_machine_code, machine/src/program.rs:181-196), or a little-endian ELF32 / ELF64 (code, static data, initial pc) —
+ * then Machine::run (basic/src/lib.rs:127-145) with fp = stack_height and the FixedAdviceProvider tape `advice` (machine/src/advice.rs:30-56),
+ * all traces generated.  The VM executes every BasicMachine opcode Machine::step dispatches (basic/src/lib.rs:1066-1188).  Refused with a
+ * message, never a crash: a malformed or truncated file, big-endian ELF, ELFCLASS other than 32 / 64, extended section numbering, no text
+ * section, a data address beyond 32 bits, more than 2^22 instructions or 2^22 static cells; at run time an unrecognized opcode, a pc beyond
+ * the ROM, a read before write, and a run that has not stopped after max_cycles cycles (the messages carry pc and opcode).
+ * max_cycles = 0: load only (ROM, static data, preprocessed traces; no run, empty logs, no main traces). */
+int32_t vgpu_workload_from_executable(const uint8_t* exe, uint64_t n_bytes, uint32_t stack_height,
+                                      const uint8_t* advice, uint64_t n_advice, uint64_t max_cycles, vgpu_workload_t** out);
+/* OutputChip::bytes (output/src/lib.rs:27-29): the bytes WRITE put on the output tape.  Returns their number (copies min(number, cap) to
+ * out, which may be null when cap = 0), or a negative error code. */
+int64_t vgpu_workload_output(const vgpu_workload_t* w, uint8_t* out, uint64_t cap);
 
 #ifdef __cplusplus
 }

@@ -67,6 +67,10 @@ def lib():
         L.vgpu_verifier_timing.restype = None
         L.vgpu_shader_clock_probe.argtypes = [ctypes.c_int32, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint64)]
         L.vgpu_shader_clock_probe.restype = ctypes.c_int32
+        L.vgpu_workload_from_executable.argtypes = [ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_uint64,
+                                                    ctypes.POINTER(ctypes.c_void_p)]
+        L.vgpu_workload_output.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_uint64]
+        L.vgpu_workload_output.restype = ctypes.c_int64
         for name in ("vgpu_air_constant", "vgpu_air_variable", "vgpu_air_is_first_row", "vgpu_air_is_last_row", "vgpu_air_is_transition", "vgpu_air_add",
                      "vgpu_air_sub", "vgpu_air_mul", "vgpu_air_neg", "vgpu_machine_num_chips", "vgpu_challenger_grind"):
             getattr(L, name).restype = ctypes.c_uint32
@@ -161,8 +165,13 @@ def decode_interaction_words(w):
 GENERATED_CHIPS = tuple(range(14))  # every BasicMachine chip has a log-driven device trace generator
 
 
+def validate_oplog(desc):
+    """The checks Prover.upload_oplog makes before it touches the device (vgpu_oplog_validate); raises VgpuError with the reason."""
+    _check(lib().vgpu_oplog_validate(ctypes.byref(desc)))
+
+
 class Workload:
-    """Synthetic workload: fib_program(n) run on the BasicMachine, all chip traces generated (host)."""
+    """A program run on the BasicMachine, all chip traces generated (host): a built-in one (fib_program(n), ...) or a Valida executable."""
 
     def __init__(self, handle):
         self._h = handle
@@ -190,6 +199,26 @@ class Workload:
         h = ctypes.c_void_p()
         _check(lib().vgpu_workload_named(name.encode(), ctypes.byref(h)))
         return cls(h)
+
+    @classmethod
+    def from_executable(cls, data, advice=b"", stack_height=1 << 24, max_cycles=1 << 22):
+        """A Valida executable — raw machine code (24-byte little-endian records) or a little-endian ELF — run as `valida run` runs it
+        (basic/src/bin/valida.rs:340-354): fp = stack_height, the FixedAdviceProvider tape `advice`.  A run that has not stopped after
+        max_cycles cycles is refused; max_cycles = 0 loads without running (ROM, static data, preprocessed traces only).  A file or program
+        the loader or the VM refuses raises VgpuError with the reason."""
+        data, advice = bytes(data), bytes(advice)
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_workload_from_executable(data, len(data), stack_height, advice, len(advice), max_cycles, ctypes.byref(h)))
+        return cls(h)
+
+    def output(self):
+        """OutputChip::bytes (output/src/lib.rs:27-29): what the program WROTE, as bytes."""
+        n = lib().vgpu_workload_output(self._h, None, 0)
+        if n < 0:
+            _check(int(n))
+        buf = ctypes.create_string_buffer(max(1, int(n)))
+        lib().vgpu_workload_output(self._h, buf, n)
+        return buf.raw[:n]
 
     def cell(self, addr):
         v = ctypes.c_uint32()

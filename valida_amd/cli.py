@@ -1,0 +1,106 @@
+"""`valida run|prove|verify` for Valida executables (the reference's CLI: basic/src/bin/valida.rs:40-56, 330-449), on this backend.
+
+    python -m valida_amd.cli run    PROGRAM OUTPUT_FILE [ADVICE] [--stack-height N] [--max-cycles N]
+    python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
+    python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
+
+PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
+ADVICE: a file whose bytes are the advice tape (FixedAdviceProvider); without it the tape is empty (the reference reads stdin instead).
+--stack-height: the initial frame pointer (default 16777216, as the reference's).  --max-cycles: a run that has not stopped after that many
+cycles is refused (default 2^22, the largest cpu height this repository proves).
+
+run     Machine::run on the host, then writes OutputChip::bytes to OUTPUT_FILE.
+prove   the device path end to end: the VM on the host, its operation logs uploaded (vgpu_oplog_upload), all fourteen main traces generated
+        on GPU D (vgpu_generate_trace), the preprocessed traces uploaded, Machine::prove, the proof written as CBOR.  One JSON line of
+        phase times (milliseconds) goes to stderr.
+verify  loads PROGRAM without running it (the preprocessed commitment depends on the ROM alone) and runs valida_amd.verify_cli on PROOF_FILE.
+
+Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
+Exit status: 0 on success (run / prove done, proof accepted), 1 otherwise (the reference always exits 0)."""
+import argparse
+import json
+import sys
+import time
+
+
+def _config_flags(ap):
+    ap.add_argument("--log-blowup", type=int, default=1)
+    ap.add_argument("--queries", type=int, default=40)
+    ap.add_argument("--pow-bits", type=int, default=8)
+    ap.add_argument("--poseidon-mmcs", action="store_true", help="commit with the Poseidon-16 MMCS (hash_kind 1) instead of Keccak-256")
+    ap.add_argument("--constants", choices=["splitmix", "cli"], default="splitmix")
+
+
+def prove_on_device(w, prover):
+    """Steps 2-4 of `prove` on an executed workload: (proof, device main traces, phase times in ms)."""
+    import valida_amd as va
+
+    times = {}
+    t = time.perf_counter()
+    log = prover.upload_oplog(w.oplog())
+    times["upload_oplog_ms"] = (time.perf_counter() - t) * 1e3
+    t = time.perf_counter()
+    main = [prover.generate_trace(log, chip) for chip in range(va.NUM_CHIPS)]
+    times["generate_trace_ms"] = (time.perf_counter() - t) * 1e3
+    t = time.perf_counter()
+    prep = [(chip, prover.upload(m)) for chip, m in w.preprocessed()]
+    times["upload_preprocessed_ms"] = (time.perf_counter() - t) * 1e3
+    t = time.perf_counter()
+    proof = prover.prove(main, prep)
+    times["prove_ms"] = (time.perf_counter() - t) * 1e3
+    return proof, main, times
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(prog="python -m valida_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("action", choices=["run", "prove", "verify"])
+    ap.add_argument("program")
+    ap.add_argument("action_file")
+    ap.add_argument("advice", nargs="?", default=None)
+    ap.add_argument("--stack-height", type=int, default=16777216)
+    ap.add_argument("--max-cycles", type=int, default=1 << 22)
+    ap.add_argument("--device", type=int, default=None, help="GPU for prove (default 0) / verify (default: the host verifier)")
+    _config_flags(ap)
+    args = ap.parse_args(argv)
+
+    if args.action == "verify":
+        from valida_amd import verify_cli
+
+        flags = ["--program-file", args.program, "--log-blowup", str(args.log_blowup), "--queries", str(args.queries), "--pow-bits", str(args.pow_bits),
+                 "--constants", args.constants] + (["--poseidon-mmcs"] if args.poseidon_mmcs else []) + (
+                     ["--device", str(args.device)] if args.device is not None else [])
+        return verify_cli.main([args.action_file] + flags)
+
+    import valida_amd as va
+
+    try:
+        t0 = time.perf_counter()
+        exe = open(args.program, "rb").read()
+        advice = open(args.advice, "rb").read() if args.advice else b""
+        w = va.Workload.from_executable(exe, advice=advice, stack_height=args.stack_height, max_cycles=args.max_cycles)
+        vm_ms = (time.perf_counter() - t0) * 1e3
+        if args.action == "run":
+            with open(args.action_file, "wb") as f:
+                f.write(w.output())
+            return 0
+        hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256
+        rc = va.poseidon_round_constants(source=args.constants)
+        prover = va.Prover(va.Machine.basic(), rc, device=args.device or 0, log_blowup=args.log_blowup, num_queries=args.queries, pow_bits=args.pow_bits,
+                           hash_kind=hash_kind)
+        proof, _, times = prove_on_device(w, prover)
+        t = time.perf_counter()
+        with open(args.action_file, "wb") as f:
+            f.write(proof.cbor())
+        times = dict(vm_ms=vm_ms, **times, write_ms=(time.perf_counter() - t) * 1e3)
+        times["total_ms"] = (time.perf_counter() - t0) * 1e3
+        print(json.dumps(dict(cycles=w.cycles, cpu_height=w.cpu_height, proof_words=int(proof.words.size),
+                              **{k: round(v, 3) for k, v in times.items()})), file=sys.stderr)
+        print("Proof successful")
+        return 0
+    except (va.VgpuError, OSError) as e:
+        print("%s: %s" % (args.action, e), file=sys.stderr)
+        return 1
+
+
+if __name__ == "__main__":
+    sys.exit(main())

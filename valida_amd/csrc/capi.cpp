@@ -18,6 +18,7 @@
 #include "host/poseidon_opt.hpp"
 #include "host/prover.hpp"
 #include "workload/basic_vm.hpp"
+#include "workload/executable.hpp"
 
 using namespace vhost;
 
@@ -50,6 +51,10 @@ struct vgpu_comm { std::shared_ptr<Prover> owner; std::unique_ptr<Comm> comm; };
 static_assert(sizeof(vgpu_cpu_op_t) == sizeof(vk::TgCpuOp) && sizeof(vgpu_mem_op_t) == sizeof(vk::TgMemOp) && sizeof(vgpu_alu_op_t) == sizeof(vk::TgAluOp),
               "C ABI log records and their device images must match");
 static_assert((int)VGPU_CPU_LOADFP == (int)vk::TG_CPU_LOADFP, "cpu op kinds");
+static_assert((int)VGPU_CPU_LOAD_U8 == (int)vk::TG_CPU_LOAD_U8 && (int)VGPU_CPU_LOAD_U8 == (int)vwork::CpuOp::LoadU8, "cpu op kinds");
+static_assert((int)VGPU_CPU_LOAD_S8 == (int)vk::TG_CPU_LOAD_S8 && (int)VGPU_CPU_LOAD_S8 == (int)vwork::CpuOp::LoadS8, "cpu op kinds");
+static_assert((int)VGPU_CPU_STORE_U8 == (int)vk::TG_CPU_STORE_U8 && (int)VGPU_CPU_STORE_U8 == (int)vwork::CpuOp::StoreU8, "cpu op kinds");
+static_assert((int)VGPU_CPU_READ_ADVICE == (int)vk::TG_CPU_READ_ADVICE && (int)VGPU_CPU_READ_ADVICE == (int)vwork::CpuOp::ReadAdvice, "cpu op kinds");
 static_assert(sizeof(vgpu_out_op_t) == sizeof(vk::TgOutOp), "C ABI log records and their device images must match");
 struct vgpu_workload {
     std::vector<vgpu_cpu_op_t> log_cpu;
@@ -388,60 +393,71 @@ int32_t vgpu_trace_download(vgpu_prover_t* p, const vgpu_trace_t* t, uint32_t* o
         p->p->download_trace(*t->t, out);
     })
 }
+// every check vgpu_oplog_upload makes before it touches the device; fills the host view of the logs
+static HostOplog checked_oplog(const vgpu_oplog_desc_t* log) {
+    if (log->struct_size != sizeof(vgpu_oplog_desc_t))
+        throw std::invalid_argument("oplog: struct_size " + std::to_string(log->struct_size) + " is not this library's sizeof(vgpu_oplog_desc_t) = " + std::to_string(sizeof(vgpu_oplog_desc_t)) +
+                                    " (host compiled against another vgpu.h?)");
+    HostOplog h;
+    h.cpu = (const vk::TgCpuOp*)log->cpu; h.n_cpu = log->n_cpu;
+    h.mem = (const vk::TgMemOp*)log->mem; h.n_mem = log->n_mem;
+    for (int k = 0; k < 4; k++) { h.alu[k] = (const vk::TgAluOp*)log->alu[k]; h.n_alu[k] = log->n_alu[k]; }
+    h.static_cells = log->static_cells; h.n_static = log->n_static;
+    h.rom_len = log->rom_len;
+    for (int k = 0; k < 4; k++) { h.alu2[k] = (const vk::TgAluOp*)log->alu2[k]; h.n_alu2[k] = log->n_alu2[k]; if (h.n_alu2[k] && !h.alu2[k]) throw std::invalid_argument("oplog: null ALU log with a nonzero length"); }
+    h.output = (const vk::TgOutOp*)log->output; h.n_output = log->n_output;
+    if (h.n_output && !h.output) throw std::invalid_argument("oplog: null output tape with a nonzero length");
+    {   // every logged operation must be a variant of its chip's Operation enum
+        using namespace vchips;
+        auto check = [&](int k, std::initializer_list<uint32_t> ok, const char* chip) {
+            for (uint64_t i = 0; i < h.n_alu2[k]; i++) {
+                bool good = false;
+                for (uint32_t o : ok) good |= h.alu2[k][i].opcode == o;
+                if (!good) throw std::invalid_argument(std::string("oplog: ") + chip + " log entry " + std::to_string(i) + " has an opcode that is not an operation of that chip");
+                if (k == 2 && h.alu2[k][i].c >= 32) throw std::invalid_argument("oplog: shift log entry " + std::to_string(i) + ": shift amount >= 32");
+            }
+        };
+        check(0, {OP_MUL32, OP_MULHS32, OP_MULHU32}, "mul");
+        check(1, {OP_DIV32, OP_SDIV32}, "div");
+        check(2, {OP_SHL32, OP_SHR32, OP_SRA32}, "shift");
+        check(3, {OP_NE32, OP_EQ32}, "com");
+    }
+    for (uint64_t i = 1; i < h.n_static; i++)
+        if (log->static_cells[2 * i] <= log->static_cells[2 * i - 2]) throw std::invalid_argument("oplog: static cells must be in ascending address order");
+    if (!h.n_cpu || !log->cpu) throw std::invalid_argument("oplog: empty cpu log");
+    if ((h.n_mem && !log->mem) || (h.n_static && !log->static_cells)) throw std::invalid_argument("oplog: null log with a nonzero length");
+    for (int k = 0; k < 4; k++) if (h.n_alu[k] && !h.alu[k]) throw std::invalid_argument("oplog: null ALU log with a nonzero length");
+    for (uint64_t i = 0; i < h.n_cpu; i++) {
+        const vgpu_cpu_op_t& o = log->cpu[i];
+        if (o.mem_first > h.n_mem || (i && o.mem_first < log->cpu[i - 1].mem_first) || o.kind > VGPU_CPU_READ_ADVICE)
+            throw std::invalid_argument("oplog: cpu record " + std::to_string(i) + " is malformed");
+        // the program chip's multiplicity histogram indexes the ROM by pc
+        if (h.rom_len && o.pc >= h.rom_len) throw std::invalid_argument("oplog: cpu record " + std::to_string(i) + ": pc beyond the ROM length");
+        // Bus operations must target a chip of the BasicMachine (every one of them has a log-driven generator now); anything else —
+        // an advice read, an opcode of another machine — has no chip to receive it here
+        if (o.kind == VGPU_CPU_BUS || o.kind == VGPU_CPU_BUS_LEFT_IMM) {
+            using namespace vchips;
+            const uint32_t op = o.opcode;
+            const bool known = (op >= OP_ADD32 && op <= OP_SLE32) || op == OP_WRITE;
+            if (!known) throw std::invalid_argument("oplog: cpu record " + std::to_string(i) + ": opcode " + std::to_string(op) + " is no bus operation of the BasicMachine's chips");
+        }
+    }
+    // the memory chip's stable by-address radix sort reproduces the reference's (addr, clk) order only for clk-ordered logs
+    for (uint64_t i = 1; i < h.n_mem; i++)
+        if (log->mem[i].clk < log->mem[i - 1].clk) throw std::invalid_argument("oplog: memory log entry " + std::to_string(i) + " is out of clock order");
+    return h;
+}
+int32_t vgpu_oplog_validate(const vgpu_oplog_desc_t* log) {
+    VG_TRY({
+        if (!log) throw std::invalid_argument("null argument");
+        checked_oplog(log);
+    })
+}
 int32_t vgpu_oplog_upload(vgpu_prover_t* p, const vgpu_oplog_desc_t* log, vgpu_oplog_t** out) {
     VG_TRY({
         if (!p || !log || !out) throw std::invalid_argument("null argument");
-        if (log->struct_size != sizeof(vgpu_oplog_desc_t))
-            throw std::invalid_argument("oplog: struct_size " + std::to_string(log->struct_size) + " is not this library's sizeof(vgpu_oplog_desc_t) = " + std::to_string(sizeof(vgpu_oplog_desc_t)) +
-                                        " (host compiled against another vgpu.h?)");
+        const HostOplog h = checked_oplog(log);
         p->p->ctx().activate();
-        HostOplog h;
-        h.cpu = (const vk::TgCpuOp*)log->cpu; h.n_cpu = log->n_cpu;
-        h.mem = (const vk::TgMemOp*)log->mem; h.n_mem = log->n_mem;
-        for (int k = 0; k < 4; k++) { h.alu[k] = (const vk::TgAluOp*)log->alu[k]; h.n_alu[k] = log->n_alu[k]; }
-        h.static_cells = log->static_cells; h.n_static = log->n_static;
-        h.rom_len = log->rom_len;
-        for (int k = 0; k < 4; k++) { h.alu2[k] = (const vk::TgAluOp*)log->alu2[k]; h.n_alu2[k] = log->n_alu2[k]; if (h.n_alu2[k] && !h.alu2[k]) throw std::invalid_argument("oplog: null ALU log with a nonzero length"); }
-        h.output = (const vk::TgOutOp*)log->output; h.n_output = log->n_output;
-        if (h.n_output && !h.output) throw std::invalid_argument("oplog: null output tape with a nonzero length");
-        {   // every logged operation must be a variant of its chip's Operation enum
-            using namespace vchips;
-            auto check = [&](int k, std::initializer_list<uint32_t> ok, const char* chip) {
-                for (uint64_t i = 0; i < h.n_alu2[k]; i++) {
-                    bool good = false;
-                    for (uint32_t o : ok) good |= h.alu2[k][i].opcode == o;
-                    if (!good) throw std::invalid_argument(std::string("oplog: ") + chip + " log entry " + std::to_string(i) + " has an opcode that is not an operation of that chip");
-                    if (k == 2 && h.alu2[k][i].c >= 32) throw std::invalid_argument("oplog: shift log entry " + std::to_string(i) + ": shift amount >= 32");
-                }
-            };
-            check(0, {OP_MUL32, OP_MULHS32, OP_MULHU32}, "mul");
-            check(1, {OP_DIV32, OP_SDIV32}, "div");
-            check(2, {OP_SHL32, OP_SHR32, OP_SRA32}, "shift");
-            check(3, {OP_NE32, OP_EQ32}, "com");
-        }
-        for (uint64_t i = 1; i < h.n_static; i++)
-            if (log->static_cells[2 * i] <= log->static_cells[2 * i - 2]) throw std::invalid_argument("oplog: static cells must be in ascending address order");
-        if (!h.n_cpu || !log->cpu) throw std::invalid_argument("oplog: empty cpu log");
-        if ((h.n_mem && !log->mem) || (h.n_static && !log->static_cells)) throw std::invalid_argument("oplog: null log with a nonzero length");
-        for (int k = 0; k < 4; k++) if (h.n_alu[k] && !h.alu[k]) throw std::invalid_argument("oplog: null ALU log with a nonzero length");
-        for (uint64_t i = 0; i < h.n_cpu; i++) {
-            const vgpu_cpu_op_t& o = log->cpu[i];
-            if (o.mem_first > h.n_mem || (i && o.mem_first < log->cpu[i - 1].mem_first) || o.kind > VGPU_CPU_LOADFP)
-                throw std::invalid_argument("oplog: cpu record " + std::to_string(i) + " is malformed");
-            // the program chip's multiplicity histogram indexes the ROM by pc
-            if (h.rom_len && o.pc >= h.rom_len) throw std::invalid_argument("oplog: cpu record " + std::to_string(i) + ": pc beyond the ROM length");
-            // Bus operations must target a chip of the BasicMachine (every one of them has a log-driven generator now); anything else —
-            // an advice read, an opcode of another machine — has no chip to receive it here
-            if (o.kind == VGPU_CPU_BUS || o.kind == VGPU_CPU_BUS_LEFT_IMM) {
-                using namespace vchips;
-                const uint32_t op = o.opcode;
-                const bool known = (op >= OP_ADD32 && op <= OP_SLE32) || op == OP_WRITE;
-                if (!known) throw std::invalid_argument("oplog: cpu record " + std::to_string(i) + ": opcode " + std::to_string(op) + " is no bus operation of the BasicMachine's chips");
-            }
-        }
-        // the memory chip's stable by-address radix sort reproduces the reference's (addr, clk) order only for clk-ordered logs
-        for (uint64_t i = 1; i < h.n_mem; i++)
-            if (log->mem[i].clk < log->mem[i - 1].clk) throw std::invalid_argument("oplog: memory log entry " + std::to_string(i) + " is out of clock order");
         std::unique_ptr<vgpu_oplog> l(new vgpu_oplog());
         l->owner = p->p;
         l->log = p->p->upload_oplog(h);
@@ -1252,6 +1268,37 @@ int32_t vgpu_workload_named(const char* name, vgpu_workload_t** out) {
         *out = w.release();
     })
 }
+int32_t vgpu_workload_from_executable(const uint8_t* exe, uint64_t n_bytes, uint32_t stack_height, const uint8_t* advice, uint64_t n_advice, uint64_t max_cycles,
+                                      vgpu_workload_t** out) {
+    VG_TRY({
+        if (!out || (n_bytes && !exe) || (n_advice && !advice)) throw std::invalid_argument("null argument");
+        vwork::Executable e = vwork::load_executable(exe, n_bytes);
+        auto w = std::make_unique<vgpu_workload>();
+        w->vm.reset(new vwork::BasicVm(std::move(e.code), stack_height, e.initial_pc));
+        for (auto& kv : e.data) w->vm->write_static(kv.first, kv.second);  // StaticDataChip::load, then initialize_memory (basic/src/bin/valida.rs:352)
+        if (n_advice) w->vm->advice.assign(advice, advice + n_advice);
+        w->prep_program = w->vm->program_preprocessed();
+        w->prep_range = vwork::BasicVm::range_preprocessed();
+        if (max_cycles) {
+            try {
+                w->vm->run(max_cycles);
+            } catch (const std::runtime_error& x) {  // a refusal of the program, not a failure of the library
+                throw std::invalid_argument(x.what());
+            }
+            w->main = w->vm->main_traces();
+            fill_logs(*w);
+        } else {
+            for (auto& kv : w->vm->static_cells) { w->log_static.push_back(kv.first); w->log_static.push_back(vwork::u32_of(kv.second)); }
+        }
+        *out = w.release();
+    })
+}
+int64_t vgpu_workload_output(const vgpu_workload_t* w, uint8_t* out, uint64_t cap) {
+    if (!w || (cap && !out)) return fail(VGPU_ERR_INVALID_ARG, "null argument");
+    const auto& v = w->vm->output_values;
+    for (uint64_t i = 0; i < std::min<uint64_t>(cap, v.size()); i++) out[i] = v[i].second;
+    return (int64_t)v.size();
+}
 int32_t vgpu_workload_cell(const vgpu_workload_t* w, uint32_t addr, uint32_t* value) {
     VG_TRY({
         if (!w || !value) throw std::invalid_argument("bad argument");
@@ -1273,10 +1320,11 @@ void vgpu_workload_oplog(const vgpu_workload_t* w, vgpu_oplog_desc_t* out) {
 void vgpu_workload_free(vgpu_workload_t* w) { delete w; }
 void vgpu_workload_stats(const vgpu_workload_t* w, uint64_t out[8]) {
     out[0] = w->vm->clock; out[1] = w->vm->cpu_ops.size(); out[2] = w->vm->mem_ops.size(); out[3] = w->vm->add_ops.size();
-    out[4] = w->result; out[5] = w->vm->rom.size(); out[6] = w->main[0].height; out[7] = 0;
+    out[4] = w->result; out[5] = w->vm->rom.size(); out[6] = w->main.empty() ? 0 : w->main[0].height; out[7] = 0;
 }
 int32_t vgpu_workload_main_trace(const vgpu_workload_t* w, uint32_t chip, const uint32_t** data, uint64_t* height, uint64_t* width) {
     VG_TRY({
+        if (w && w->main.empty()) throw std::invalid_argument("the workload was loaded without running (max_cycles = 0): it has no main traces");
         if (!w || chip >= w->main.size()) throw std::invalid_argument("bad chip index");
         *data = w->main[chip].v.data(); *height = w->main[chip].height; *width = w->main[chip].width;
     })

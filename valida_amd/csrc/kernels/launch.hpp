@@ -133,7 +133,7 @@ struct TgMemOp { uint32_t clk, addr, value, is_write; };
 struct TgAluOp { uint32_t opcode, a, b, c; };  // a = result, b / c = inputs, as u32 values of the big-endian Words
 struct TgOutOp { uint32_t clk, byte; };          // OutputChip::values entry
 enum { TG_CPU_STORE32 = 0, TG_CPU_LOAD32, TG_CPU_JAL, TG_CPU_JALV, TG_CPU_BEQ, TG_CPU_BNE, TG_CPU_IMM32, TG_CPU_BUS, TG_CPU_BUS_LEFT_IMM, TG_CPU_STOP,
-       TG_CPU_LOADFP };
+       TG_CPU_LOADFP, TG_CPU_LOAD_U8, TG_CPU_LOAD_S8, TG_CPU_STORE_U8, TG_CPU_READ_ADVICE };
 void launch_tracegen_cpu(hipStream_t st, const TgCpuOp* ops, uint64_t n, const TgMemOp* mem, uint64_t n_mem, DMatView t);
 size_t tracegen_mem_sort_scratch_bytes(uint64_t n);
 hipError_t launch_tracegen_mem(hipStream_t st, const TgMemOp* mem, uint64_t n, const uint32_t* static_cells, uint64_t n_static, uint32_t* keys2, uint32_t* idx2,

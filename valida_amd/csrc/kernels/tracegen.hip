@@ -28,6 +28,27 @@ __device__ __forceinline__ uint32_t from_i32(int32_t x) {  // Val::from_canonica
 }
 
 // ---- cpu -----------------------------------------------------------------------------------------------
+// the flag column of an op kind (Operation -> is_* flags, cpu/src/lib.rs:163-236); the kinds are exclusive, so a row carries one index
+// instead of fifteen booleans
+__device__ __forceinline__ int cpu_flag_col(uint32_t kind) {
+    switch (kind) {
+        case TG_CPU_STORE32: return cpu::IS_STORE;
+        case TG_CPU_LOAD32: return cpu::IS_LOAD;
+        case TG_CPU_JAL: return cpu::IS_JAL;
+        case TG_CPU_JALV: return cpu::IS_JALV;
+        case TG_CPU_BEQ: return cpu::IS_BEQ;
+        case TG_CPU_BNE: return cpu::IS_BNE;
+        case TG_CPU_IMM32: return cpu::IS_IMM32;
+        case TG_CPU_BUS: case TG_CPU_BUS_LEFT_IMM: return cpu::IS_BUS_OP;
+        case TG_CPU_STOP: return cpu::IS_STOP;
+        case TG_CPU_LOADFP: return cpu::IS_LOADFP;
+        case TG_CPU_LOAD_U8: return cpu::IS_LOAD_U8;
+        case TG_CPU_LOAD_S8: return cpu::IS_LOAD_S8;
+        case TG_CPU_STORE_U8: return cpu::IS_STORE_U8;
+        case TG_CPU_READ_ADVICE: return cpu::IS_ADVICE;
+        default: return -1;  // refused at upload (vgpu_oplog_upload)
+    }
+}
 __global__ void __launch_bounds__(256) k_tracegen_cpu(const TgCpuOp* __restrict__ ops, uint64_t n, const TgMemOp* __restrict__ mem, uint64_t n_mem, DMatView t) {
     const uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= t.height) return;
@@ -36,17 +57,14 @@ __global__ void __launch_bounds__(256) k_tracegen_cpu(const TgCpuOp* __restrict_
     for (int c = 0; c < cpu::NUM_COLS; c++) r[c] = 0;
     r[cpu::ch(0, cpu::CH_IS_READ)] = 1; r[cpu::ch(1, cpu::CH_IS_READ)] = 1;
     Fp diff = Fp::zero();
+    int flag = cpu::IS_STOP;  // padding rows are STOPs
     if (i < n) {
         const TgCpuOp o = ops[i];
         r[cpu::PC] = o.pc; r[cpu::FP] = o.fp % vg::P; r[cpu::CLK] = (uint32_t)i; r[cpu::OPCODE] = o.opcode;
 #pragma unroll
         for (int k = 0; k < 5; k++) r[cpu::OPERAND_A + k] = from_i32(o.operands[k]);
         const bool left = o.kind == TG_CPU_BUS_LEFT_IMM;
-        // flag column of the op kind (Operation -> is_* flags, cpu/src/lib.rs:163-236)
-        r[cpu::IS_STORE] = o.kind == TG_CPU_STORE32; r[cpu::IS_LOAD] = o.kind == TG_CPU_LOAD32; r[cpu::IS_JAL] = o.kind == TG_CPU_JAL;
-        r[cpu::IS_JALV] = o.kind == TG_CPU_JALV; r[cpu::IS_BEQ] = o.kind == TG_CPU_BEQ; r[cpu::IS_BNE] = o.kind == TG_CPU_BNE;
-        r[cpu::IS_IMM32] = o.kind == TG_CPU_IMM32; r[cpu::IS_BUS_OP] = (o.kind == TG_CPU_BUS || left); r[cpu::IS_STOP] = o.kind == TG_CPU_STOP;
-        r[cpu::IS_LOADFP] = o.kind == TG_CPU_LOADFP;
+        flag = cpu_flag_col(o.kind);
         uint32_t val[3][4] = {{0, 0, 0, 0}, {0, 0, 0, 0}, {0, 0, 0, 0}}, used[3] = {0, 0, 0}, addr[3] = {0, 0, 0};
         const bool imm_kind = o.kind == TG_CPU_BEQ || o.kind == TG_CPU_BNE || o.kind == TG_CPU_BUS || left;
         if (o.has_imm && imm_kind) {  // the immediate rides in the read channel it replaces; operand = Word::reduce
@@ -55,7 +73,8 @@ __global__ void __launch_bounds__(256) k_tracegen_cpu(const TgCpuOp* __restrict_
 #pragma unroll
             for (int k = 0; k < 4; k++) { if (left) val[0][k] = byte_of(o.imm, k); else val[1][k] = byte_of(o.imm, k); }
         }
-        // set_memory_channel_values: this cycle's memory operations in issue order
+        // set_memory_channel_values: this cycle's memory operations in issue order (a STOREU8's three reads: the first to channel 0, the
+        // second and third to channel 1, the third staying — as the host's loop leaves them)
         const uint64_t m0 = o.mem_first, m1 = i + 1 < n ? ops[i + 1].mem_first : n_mem;
         bool first_read = true;
         for (uint64_t k = m0; k < m1; k++) {
@@ -83,11 +102,11 @@ __global__ void __launch_bounds__(256) k_tracegen_cpu(const TgCpuOp* __restrict_
         // pad_to_power_of_two: STOP rows continuing the clock
         const TgCpuOp o = ops[n - 1];
         r[cpu::PC] = o.pc; r[cpu::FP] = o.fp % vg::P; r[cpu::CLK] = (uint32_t)(((n - 1) % vg::P + (i - n + 1) % vg::P) % vg::P);
-        r[cpu::IS_STOP] = 1; r[cpu::OPCODE] = OP_STOP;
+        r[cpu::OPCODE] = OP_STOP;
     }
 #pragma unroll
-    for (int c = 0; c < cpu::NUM_COLS; c++)
-        if (c != cpu::DIFF && c != cpu::DIFF_INV && c != cpu::NOT_EQUAL) put(t, c, i, r[c]);
+    for (int c = 0; c < cpu::NUM_COLS; c++)  // the opcode flags lie in [IS_BUS_OP, IS_LOADFP] (chips/basic_machine.hpp)
+        if (c != cpu::DIFF && c != cpu::DIFF_INV && c != cpu::NOT_EQUAL) put(t, c, i, (c >= cpu::IS_BUS_OP && c <= cpu::IS_LOADFP) ? (r[c] | (uint32_t)(c == flag)) : r[c]);
     put_raw(t, cpu::DIFF, i, diff);
     put_raw(t, cpu::DIFF_INV, i, diff.inv());  // 0 -> 0
     put(t, cpu::NOT_EQUAL, i, diff.is_zero() ? 0u : 1u);

@@ -1,11 +1,13 @@
-// Synthetic-workload generator: a minimal interpreter for the BasicMachine opcodes the benchmark
-// programs use, plus each chip's `generate_trace`, producing the host-resident RowMajorMatrix inputs
-// that `Machine::prove` starts from.  Trace generation is UPSTREAM of the hot path (SURVEY.md §3.5,
+// The host VM: an interpreter for every opcode the BasicMachine's `Machine::step` dispatches, plus each
+// chip's `generate_trace`, producing the host-resident RowMajorMatrix inputs that `Machine::prove` starts
+// from — for the built-in programs below and for Valida executables (executable.hpp).  Trace generation is UPSTREAM of the hot path (SURVEY.md §3.5,
 // §7.1 step 1b); it lives here so that bench.py and the tests can build inputs without the oracle.
 //
 // Restated from (reference file:line):
 //   Machine::run / step                  basic/src/lib.rs:127-145, :1066-1188
 //   core instructions                    cpu/src/lib.rs:430-881
+//   READ_ADVICE / LOADU8 / LOADS8 / STOREU8  cpu/src/lib.rs:398-436, :493-601, :646-697; addr_of_word, index_of_byte, sign_extend_byte,
+//                                        update_byte machine/src/core.rs:14-60; read_or_init memory/src/lib.rs:107-120
 //   add/sub/lt/bitwise instructions      alu_u32/src/{add,sub,lt,bitwise}/mod.rs
 //   MemoryChip read/write/generate_trace memory/src/lib.rs:84-194, :236-262
 //   CpuChip generate_trace + padding     cpu/src/lib.rs:79-97, :163-373
@@ -55,7 +57,7 @@ inline uint32_t word_reduce(const Word& w) {  // Word::reduce in the field
 }
 
 struct MemOp { uint32_t clk; uint32_t addr; Word value; bool is_write; };
-enum class CpuOp { Store32, Load32, Jal, Jalv, Beq, Bne, Imm32, Bus, BusLeftImm, Stop, LoadFp };
+enum class CpuOp { Store32, Load32, Jal, Jalv, Beq, Bne, Imm32, Bus, BusLeftImm, Stop, LoadFp, LoadU8, LoadS8, StoreU8, ReadAdvice };  // = VGPU_CPU_*
 struct CpuRecord { CpuOp op; bool has_imm; Word imm; uint32_t pc, fp; InstructionWord instr; };
 struct AluOp { uint32_t opcode; Word a, b, c; };
 
@@ -81,16 +83,29 @@ struct BasicVm {
     std::vector<uint32_t> program_counts;
     uint32_t range_counts[256] = {0};
     std::map<uint32_t, Word> static_cells;  // StaticDataChip::cells, copied into memory by initialize_memory (static_data/src/lib.rs:28-32)
+    std::vector<uint8_t> advice;            // FixedAdviceProvider's tape (machine/src/advice.rs:30-56)
+    size_t advice_pos = 0;
     // machine.static_data_mut().write(addr, value) before run (basic/tests/test_static_data.rs:57-58)
     void write_static(uint32_t addr, Word w) { static_cells[addr] = w; cells[addr] = u32_of(w); }
 
-    explicit BasicVm(std::vector<InstructionWord> program, uint32_t initial_fp = 0x1000) : rom(std::move(program)), fp(initial_fp) {
+    // initial_fp: the stack height (basic/src/bin/valida.rs:348); initial_pc: the executable's (elf/src/lib.rs:68-72)
+    explicit BasicVm(std::vector<InstructionWord> program, uint32_t initial_fp = 0x1000, uint32_t initial_pc = 0)
+        : rom(std::move(program)), pc(initial_pc), fp(initial_fp) {
         program_counts.assign(rom.size(), 0);
     }
     Word read(uint32_t addr) {
         auto it = cells.find(addr);
-        if (it == cells.end()) throw std::runtime_error("memory chip: read before write: " + std::to_string(addr) + " (pc = " + std::to_string(pc) + ")");
+        if (it == cells.end())
+            throw std::runtime_error("memory chip: read before write: " + std::to_string(addr) + " (pc = " + std::to_string(pc) + ", opcode = " +
+                                     std::to_string(pc < rom.size() ? rom[pc].opcode : 0) + ")");
         Word w = word_of(it->second);
+        mem_ops.push_back({clock, addr, w, false});
+        return w;
+    }
+    // read_or_init (memory/src/lib.rs:107-120): a never-written cell reads as 0 — logged as a Read all the same, the cell stays unwritten
+    Word read_or_init(uint32_t addr) {
+        auto it = cells.find(addr);
+        Word w = it == cells.end() ? Word{{0, 0, 0, 0}} : word_of(it->second);
         mem_ops.push_back({clock, addr, w, false});
         return w;
     }
@@ -105,7 +120,8 @@ struct BasicVm {
     }
     // One Machine::step (basic/src/lib.rs:1066-1188).  Returns true on STOP.
     bool step() {
-        if (pc >= rom.size()) throw std::runtime_error("pc out of range");
+        if (pc >= rom.size())
+            throw std::runtime_error("workload VM: pc = " + std::to_string(pc) + " is beyond the ROM of " + std::to_string(rom.size()) + " instructions");
         const InstructionWord iw = rom[pc];
         const int32_t* o = iw.ops;
         const uint32_t pc0 = pc, fp0 = fp;
@@ -258,15 +274,46 @@ struct BasicVm {
                 pc += 1; push(CpuOp::Bus, iw, pc0, fp0);
                 break;
             }
-            default: throw std::runtime_error("workload VM: unsupported opcode " + std::to_string(iw.opcode));
+            case OP_READ_ADVICE: {  // cpu/src/lib.rs:398-436: the next advice byte as Word::from_u8, or Word::from(u32::MAX) at the end of the tape
+                const Word w = advice_pos < advice.size() ? Word{{0, 0, 0, advice[advice_pos++]}} : word_of(0xFFFFFFFFu);
+                write(at(o[0]), w);
+                pc += 1; push(CpuOp::ReadAdvice, iw, pc0, fp0); break;
+            }
+            case OP_LOADU8: case OP_LOADS8: {  // cpu/src/lib.rs:493-601
+                const uint32_t read_addr = u32_of(read(at(o[2])));
+                const Word cell = read(read_addr & ~3u);                // addr_of_word
+                const uint8_t byte = cell.b[3 - (read_addr & 3)];       // index_of_byte
+                const uint8_t fill = (iw.opcode == OP_LOADS8 && (byte & 0x80)) ? 0xFF : 0;  // Word::sign_extend_byte / Word::from_u8
+                write(at(o[0]) & ~3u, Word{{fill, fill, fill, byte}});
+                pc += 1; push(iw.opcode == OP_LOADU8 ? CpuOp::LoadU8 : CpuOp::LoadS8, iw, pc0, fp0); break;
+            }
+            case OP_STOREU8: {  // cpu/src/lib.rs:646-697: three reads (the last one read_or_init), then the write
+                const uint32_t read_addr = at(o[2]);
+                const uint32_t write_addr = u32_of(read(at(o[1])));
+                const Word cell = read(read_addr & ~3u);
+                const uint8_t byte = cell.b[3 - (read_addr & 3)];
+                const Word old = read_or_init(write_addr & ~3u);
+                // Word::update_byte (core.rs:46-57) reverses the cell's bytes ("little to big endian") before it replaces one — restated as written
+                Word nw{{old.b[3], old.b[2], old.b[1], old.b[0]}};
+                nw.b[3 - (write_addr & 3)] = byte;
+                write(write_addr & ~3u, nw);
+                pc += 1; push(CpuOp::StoreU8, iw, pc0, fp0); break;
+            }
+            default:  // basic/src/lib.rs:1175: "Unrecognized opcode: {}, pc = {}"
+                throw std::runtime_error("workload VM: unrecognized opcode " + std::to_string(iw.opcode) + ", pc = " + std::to_string(pc0));
         }
         program_counts[pc0]++;  // read_word(pc) (basic/src/lib.rs:1179)
         return iw.opcode == OP_STOP;
     }
     // Machine::run (basic/src/lib.rs:127-145)
+    // max_cycles: a run that has not stopped after that many cycles is refused
     void run(uint64_t max_cycles = (uint64_t)1 << 32) {
-        uint64_t n = 0;
-        while (!step()) if (++n > max_cycles) throw std::runtime_error("workload VM: cycle limit exceeded");
+        for (;;) {
+            if (clock >= max_cycles)
+                throw std::runtime_error("workload VM: cycle limit of " + std::to_string(max_cycles) + " cycles reached without STOP (pc = " + std::to_string(pc) +
+                                         ", opcode = " + std::to_string(pc < rom.size() ? rom[pc].opcode : 0) + ")");
+            if (step()) break;
+        }
         size_t pad = next_pow2(clock) - clock;
         program_counts[pc] += (uint32_t)pad;  // padded STOP reads
     }
@@ -305,8 +352,13 @@ struct BasicVm {
                 case CpuOp::BusLeftImm: r[cpu::IS_BUS_OP] = 1; set_imm(true); break;
                 case CpuOp::Stop: r[cpu::IS_STOP] = 1; break;
                 case CpuOp::LoadFp: r[cpu::IS_LOADFP] = 1; break;
+                case CpuOp::LoadU8: r[cpu::IS_LOAD_U8] = 1; break;
+                case CpuOp::LoadS8: r[cpu::IS_LOAD_S8] = 1; break;
+                case CpuOp::StoreU8: r[cpu::IS_STORE_U8] = 1; break;
+                case CpuOp::ReadAdvice: r[cpu::IS_ADVICE] = 1; break;
             }
-            // set_memory_channel_values (cpu/src/lib.rs:253-296)
+            // set_memory_channel_values (cpu/src/lib.rs:253-296): first read to channel 0, every later one to channel 1 (the last one wins: a
+            // STOREU8's three reads leave its second in no channel), the write to channel 2
             r[cpu::ch(0, cpu::CH_IS_READ)] = 1; r[cpu::ch(1, cpu::CH_IS_READ)] = 1; r[cpu::ch(2, cpu::CH_IS_READ)] = 0;
             bool is_left_imm = r[cpu::IS_LEFT_IMM_OP] == 1, is_first_read = true;
             for (size_t k = first[i]; k < first[i + 1]; k++) {

@@ -3,10 +3,13 @@ product — vgpu_verify — over a proof file.  Host-only: runs anywhere the lib
 
     python -m valida_amd.verify_cli PROOF [PROOF ...] --program fib --n 25 [--log-blowup 1] [--queries 40] [--pow-bits 8] [--poseidon-mmcs]
                                           [--constants splitmix|cli] [--device D] [--try-conventions]
+    python -m valida_amd.verify_cli PROOF [PROOF ...] --program-file EXECUTABLE [...]
 
 PROOF: the CBOR image the reference writes (`ciborium::into_writer(&proof, ..)`, either setting of the two encoding switches) or raw
 little-endian VPF1 words.  The program selects the preprocessed traces (ROM, range table) whose commitment the verifier recomputes
 (basic/src/lib.rs:791-804): fib N | alu ITERS | left_imm_ops | signed_inequality | loadfp | static_data.  Exit status 0 = accepted.
+--program-file EXECUTABLE: a Valida executable (raw machine code or ELF, Workload.from_executable) instead of a built-in program; it is
+loaded, not run — the preprocessed traces depend on its ROM alone.  --program / --n are then ignored.
 
 Several PROOF files: each is checked (one line per file, prefixed with its name); exit status 0 when every one is accepted.
 --device D: the batched verifier on GPU D (vgpu_verify_batch: Merkle openings, reduced openings and FRI folds on the device) instead of
@@ -33,6 +36,7 @@ def main(argv=None):
     ap.add_argument("proof", nargs="+")
     ap.add_argument("--program", default="fib")
     ap.add_argument("--n", type=int, default=25)
+    ap.add_argument("--program-file", default=None, help="a Valida executable (raw machine code or ELF) instead of --program")
     ap.add_argument("--log-blowup", type=int, default=1)
     ap.add_argument("--queries", type=int, default=40)
     ap.add_argument("--pow-bits", type=int, default=8)
@@ -44,7 +48,14 @@ def main(argv=None):
 
     import valida_amd as va
 
-    w = va.Workload.fib(args.n) if args.program == "fib" else va.Workload.alu(args.n) if args.program == "alu" else va.Workload.named(args.program)
+    if args.program_file is not None:
+        try:
+            w = va.Workload.from_executable(open(args.program_file, "rb").read(), max_cycles=0)
+        except (va.VgpuError, OSError) as e:
+            print("REJECTED: cannot load %s: %s" % (args.program_file, e))
+            return 1
+    else:
+        w = va.Workload.fib(args.n) if args.program == "fib" else va.Workload.alu(args.n) if args.program == "alu" else va.Workload.named(args.program)
     hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256
     machine = va.Machine.basic()
 
