@@ -318,6 +318,42 @@ int64_t vgpu_proof_debug_perm_trace(const vgpu_proof_t* pr, uint32_t chip, uint3
 int64_t vgpu_proof_debug_quotient(const vgpu_proof_t* pr, uint32_t chip, uint32_t* out, uint64_t cap_words);
 void vgpu_proof_free(vgpu_proof_t* pr);
 
+/* ---- Bus audit: WHICH LogUp tuples of a witness are unbalanced — the exact, challenge-free statement of which check_cumulative_sums
+ * (basic/src/lib.rs:373-375, the debug_flags & 2 path of vgpu_prove) is the randomised form.  Inputs: exactly what vgpu_prove takes.
+ *   record    one (chip, row, interaction) of Chip::all_interactions order (machine/src/chip.rs:40-63) whose count column is non-zero on that row;
+ *             its tuple = the interaction's fields on the row (canonical), its bus = (is_global, bus_index).
+ *   same tuple  two records of one bus whose field lists are equal after ZERO-PADDING to the widest interaction of that bus: the permutation
+ *             argument reduces a tuple as sum_j f_j beta^j (machine/src/chip.rs:121-208), so a trailing zero field is invisible to it
+ *             (BasicMachine: the cpu chip sends 14 fields on the general bus, every ALU chip receives 13).
+ *   net       sum of the counts of a tuple's send records minus that of its receive records, in F_p; unbalanced: net != 0.
+ *   order     records ascend by (chip, row, interaction); the report lists the tuples by their first record and, under each, its first
+ *             max_records_per_tuple records.  The report is exact (no hash decides it) and the same words run after run.
+ * Options: a zero field selects its default — max_tuples 64, max_records_per_tuple 4, hash_bits 64; opts may be NULL.  hash_bits is a test
+ * hook: the device's grouping key is cut to that many bits (1..64; more is refused), collisions become common, the report must not change.
+ * vgpu_bus_audit runs on the device (kernels/bus_audit.hip), queued on the prover context like a proof; scratch comes from the prover's pool:
+ * 60 bytes per (row, interaction) pair of the machine (live or not), 24 more per unbalanced tuple, plus the working-layout copy of every
+ * uploaded (not device-generated) trace; VGPU_ERR_OOM with a message when the pool cannot give them, VGPU_ERR_INVALID_ARG for more than
+ * 2^32 - 2 pairs.  vgpu_bus_audit_host is the same contract on the host over canonical row-major matrices (one thread, no device): for small
+ * programs on a box without a GPU.  Both validate shapes as vgpu_prove does.
+ * Report image (vgpu_bus_report_words, u32 words; u64 values as lo, hi):
+ *   [0] 0x31524256 "VBR1" [1] word count [2] balanced [3] truncated [4,5] total_unbalanced (exact even when the list is cut) [6] reported [7] n_buses
+ *   per bus, ascending (is_global, bus_index), 12 words: is_global, bus_index, width, 0, live records, send records, receive records, unbalanced tuples (u64 each)
+ *   per reported tuple: is_global, bus_index, width, net, send sum, receive sum (canonical), send records, receive records (u64 each), n_listed,
+ *                       width fields (padded), n_listed x (chip, row, interaction, is_send, count). */
+typedef struct vgpu_bus_audit_opts { uint64_t max_tuples; uint32_t max_records_per_tuple; uint32_t hash_bits; } vgpu_bus_audit_opts_t;
+typedef struct vgpu_bus_report vgpu_bus_report_t;
+int32_t vgpu_bus_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                       uint32_t n_prep, const vgpu_bus_audit_opts_t* opts, vgpu_bus_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_bus_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                            const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                            const vgpu_bus_audit_opts_t* opts, vgpu_bus_report_t** out);
+uint64_t vgpu_bus_report_len(const vgpu_bus_report_t* r);
+const uint32_t* vgpu_bus_report_words(const vgpu_bus_report_t* r);
+/* out[0]: the device pass (events around it on the prover's stream; 0 for the host audit), out[1]: wall time of the whole call; milliseconds */
+void vgpu_bus_report_timing(const vgpu_bus_report_t* r, double out[2]);
+void vgpu_bus_report_free(vgpu_bus_report_t* r);
+
 /* ---- RCCL inside the library: one process per GPU; the host's launcher distributes the 128-byte id that rank 0
  * obtains from vgpu_comm_unique_id (any out-of-band channel: MPI, a file, the Rust host's own RPC), every rank then calls
  * vgpu_comm_init with its prover.  vgpu_comm_allgather_roots is the path's one collective: each segment's commitment roots

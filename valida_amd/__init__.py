@@ -921,6 +921,98 @@ def prove_sharded_local(provers, main_traces, preprocessed, log_min_sharded=12, 
     return Proof(h)
 
 
+class BusAuditOpts(ctypes.Structure):  # vgpu_bus_audit_opts_t
+    _fields_ = [("max_tuples", ctypes.c_uint64), ("max_records_per_tuple", ctypes.c_uint32), ("hash_bits", ctypes.c_uint32)]
+
+
+BUS_NAMES = {(1, 0): "general", (1, 1): "program", (1, 2): "memory", (1, 3): "range"}  # BasicMachine's global buses (basic/src/lib.rs: bus indices)
+
+
+class BusReport:
+    """The bus audit of a witness (vgpu_bus_audit / vgpu_bus_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
+    balanced, truncated, total_unbalanced, reported, buses = [dict(bus=(is_global, bus_index), width, live, sends, receives, unbalanced)],
+    tuples = [dict(bus, fields, net, net_signed, send_sum, recv_sum, n_send, n_recv, records=[(chip, row, interaction, is_send, count)])],
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call)."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 8 or w[0] != 0x31524256 or w[1] != len(w):
+            raise ValueError("not a bus report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.balanced, self.truncated = bool(w[2]), bool(w[3])
+        self.total_unbalanced, self.reported = w[4] | (w[5] << 32), w[6]
+        self.device_ms, self.host_ms = float(device_ms), float(host_ms)
+        pos = 8
+        self.buses = []
+        for _ in range(w[7]):
+            live, sends, recvs, unb = (w[pos + 4 + 2 * k] | (w[pos + 5 + 2 * k] << 32) for k in range(4))
+            self.buses.append(dict(bus=(w[pos], w[pos + 1]), width=w[pos + 2], live=live, sends=sends, receives=recvs, unbalanced=unb))
+            pos += 12
+        self.tuples = []
+        for _ in range(self.reported):
+            width, net, n_listed = w[pos + 2], w[pos + 3], w[pos + 10]
+            t = dict(bus=(w[pos], w[pos + 1]), net=net, net_signed=net if net <= P // 2 else net - P, send_sum=w[pos + 4], recv_sum=w[pos + 5],
+                     n_send=w[pos + 6] | (w[pos + 7] << 32), n_recv=w[pos + 8] | (w[pos + 9] << 32), fields=w[pos + 11:pos + 11 + width])
+            pos += 11 + width
+            t["records"] = [tuple(w[pos + 5 * k:pos + 5 * k + 5]) for k in range(n_listed)]
+            pos += 5 * n_listed
+            self.tuples.append(t)
+        assert pos == len(w)
+
+    def to_json(self):
+        import json
+
+        return json.dumps(dict(balanced=self.balanced, truncated=self.truncated, total_unbalanced=self.total_unbalanced, reported=self.reported,
+                               device_ms=self.device_ms, host_ms=self.host_ms, buses=[dict(b, bus=list(b["bus"])) for b in self.buses],
+                               tuples=[dict(t, bus=list(t["bus"]), records=[list(r) for r in t["records"]]) for t in self.tuples]))
+
+
+def _bus_opts(max_tuples, max_records_per_tuple, hash_bits):
+    # in the C struct a zero field selects its default, so the refusals of explicit zeros are made here, with the library's status code
+    if not 1 <= int(hash_bits) <= 64:
+        raise VgpuError(-1, "bus_audit: hash_bits must be 1..64")
+    if int(max_tuples) < 1 or int(max_records_per_tuple) < 1:
+        raise VgpuError(-1, "bus_audit: max_tuples and max_records_per_tuple must be at least 1")
+    return BusAuditOpts(int(max_tuples), int(max_records_per_tuple), int(hash_bits))
+
+
+def _bus_report(h):
+    L = lib()
+    L.vgpu_bus_report_len.restype = ctypes.c_uint64
+    L.vgpu_bus_report_words.restype = c_u32p
+    L.vgpu_bus_report_len.argtypes = L.vgpu_bus_report_words.argtypes = L.vgpu_bus_report_free.argtypes = [ctypes.c_void_p]
+    try:
+        n = int(L.vgpu_bus_report_len(h))
+        words = np.ctypeslib.as_array(L.vgpu_bus_report_words(h), shape=(n,)).copy()
+        tm = (ctypes.c_double * 2)()
+        L.vgpu_bus_report_timing(h, tm)
+    finally:
+        L.vgpu_bus_report_free(h)
+    return BusReport(words, tm[0], tm[1])
+
+
+def bus_audit_host(machine, main_matrices, preprocessed, max_tuples=64, max_records_per_tuple=4, hash_bits=64):
+    """The bus audit on the HOST (vgpu_bus_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
+    [(chip index, matrix)].  hash_bits is accepted for symmetry with Prover.bus_audit (the host groups by full tuples)."""
+    opts = _bus_opts(max_tuples, max_records_per_tuple, hash_bits)
+    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
+    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
+    for m in mains + [m for _, m in preps]:
+        if m.ndim != 2:
+            raise VgpuError(-1, "bus_audit: traces are two-dimensional matrices")
+
+    def arrays(ms):
+        n = max(1, len(ms))
+        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
+
+    mp, mh, mw = arrays(mains)
+    pp, ph, pw = arrays([m for _, m in preps])
+    chips = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
+    h = ctypes.c_void_p()
+    _check(lib().vgpu_bus_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chips, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
+    return _bus_report(h)
+
+
 class Ticket:
     """An outstanding asynchronous proof (vgpu_prove_async); keeps its inputs alive until waited for."""
 
@@ -1072,6 +1164,17 @@ class Prover:
         _check(lib().vgpu_prove(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)),
                                 ctypes.c_uint32((1 if debug else 0) | (2 if check else 0)), ctypes.byref(h)))
         return Proof(h)
+
+    def bus_audit(self, main, preprocessed, max_tuples=64, max_records_per_tuple=4, hash_bits=64):
+        """Which bus tuples of this witness are unbalanced (vgpu_bus_audit; the exact form of check_cumulative_sums): the arguments of prove,
+        a BusReport back.  hash_bits < 64 is a test hook (the grouping key is cut; the report must not change)."""
+        opts = _bus_opts(max_tuples, max_records_per_tuple, hash_bits)
+        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
+        chips = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
+        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_bus_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
+        return _bus_report(h)
 
     def prove_async(self, main, preprocessed, keep=None):
         """Start Machine::prove on a host thread of the library; returns a Ticket (wait() -> Proof).  `keep`: further objects

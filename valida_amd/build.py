@@ -23,6 +23,7 @@ SOURCES = [
     "kernels/open.hip",
     "kernels/tracegen.hip",
     "kernels/verify.hip",
+    "kernels/bus_audit.hip",
     "host/prover.cpp",
     "host/sharded_prover.cpp",
     "capi.cpp",

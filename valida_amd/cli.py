@@ -1,8 +1,9 @@
-"""`valida run|prove|verify` for Valida executables (the reference's CLI: basic/src/bin/valida.rs:40-56, 330-449), on this backend.
+"""`valida run|prove|verify` (and `check`) for Valida executables (the reference's CLI: basic/src/bin/valida.rs:40-56, 330-449), on this backend.
 
     python -m valida_amd.cli run    PROGRAM OUTPUT_FILE [ADVICE] [--stack-height N] [--max-cycles N]
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
+    python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
 ADVICE: a file whose bytes are the advice tape (FixedAdviceProvider); without it the tape is empty (the reference reads stdin instead).
@@ -15,8 +16,14 @@ prove   the device path end to end: the VM on the host, its operation logs uploa
         phase times (milliseconds) goes to stderr.
 verify  loads PROGRAM without running it (the preprocessed commitment depends on the ROM alone) and runs valida_amd.verify_cli on PROOF_FILE.
 
+check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tuples are unbalanced, sent by which chip on which row, received by
+        nobody — what a proof every verifier rejects for its cumulative sums cannot say): the VM on the host, then either the device path of
+        `prove` up to the traces (operation logs uploaded, fourteen traces generated on GPU D, default 0) and the audit on the device, or, with
+        --host, host traces and the host audit.  Writes the JSON report to REPORT_FILE, prints one line per reported tuple (bus, fields, net, the
+        listed records; for a memory-bus tuple also pc and opcode of its cycle: cpu rows are indexed by clk) and a summary line.
+
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
-Exit status: 0 on success (run / prove done, proof accepted), 1 otherwise (the reference always exits 0)."""
+Exit status: 0 on success (run / prove done, proof accepted, witness balanced), 1 otherwise (the reference always exits 0)."""
 import argparse
 import json
 import sys
@@ -51,15 +58,51 @@ def prove_on_device(w, prover):
     return proof, main, times
 
 
+OPCODE_NAMES = {1: "LOAD32", 2: "STORE32", 3: "JAL", 4: "JALV", 5: "BEQ", 6: "BNE", 7: "IMM32", 8: "STOP", 9: "READ_ADVICE", 10: "LOADFP", 11: "LOADU8", 12: "LOADS8",
+                13: "STOREU8", 100: "ADD32", 101: "SUB32", 102: "MUL32", 103: "DIV32", 104: "LT32", 105: "SHL32", 106: "SHR32", 107: "AND32", 108: "OR32",
+                109: "XOR32", 110: "SDIV32", 111: "NE32", 112: "MULHU32", 113: "SRA32", 114: "MULHS32", 115: "LTE32", 116: "EQ32", 117: "SLT32", 118: "SLE32",
+                300: "WRITE"}  # opcodes/src/lib.rs:7-45
+CPU_PC, CPU_OPCODE = 1, 3  # cpu/src/columns.rs
+
+
+def report_lines(report, cpu_trace):
+    """One line per reported tuple of a BasicMachine bus report, and the summary line."""
+    import valida_amd as va
+
+    lines = []
+    for t in report.tuples:
+        bus = "%s bus" % va.BUS_NAMES[t["bus"]] if t["bus"] in va.BUS_NAMES else "bus (%s, %d)" % ("global" if t["bus"][0] else "local", t["bus"][1])
+        recs = ", ".join("%s row %d interaction %d %s %d" % (va.CHIP_NAMES[c] if c < len(va.CHIP_NAMES) else "chip %d" % c, row, m, "sends" if snd else "receives", cnt)
+                         for c, row, m, snd, cnt in t["records"])
+        more = t["n_send"] + t["n_recv"] - len(t["records"])
+        line = "%s %s net %+d (%d sent in %d records, %d received in %d): %s%s" % (
+            bus, t["fields"], t["net_signed"], t["send_sum"], t["n_send"], t["recv_sum"], t["n_recv"], recs, " and %d more" % more if more else "")
+        if t["bus"] == (1, 2) and len(t["fields"]) > 1 and t["fields"][1] < cpu_trace.shape[0]:  # memory bus: [is_read, clk, addr, value..]
+            clk = t["fields"][1]
+            op = int(cpu_trace[clk, CPU_OPCODE])
+            line += "; cycle %d: pc %d %s" % (clk, int(cpu_trace[clk, CPU_PC]), OPCODE_NAMES.get(op, "opcode %d" % op))
+        lines.append(line)
+    live = sum(b["live"] for b in report.buses)
+    if report.balanced:
+        lines.append("balanced: %d live bus records, no unbalanced tuple" % live)
+    else:
+        lines.append("unbalanced: %d tuples of %d live bus records do not cancel%s" % (
+            report.total_unbalanced, live, " (the first %d are listed)" % report.reported if report.truncated else ""))
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m valida_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
-    ap.add_argument("action", choices=["run", "prove", "verify"])
+    ap.add_argument("action", choices=["run", "prove", "verify", "check"])
     ap.add_argument("program")
     ap.add_argument("action_file")
     ap.add_argument("advice", nargs="?", default=None)
     ap.add_argument("--stack-height", type=int, default=16777216)
     ap.add_argument("--max-cycles", type=int, default=1 << 22)
     ap.add_argument("--device", type=int, default=None, help="GPU for prove (default 0) / verify (default: the host verifier)")
+    ap.add_argument("--host", action="store_true", help="check: host traces and the host audit (no GPU)")
+    ap.add_argument("--max-tuples", type=int, default=64)
+    ap.add_argument("--max-records", type=int, default=4)
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -83,6 +126,20 @@ def main(argv=None):
             with open(args.action_file, "wb") as f:
                 f.write(w.output())
             return 0
+        if args.action == "check":
+            if args.host:
+                report = va.bus_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_tuples=args.max_tuples, max_records_per_tuple=args.max_records)
+            else:
+                prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
+                log = prover.upload_oplog(w.oplog())
+                main = [prover.generate_trace(log, chip) for chip in range(va.NUM_CHIPS)]
+                prep = [(chip, prover.upload(m)) for chip, m in w.preprocessed()]
+                report = prover.bus_audit(main, prep, max_tuples=args.max_tuples, max_records_per_tuple=args.max_records)
+            with open(args.action_file, "w") as f:
+                f.write(report.to_json() + "\n")
+            for line in report_lines(report, w.main_trace(0)):
+                print(line)
+            return 0 if report.balanced else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256
         rc = va.poseidon_round_constants(source=args.constants)
         prover = va.Prover(va.Machine.basic(), rc, device=args.device or 0, log_blowup=args.log_blowup, num_queries=args.queries, pow_bits=args.pow_bits,

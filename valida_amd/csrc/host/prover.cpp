@@ -1125,4 +1125,166 @@ PcsOpening Prover::open_multi_batches(const std::vector<OpenRound>& rounds, Chal
     return res;
 }
 
+
+// ---- bus audit (host/bus_audit.hpp; kernels/bus_audit.hip) ------------------------------------------------------------------------------
+namespace {
+struct BusAuditNoMemory : std::bad_alloc {  // the pool cannot give the pass its scratch: VGPU_ERR_OOM with a message that says how much it needs
+    std::string msg;
+    explicit BusAuditNoMemory(std::string m) : msg(std::move(m)) {}
+    const char* what() const noexcept override { return msg.c_str(); }
+};
+}  // namespace
+
+BusReport Prover::bus_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const BusAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const BusAuditOpts o = bus_audit_checked_opts(opts_in);
+    std::vector<BusShape> ms, ps;
+    std::vector<int> prep_chips, prep_slot;
+    for (auto t : main) { if (!t) throw std::invalid_argument("bus_audit: null trace"); ms.push_back({t->height, t->width}); }
+    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("bus_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
+    BusPlan plan = bus_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
+    const uint64_t n = plan.n_slots;
+    if (n >= 0xffffffffull) throw std::invalid_argument("bus_audit: more than 2^32 - 2 (row, interaction) pairs; record ids are 32-bit");
+
+    DeviceCtx& c = *ctx_;
+    c.activate();
+    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
+    c.activate();
+    struct Running {
+        std::atomic<int>& n;
+        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
+        ~Running() { n.fetch_sub(1); }
+    } running(c.proofs_running);
+    const size_t NC = machine_.airs.size(), NB = plan.buses.size();
+    hipStream_t st = c.stream;
+
+    BusReport rep;
+    rep.buses = plan.buses;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
+    VG_HIP_CHECK(hipEventCreate(&ev0));
+    VG_HIP_CHECK(hipEventCreate(&ev1));
+    try {
+        // working-layout copies, as prove makes them (traces generated on the device are already column-major Montgomery)
+        std::vector<DMat> own;
+        std::vector<const uint32_t*> mptr(NC, nullptr), pptr(NC, nullptr);
+        std::vector<uint64_t> mstride(NC, 0), pstride(NC, 0);
+        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
+            if (!t->nat.empty()) return t->nat.view();
+            own.emplace_back(&c, t->height, t->width);
+            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
+            return own.back().view();
+        };
+        own.reserve(NC + preprocessed.size());
+        VG_HIP_CHECK(hipEventRecord(ev0, st));
+        for (size_t i = 0; i < NC; i++) {
+            if (!plan.chips[i].M) continue;  // a chip without interactions is not read
+            const vk::DMatView v = working(main[i]);
+            mptr[i] = v.data; mstride[i] = v.stride;
+            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); pptr[i] = pv.data; pstride[i] = pv.stride; }
+        }
+        c.check_launch("bus_audit ingest");
+        DBuf desc(&c, bus_audit_descriptor(machine_, plan, mptr, mstride, pptr, pstride));
+
+        uint32_t total_inter = 0;
+        std::vector<uint32_t> inter_base(NC, 0);
+        for (size_t i = 0; i < NC; i++) { inter_base[i] = total_inter; total_inter += plan.chips[i].M; }
+        const size_t n_counters = 8 + NB + total_inter;
+        const uint64_t na = n ? n : 1;
+        DBuf keys2(&c, (size_t)(4 * na)), ids2(&c, (size_t)(2 * na)), cnt(&c, (size_t)na), gid(&c, (size_t)na), head_pos(&c, (size_t)na), sums(&c, (size_t)(4 * na)),
+            nrec(&c, (size_t)(2 * na)), sort_tmp(&c, vk::bus_audit_sort_scratch_words(na)), scan_tmp(&c, vk::bus_audit_scan_scratch_words(na)), counters(&c, n_counters);
+        unsigned long long* keys = (unsigned long long*)keys2.data;
+        unsigned long long* sums_p = (unsigned long long*)sums.data;
+        VG_HIP_CHECK(hipMemsetAsync(counters.data, 0, n_counters * 4, st));
+        VG_HIP_CHECK(hipMemsetAsync(sums.data, 0, (size_t)(4 * na) * 4, st));
+        VG_HIP_CHECK(hipMemsetAsync(nrec.data, 0, (size_t)(2 * na) * 4, st));
+
+        for (size_t i = 0; i < NC; i++)
+            vk::launch_ba_records(st, desc.data, (uint32_t)i, plan.chips[i].height, machine_.airs[i].width, plan.chips[i].M, o.hash_bits, keys, ids2.data, cnt.data,
+                                  counters.data + 8 + NB + inter_base[i]);
+        int shifts[8], n_shifts = 0;
+        for (uint32_t b = 0; b < (o.hash_bits + 7) / 8; b++) shifts[n_shifts++] = 8 * (int)b;
+        if (o.hash_bits <= 56) shifts[n_shifts++] = 56;  // the pass that sinks the dead slots (key ~0) behind the live ones
+        int half = vk::launch_ba_sort(st, keys, ids2.data, n, sort_tmp.data, shifts, n_shifts, 0);
+        vk::launch_ba_groups(st, desc.data, keys + (uint64_t)half * n, ids2.data + (uint64_t)half * n, n, false, gid.data, head_pos.data, scan_tmp.data, counters.data);
+        vk::launch_ba_reduce(st, desc.data, ids2.data + (uint64_t)half * n, cnt.data, gid.data, head_pos.data, n, true, sums_p, nrec.data, counters.data);
+        vk::launch_ba_select(st, desc.data, ids2.data + (uint64_t)half * n, head_pos.data, sums_p, n, false, 0, nullptr, nullptr, counters.data);
+        c.check_launch("bus_audit");
+        std::vector<uint32_t> cw(n_counters);
+        c.download_small(cw.data(), counters.data, n_counters * 4);
+
+        if (cw[2]) {
+            // a key collision (with 64 key bits: practically never; the hash_bits test hook forces it): group by the full padded tuples instead.
+            // Words [bus slot, field 0, ..]: two per radix sort, least significant pair first; the sorts are stable, ids start ascending.
+            VG_HIP_CHECK(hipMemsetAsync(counters.data + 1, 0, (7 + NB) * 4, st));
+            VG_HIP_CHECK(hipMemsetAsync(sums.data, 0, (size_t)(4 * na) * 4, st));
+            VG_HIP_CHECK(hipMemsetAsync(nrec.data, 0, (size_t)(2 * na) * 4, st));
+            const int all[8] = {0, 8, 16, 24, 32, 40, 48, 56};
+            half = 0;
+            vk::launch_ba_iota(st, ids2.data, n);
+            for (int chunk = (int)(plan.wmax + 1 + 1) / 2 - 1; chunk >= 0; chunk--) {
+                vk::launch_ba_rekey(st, desc.data, (uint32_t)chunk, ids2.data + (uint64_t)half * n, cnt.data, keys + (uint64_t)half * n, n);
+                half = vk::launch_ba_sort(st, keys, ids2.data, n, sort_tmp.data, all, 8, half);
+            }
+            vk::launch_ba_groups(st, desc.data, keys + (uint64_t)half * n, ids2.data + (uint64_t)half * n, n, true, gid.data, head_pos.data, scan_tmp.data, counters.data);
+            vk::launch_ba_reduce(st, desc.data, ids2.data + (uint64_t)half * n, cnt.data, gid.data, head_pos.data, n, false, sums_p, nrec.data, counters.data);
+            vk::launch_ba_select(st, desc.data, ids2.data + (uint64_t)half * n, head_pos.data, sums_p, n, false, 0, nullptr, nullptr, counters.data);
+            c.check_launch("bus_audit exact");
+            c.download_small(cw.data(), counters.data, n_counters * 4);
+        }
+        const uint32_t n_unb = cw[3];
+        rep.total_unbalanced = n_unb;
+        for (size_t b = 0; b < NB; b++) rep.buses[b].unbalanced = cw[8 + b];
+        for (size_t i = 0; i < NC; i++)
+            for (uint32_t m = 0; m < plan.chips[i].M; m++) {
+                BusStat& b = rep.buses[plan.chips[i].bus_slot[m]];
+                const uint64_t live = cw[8 + NB + inter_base[i] + m];
+                b.live += live;
+                (machine_.airs[i].interactions[m].is_send() ? b.sends : b.receives) += live;
+            }
+        if (n_unb) {
+            const uint32_t n_rep = (uint32_t)std::min<uint64_t>(n_unb, o.max_tuples), R = o.max_records_per_tuple, stride = 8 + plan.wmax + 2 * R;
+            DBuf ukeys(&c, (size_t)4 * n_unb), uvals(&c, (size_t)2 * n_unb), out(&c, (size_t)n_rep * stride);
+            vk::launch_ba_select(st, desc.data, ids2.data + (uint64_t)half * n, head_pos.data, sums_p, cw[1], true, n_unb, (unsigned long long*)ukeys.data, uvals.data, counters.data);
+            const int id_bytes[4] = {0, 8, 16, 24};  // keys are 32-bit record ids
+            const int uh = vk::launch_ba_sort(st, (unsigned long long*)ukeys.data, uvals.data, n_unb, sort_tmp.data, id_bytes, 4, 0);
+            vk::launch_ba_report(st, desc.data, ids2.data + (uint64_t)half * n, cnt.data, head_pos.data, sums_p, nrec.data, uvals.data + (uint64_t)uh * n_unb, n_rep, R, out.data);
+            c.check_launch("bus_audit report");
+            std::vector<uint32_t> w((size_t)n_rep * stride);
+            c.download_small(w.data(), out.data, w.size() * 4);
+            for (uint32_t t = 0; t < n_rep; t++) {
+                const uint32_t* e = w.data() + (size_t)t * stride;
+                const BusStat& bus = plan.buses.at(e[0]);
+                BusTuple bt;
+                bt.is_global = bus.is_global; bt.bus_index = bus.bus_index;
+                bt.fields.assign(e + 8, e + 8 + bus.width);
+                bt.send_sum = (uint32_t)((((uint64_t)e[3] << 32) | e[2]) % vg::P);
+                bt.recv_sum = (uint32_t)((((uint64_t)e[5] << 32) | e[4]) % vg::P);
+                bt.net = (bt.send_sum + vg::P - bt.recv_sum) % vg::P;
+                bt.n_send = e[6]; bt.n_recv = e[7];
+                for (uint32_t k = 0; k < e[1] && k < R; k++) {
+                    BusRecord r = plan.decode(e[8 + plan.wmax + 2 * k]);
+                    r.is_send = machine_.airs[r.chip].interactions[r.interaction].is_send() ? 1u : 0u;
+                    r.count = e[8 + plan.wmax + 2 * k + 1];
+                    bt.records.push_back(r);
+                }
+                rep.tuples.push_back(std::move(bt));
+            }
+        }
+        VG_HIP_CHECK(hipEventRecord(ev1, st));
+        c.sync();
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
+    } catch (const BusAuditNoMemory&) {
+        throw;
+    } catch (const std::bad_alloc&) {
+        (void)hipStreamSynchronize(st);
+        throw BusAuditNoMemory("bus_audit: the device pool cannot give the pass its scratch: " + std::to_string(BUS_AUDIT_BYTES_PER_SLOT) + " bytes for each of the " +
+                               std::to_string(n) + " (row, interaction) pairs, 24 more per unbalanced tuple, plus the working-layout copies of uploaded traces");
+    }
+    bus_audit_finish(rep, o);
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 }  // namespace vhost

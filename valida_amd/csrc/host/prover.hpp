@@ -5,6 +5,7 @@
 #include <chrono>
 #include <map>
 #include <memory>
+#include "bus_audit.hpp"
 #include "challenger.hpp"
 #include "machine.hpp"
 #include "pcs.hpp"
@@ -101,6 +102,11 @@ class Prover {
     // main[i]: trace of chip i (chip order).  preprocessed: (chip index, trace) in chip order.
     std::vector<uint32_t> prove(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
                                 PhaseTimes* times = nullptr, ProveDebugOut* dbg = nullptr);
+
+    // Bus audit of a witness (host/bus_audit.hpp, kernels/bus_audit.hip): the same trace handles as prove, queued on the context like a proof.
+    // Scratch from the pool: BUS_AUDIT_BYTES_PER_SLOT per (row, interaction) pair, 24 more per unbalanced tuple.
+    static constexpr uint64_t BUS_AUDIT_BYTES_PER_SLOT = 60;
+    BusReport bus_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const BusAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

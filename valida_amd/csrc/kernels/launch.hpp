@@ -147,6 +147,24 @@ hipError_t launch_tracegen_range(hipStream_t st, const TgCpuOp* ops, uint64_t n,
 void launch_tracegen_alu2(hipStream_t st, int chip, const TgAluOp* ops, uint64_t n, DMatView t);
 void launch_tracegen_output(hipStream_t st, const TgOutOp* vals, const uint32_t* row0, uint64_t n, uint64_t n_rows, DMatView t);
 hipError_t launch_tracegen_program(hipStream_t st, const TgCpuOp* ops, uint64_t n, uint64_t padded_n, uint32_t rom_len, uint32_t* counts, DMatView t);
+// bus_audit.hip — the passes of the bus audit (host/bus_audit.hpp: contract, descriptor layout `desc`; Prover::bus_audit drives them).
+// n = record slots = sum over chips of height x interactions.  keys2 / ids2: [2 n] ping-pong halves; cnt, gid, head_pos: [n]; sums, nrec: [2 n];
+// counters: [8 + buses] words; sort / scan scratch: the word counts below.
+size_t bus_audit_sort_scratch_words(uint64_t n);
+size_t bus_audit_scan_scratch_words(uint64_t n);
+void launch_ba_records(hipStream_t st, const uint32_t* desc, uint32_t chip, uint64_t height, uint32_t width, uint32_t M, uint32_t hash_bits, unsigned long long* keys, uint32_t* ids,
+                       uint32_t* cnt, uint32_t* live_out);
+void launch_ba_iota(hipStream_t st, uint32_t* ids, uint64_t n);
+void launch_ba_rekey(hipStream_t st, const uint32_t* desc, uint32_t chunk, const uint32_t* ids, const uint32_t* cnt, unsigned long long* keys, uint64_t n);
+int launch_ba_sort(hipStream_t st, unsigned long long* keys2, uint32_t* vals2, uint64_t n, uint32_t* counts, const int* shifts, int n_shifts, int half);
+void launch_ba_groups(hipStream_t st, const uint32_t* desc, const unsigned long long* keys, const uint32_t* ids, uint64_t n, bool exact, uint32_t* gid, uint32_t* head_pos,
+                      uint32_t* scan_tmp, uint32_t* counters);
+void launch_ba_reduce(hipStream_t st, const uint32_t* desc, const uint32_t* ids, const uint32_t* cnt, const uint32_t* gid, const uint32_t* head_pos, uint64_t n, bool check,
+                      unsigned long long* sums, uint32_t* nrec, uint32_t* counters);
+void launch_ba_select(hipStream_t st, const uint32_t* desc, const uint32_t* ids, const uint32_t* head_pos, const unsigned long long* sums, uint64_t n_groups_max, bool collect,
+                      uint32_t cap, unsigned long long* ukeys, uint32_t* uvals, uint32_t* counters);
+void launch_ba_report(hipStream_t st, const uint32_t* desc, const uint32_t* ids, const uint32_t* cnt, const uint32_t* head_pos, const unsigned long long* sums, const uint32_t* nrec,
+                      const uint32_t* uvals, uint32_t n_rep, uint32_t R, uint32_t* out);
 // open.hip
 void launch_bary_weights(hipStream_t st, uint64_t n, const uint32_t* min_poly_dev, Fp shift, const DeviceTables& tb, uint32_t* w);
 // the same for several (height, point) pairs in one launch: job = { first block (u32), pad, n (u64), min-poly pointer, weight buffer, digit-plane image (or null) }
