@@ -354,6 +354,48 @@ const uint32_t* vgpu_bus_report_words(const vgpu_bus_report_t* r);
 void vgpu_bus_report_timing(const vgpu_bus_report_t* r, double out[2]);
 void vgpu_bus_report_free(vgpu_bus_report_t* r);
 
+/* ---- Constraint audit: WHICH AIR constraints of a witness fail, on which rows, with which value — check_constraints
+ * (machine/src/check_constraints.rs:14-84, called per chip from basic/src/lib.rs:270-277; the debug_flags & 2 path of vgpu_prove reports one
+ * (row, constraint) of the first failing chip) made exact and complete.  Inputs: exactly what vgpu_prove and vgpu_bus_audit take.
+ *   domain      the trace itself: row r of chip c of height n has next = (r + 1) mod n; is_first_row = [r == 0], is_last_row = [r == n - 1],
+ *               is_transition = [r != n - 1], as 0/1 field values (check_constraints.rs:37, :69-79).
+ *   constraint  k of a chip = the k-th assert_zero of its Air::eval, in call order (for a vgpu_air_* captured AIR: the k-th vgpu_air_assert_zero);
+ *               it fails on row r when its value there is non-zero.  Only Air::eval is audited: the three permutation / running-sum constraints
+ *               depend on sampled challenges, and their exact statement is the bus audit above.
+ *   order       entries ascend by (chip, constraint); under each, its first max_rows_per_constraint failing rows in ascending row order, each
+ *               with the canonical value of the constraint polynomial on that row.  Only the first max_constraints failing (chip, constraint)
+ *               pairs are listed; the totals stay exact and `truncated` says the list was cut.  No challenge enters: the report is exact and the
+ *               same words run after run, for Machine.basic (compiled chip templates) and for captured AIRs (the interpreted program) alike.
+ * Options: a zero field selects its default — max_constraints 64, max_rows_per_constraint 4 (at most 2^24 and 4096); opts may be NULL;
+ * reserved != 0 is refused.
+ * vgpu_constraint_audit runs on the device (kernels/constraint_audit.hip), queued on the prover context like a proof or a bus audit; it accepts
+ * device-generated and uploaded traces, and traces of another context of the same device.  Chips without constraints are not read.  Scratch
+ * comes from the prover's pool: 8 bytes per (constraint, workgroup of T rows) of every chip with constraints, i.e. at most 8 K / T bytes per
+ * row (K <= 96 constraints, T = 256 rows, down to 64 for a captured AIR with a large register file: 3 to 12 bytes per row), 8 (K + 1) per chip,
+ * 8 bytes per (constraint, listed row slot) of a failing chip, plus the working-layout copy of every uploaded (not device-generated) trace;
+ * VGPU_ERR_OOM with a message when the pool cannot give them; VGPU_ERR_INVALID_ARG for bad shapes and for a chip of more than 96 constraints.
+ * vgpu_constraint_audit_host is the same contract on the host over canonical row-major matrices (one thread, no device, any number of
+ * constraints).  Both validate shapes as vgpu_prove does.
+ * Report image (vgpu_constraint_report_words, u32 words; u64 values as lo, hi):
+ *   [0] 0x31524356 "VCR1" [1] word count [2] satisfied [3] truncated [4,5] total_failing = failing (chip, constraint) pairs (exact even when
+ *   the list is cut) [6] reported [7] n_chips
+ *   per chip, in machine order, 6 words: constraints, failing constraints, height (u64), rows failing at least one constraint (u64)
+ *   per reported constraint: chip, constraint, failing rows (u64), n_listed, then n_listed x (row, value). */
+typedef struct vgpu_constraint_audit_opts { uint64_t max_constraints; uint32_t max_rows_per_constraint; uint32_t reserved; } vgpu_constraint_audit_opts_t;
+typedef struct vgpu_constraint_report vgpu_constraint_report_t;
+int32_t vgpu_constraint_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                              uint32_t n_prep, const vgpu_constraint_audit_opts_t* opts, vgpu_constraint_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_constraint_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                                   const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                                   const vgpu_constraint_audit_opts_t* opts, vgpu_constraint_report_t** out);
+uint64_t vgpu_constraint_report_len(const vgpu_constraint_report_t* r);
+const uint32_t* vgpu_constraint_report_words(const vgpu_constraint_report_t* r);
+/* out[0]: the device pass (events around it on the prover's stream, after the working-layout copies of uploaded traces; 0 for the host audit),
+ * out[1]: wall time of the whole call; milliseconds */
+void vgpu_constraint_report_timing(const vgpu_constraint_report_t* r, double out[2]);
+void vgpu_constraint_report_free(vgpu_constraint_report_t* r);
+
 /* ---- RCCL inside the library: one process per GPU; the host's launcher distributes the 128-byte id that rank 0
  * obtains from vgpu_comm_unique_id (any out-of-band channel: MPI, a file, the Rust host's own RPC), every rank then calls
  * vgpu_comm_init with its prover.  vgpu_comm_allgather_roots is the path's one collective: each segment's commitment roots

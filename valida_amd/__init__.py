@@ -1013,6 +1013,94 @@ def bus_audit_host(machine, main_matrices, preprocessed, max_tuples=64, max_reco
     return _bus_report(h)
 
 
+class ConstraintAuditOpts(ctypes.Structure):  # vgpu_constraint_audit_opts_t
+    _fields_ = [("max_constraints", ctypes.c_uint64), ("max_rows_per_constraint", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class ConstraintReport:
+    """The constraint audit of a witness (vgpu_constraint_audit / vgpu_constraint_audit_host; the contract is stated in include/vgpu.h), as plain
+    Python values: satisfied, truncated, total_failing (failing (chip, constraint) pairs), reported,
+    chips = [dict(chip, constraints, failing_constraints, height, failing_rows)], constraints = [dict(chip, constraint, failing_rows,
+    rows=[(row, value)])] ascending by (chip, constraint), device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call)."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 8 or w[0] != 0x31524356 or w[1] != len(w):
+            raise ValueError("not a constraint report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.satisfied, self.truncated = bool(w[2]), bool(w[3])
+        self.total_failing, self.reported = w[4] | (w[5] << 32), w[6]
+        self.device_ms, self.host_ms = float(device_ms), float(host_ms)
+        pos = 8
+        self.chips = []
+        for c in range(w[7]):
+            self.chips.append(dict(chip=c, constraints=w[pos], failing_constraints=w[pos + 1], height=w[pos + 2] | (w[pos + 3] << 32), failing_rows=w[pos + 4] | (w[pos + 5] << 32)))
+            pos += 6
+        self.constraints = []
+        for _ in range(self.reported):
+            n_listed = w[pos + 4]
+            e = dict(chip=w[pos], constraint=w[pos + 1], failing_rows=w[pos + 2] | (w[pos + 3] << 32))
+            pos += 5
+            e["rows"] = [(w[pos + 2 * k], w[pos + 2 * k + 1]) for k in range(n_listed)]
+            pos += 2 * n_listed
+            self.constraints.append(e)
+        assert pos == len(w)
+
+    def to_dict(self):
+        return dict(satisfied=self.satisfied, truncated=self.truncated, total_failing=self.total_failing, reported=self.reported, device_ms=self.device_ms,
+                    host_ms=self.host_ms, chips=self.chips, constraints=[dict(e, rows=[list(r) for r in e["rows"]]) for e in self.constraints])
+
+    def to_json(self):
+        import json
+
+        return json.dumps(self.to_dict())
+
+
+def _constraint_opts(max_constraints, max_rows_per_constraint):
+    # in the C struct a zero field selects its default, so the refusals of explicit zeros are made here, with the library's status code
+    if int(max_constraints) < 1 or int(max_rows_per_constraint) < 1:
+        raise VgpuError(-1, "constraint_audit: max_constraints and max_rows_per_constraint must be at least 1")
+    return ConstraintAuditOpts(int(max_constraints), int(max_rows_per_constraint), 0)
+
+
+def _constraint_report(h):
+    L = lib()
+    L.vgpu_constraint_report_len.restype = ctypes.c_uint64
+    L.vgpu_constraint_report_words.restype = c_u32p
+    L.vgpu_constraint_report_len.argtypes = L.vgpu_constraint_report_words.argtypes = L.vgpu_constraint_report_free.argtypes = [ctypes.c_void_p]
+    L.vgpu_constraint_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    try:
+        n = int(L.vgpu_constraint_report_len(h))
+        words = np.ctypeslib.as_array(L.vgpu_constraint_report_words(h), shape=(n,)).copy()
+        tm = (ctypes.c_double * 2)()
+        L.vgpu_constraint_report_timing(h, tm)
+    finally:
+        L.vgpu_constraint_report_free(h)
+    return ConstraintReport(words, tm[0], tm[1])
+
+
+def constraint_audit_host(machine, main_matrices, preprocessed, max_constraints=64, max_rows_per_constraint=4):
+    """The constraint audit on the HOST (vgpu_constraint_audit_host: no device, one thread): main_matrices = one canonical matrix per chip,
+    preprocessed = [(chip index, matrix)]; a ConstraintReport back."""
+    opts = _constraint_opts(max_constraints, max_rows_per_constraint)
+    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
+    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
+    for m in mains + [m for _, m in preps]:
+        if m.ndim != 2:
+            raise VgpuError(-1, "constraint_audit: traces are two-dimensional matrices")
+
+    def arrays(ms):
+        n = max(1, len(ms))
+        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
+
+    mp, mh, mw = arrays(mains)
+    pp, ph, pw = arrays([m for _, m in preps])
+    chips = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
+    h = ctypes.c_void_p()
+    _check(lib().vgpu_constraint_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chips, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
+    return _constraint_report(h)
+
+
 class Ticket:
     """An outstanding asynchronous proof (vgpu_prove_async); keeps its inputs alive until waited for."""
 
@@ -1175,6 +1263,17 @@ class Prover:
         h = ctypes.c_void_p()
         _check(lib().vgpu_bus_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
         return _bus_report(h)
+
+    def constraint_audit(self, main, preprocessed, max_constraints=64, max_rows_per_constraint=4):
+        """Which AIR constraints of this witness fail, on which rows, with which value (vgpu_constraint_audit; check_constraints made exact and
+        complete): the arguments of prove, a ConstraintReport back."""
+        opts = _constraint_opts(max_constraints, max_rows_per_constraint)
+        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
+        chips = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
+        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_constraint_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
+        return _constraint_report(h)
 
     def prove_async(self, main, preprocessed, keep=None):
         """Start Machine::prove on a host thread of the library; returns a Ticket (wait() -> Proof).  `keep`: further objects

@@ -24,6 +24,7 @@ SOURCES = [
     "kernels/tracegen.hip",
     "kernels/verify.hip",
     "kernels/bus_audit.hip",
+    "kernels/constraint_audit.hip",
     "host/prover.cpp",
     "host/sharded_prover.cpp",
     "capi.cpp",

@@ -4,6 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
+                                                                [--constraints] [--max-constraints N]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
 ADVICE: a file whose bytes are the advice tape (FixedAdviceProvider); without it the tape is empty (the reference reads stdin instead).
@@ -21,9 +22,15 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         `prove` up to the traces (operation logs uploaded, fourteen traces generated on GPU D, default 0) and the audit on the device, or, with
         --host, host traces and the host audit.  Writes the JSON report to REPORT_FILE, prints one line per reported tuple (bus, fields, net, the
         listed records; for a memory-bus tuple also pc and opcode of its cycle: cpu rows are indexed by clk) and a summary line.
+        --constraints adds the constraint audit of the same witness (vgpu_constraint_audit: which AIR constraints fail, on which rows, with
+        which value — what check_constraints and the debug path of `prove` report one chip and one row at a time), on the same path as the bus
+        audit (device or --host).  The JSON report gets one more key, "constraints" (ConstraintReport.to_json's object); after the bus lines
+        stdout gets one line per listed constraint, `<chip> constraint <k> fails on <count> rows: row r = value, ..` (for a cpu row also pc and
+        opcode), and a summary line `satisfied: ..` or `violated: N constraints of M chips ..`; --max-constraints N cuts the list (default 64).
+        Without the flag `check` does what it did before the flag existed, byte for byte.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
-Exit status: 0 on success (run / prove done, proof accepted, witness balanced), 1 otherwise (the reference always exits 0)."""
+Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
 import argparse
 import json
 import sys
@@ -91,6 +98,32 @@ def report_lines(report, cpu_trace):
     return lines
 
 
+def constraint_lines(report, cpu_trace):
+    """One line per listed constraint of a constraint report, and the summary line."""
+    import valida_amd as va
+
+    lines = []
+    for e in report.constraints:
+        name = va.CHIP_NAMES[e["chip"]] if e["chip"] < len(va.CHIP_NAMES) else "chip %d" % e["chip"]
+        rows = []
+        for row, value in e["rows"]:
+            text = "row %d = %d" % (row, value)
+            if e["chip"] == 0 and row < cpu_trace.shape[0]:
+                op = int(cpu_trace[row, CPU_OPCODE])
+                text += " (pc %d %s)" % (int(cpu_trace[row, CPU_PC]), OPCODE_NAMES.get(op, "opcode %d" % op))
+            rows.append(text)
+        more = e["failing_rows"] - len(e["rows"])
+        lines.append("%s constraint %d fails on %d rows: %s%s" % (name, e["constraint"], e["failing_rows"], ", ".join(rows), " and %d more" % more if more else ""))
+    n_constraints = sum(c["constraints"] for c in report.chips)
+    if report.satisfied:
+        lines.append("satisfied: all %d constraints of %d chips hold on every row" % (n_constraints, len(report.chips)))
+    else:
+        lines.append("violated: %d constraints of %d chips fail, on %d rows%s" % (
+            report.total_failing, sum(1 for c in report.chips if c["failing_constraints"]), sum(c["failing_rows"] for c in report.chips),
+            " (the first %d are listed)" % report.reported if report.truncated else ""))
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m valida_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("action", choices=["run", "prove", "verify", "check"])
@@ -103,6 +136,8 @@ def main(argv=None):
     ap.add_argument("--host", action="store_true", help="check: host traces and the host audit (no GPU)")
     ap.add_argument("--max-tuples", type=int, default=64)
     ap.add_argument("--max-records", type=int, default=4)
+    ap.add_argument("--constraints", action="store_true", help="check: also the constraint audit (which AIR constraints fail on which rows)")
+    ap.add_argument("--max-constraints", type=int, default=64)
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -129,17 +164,22 @@ def main(argv=None):
         if args.action == "check":
             if args.host:
                 report = va.bus_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_tuples=args.max_tuples, max_records_per_tuple=args.max_records)
+                creport = va.constraint_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_constraints=args.max_constraints) if args.constraints else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
                 main = [prover.generate_trace(log, chip) for chip in range(va.NUM_CHIPS)]
                 prep = [(chip, prover.upload(m)) for chip, m in w.preprocessed()]
                 report = prover.bus_audit(main, prep, max_tuples=args.max_tuples, max_records_per_tuple=args.max_records)
+                creport = prover.constraint_audit(main, prep, max_constraints=args.max_constraints) if args.constraints else None
+            text = report.to_json()
+            if creport is not None:
+                text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
             with open(args.action_file, "w") as f:
-                f.write(report.to_json() + "\n")
-            for line in report_lines(report, w.main_trace(0)):
+                f.write(text + "\n")
+            for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []):
                 print(line)
-            return 0 if report.balanced else 1
+            return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256
         rc = va.poseidon_round_constants(source=args.constants)
         prover = va.Prover(va.Machine.basic(), rc, device=args.device or 0, log_blowup=args.log_blowup, num_queries=args.queries, pow_bits=args.pow_bits,

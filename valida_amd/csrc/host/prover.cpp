@@ -1287,4 +1287,136 @@ BusReport Prover::bus_audit(const std::vector<const DeviceTrace*>& main, const s
     return rep;
 }
 
+// ---- constraint audit (host/constraint_audit.hpp; kernels/constraint_audit.hip) ------------------------------------------------------------
+ConstraintReport Prover::constraint_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
+                                          const ConstraintAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const ConstraintAuditOpts o = constraint_audit_checked_opts(opts_in);
+    std::vector<ConstraintShape> ms, ps;
+    std::vector<int> prep_chips, prep_slot;
+    for (auto t : main) { if (!t) throw std::invalid_argument("constraint_audit: null trace"); ms.push_back({t->height, t->width}); }
+    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("constraint_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
+    constraint_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
+    const size_t NC = machine_.airs.size();
+    for (size_t i = 0; i < NC; i++)
+        if (machine_.airs[i].program.num_asserts > vk::CA_MAX_CONSTRAINTS)
+            throw std::invalid_argument("constraint_audit: chip " + machine_.airs[i].name + " has " + std::to_string(machine_.airs[i].program.num_asserts) + " constraints; the device audit handles up to " +
+                                        std::to_string(vk::CA_MAX_CONSTRAINTS) + " per chip (the host audit has no limit)");
+
+    DeviceCtx& c = *ctx_;
+    c.activate();
+    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
+    c.activate();
+    struct Running {
+        std::atomic<int>& n;
+        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
+        ~Running() { n.fetch_sub(1); }
+    } running(c.proofs_running);
+    hipStream_t st = c.stream;
+
+    ConstraintReport rep;
+    rep.chips.resize(NC);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
+    VG_HIP_CHECK(hipEventCreate(&ev0));
+    VG_HIP_CHECK(hipEventCreate(&ev1));
+    uint64_t scratch_words = 0;
+    try {
+        // working-layout copies, as prove makes them (traces generated on the device are already column-major Montgomery)
+        std::vector<DMat> own;
+        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
+            if (!t->nat.empty()) return t->nat.view();
+            own.emplace_back(&c, t->height, t->width);
+            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
+            return own.back().view();
+        };
+        own.reserve(NC + preprocessed.size());
+        // per chip: the launch shape and its slice of the scratch (u32 words): totals [2 (K + 1)], table [K NB], prefix [K NB]
+        std::vector<vk::CaArgs> args(NC);
+        std::vector<uint64_t> tot_at(NC, 0), tab_at(NC, 0), pre_at(NC, 0);
+        uint64_t zeroed = 0;
+        for (size_t i = 0; i < NC; i++) {
+            const AirDesc& air = machine_.airs[i];
+            vk::CaArgs& a = args[i];
+            a = vk::CaArgs{};
+            a.K = air.program.num_asserts;
+            rep.chips[i].n_constraints = a.K; rep.chips[i].height = main[i]->height;
+            if (!a.K) continue;  // a chip without constraints (program, mem, div, range) is not read
+            const vk::DMatView v = working(main[i]);
+            a.main = v.data; a.mstride = v.stride; a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
+            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
+            a.prog = (const vair::Instr*)prog_dev_[i].data;
+            a.n_instrs = (uint32_t)air.program.instrs.size();
+            a.n_regs = air.program.num_regs;
+            a.native_chip = fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip;
+            a.T = vk::ca_block_threads(a);
+            a.NB = (uint32_t)((a.n + a.T - 1) / a.T);
+            tot_at[i] = zeroed; zeroed += 2 * (uint64_t)(a.K + 1);
+            tab_at[i] = zeroed; zeroed += ((uint64_t)a.K * a.NB + 1) & ~1ull;  // the next chip's u64 totals stay 8-byte aligned
+        }
+        scratch_words = zeroed;
+        for (size_t i = 0; i < NC; i++) if (args[i].K) { pre_at[i] = scratch_words; scratch_words += (uint64_t)args[i].K * args[i].NB; }
+        c.check_launch("constraint_audit ingest");
+        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
+        // the device pass: everything from here to the last download is between the two events (the working-layout copies of uploaded traces,
+        // which a proof makes as well, are before them)
+        VG_HIP_CHECK(hipEventRecord(ev0, st));
+        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)zeroed * 4, st));
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].K) vk::launch_ca_count(st, args[i], reinterpret_cast<unsigned long long*>(scratch.data + tot_at[i]), scratch.data + tab_at[i]);
+        c.check_launch("constraint_audit count");
+        // the totals of all chips lie in front of their tables: gather them with one small copy per chip
+        std::vector<std::vector<uint64_t>> counts(NC);
+        {
+            std::vector<uint32_t> tw;
+            for (size_t i = 0; i < NC; i++) {
+                const uint32_t K = args[i].K;
+                counts[i].assign(K, 0);
+                if (!K) continue;
+                tw.resize(2 * (size_t)(K + 1));
+                c.download_small(tw.data(), scratch.data + tot_at[i], tw.size() * 4);
+                for (uint32_t k = 0; k < K; k++) counts[i][k] = ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k];
+                rep.chips[i].failing_rows = ((uint64_t)tw[2 * K + 1] << 32) | tw[2 * K];
+            }
+        }
+        constraint_audit_finish(rep, counts, o);
+        const uint32_t R = o.max_rows_per_constraint;
+        for (size_t e0 = 0; e0 < rep.constraints.size();) {
+            // the listed constraints of one chip: scan, list, values, one download
+            const uint32_t chip = rep.constraints[e0].chip;
+            size_t e1 = e0;
+            vk::CaListed listed{};
+            while (e1 < rep.constraints.size() && rep.constraints[e1].chip == chip) { const uint32_t k = rep.constraints[e1].constraint; listed.w[k >> 5] |= 1u << (k & 31u); e1++; }
+            const vk::CaArgs& a = args[chip];
+            DBuf out(&c, (size_t)2 * a.K * R);
+            uint32_t* rows = out.data;
+            uint32_t* values = out.data + (size_t)a.K * R;
+            vk::launch_ca_scan(st, a, scratch.data + tab_at[chip], scratch.data + pre_at[chip], listed);
+            vk::launch_ca_list(st, a, scratch.data + tab_at[chip], scratch.data + pre_at[chip], listed, R, rows);
+            vk::launch_ca_values(st, a, reinterpret_cast<const unsigned long long*>(scratch.data + tot_at[chip]), listed, R, rows, values);
+            c.check_launch("constraint_audit list");
+            std::vector<uint32_t> w((size_t)2 * a.K * R);
+            c.download_small(w.data(), out.data, w.size() * 4);
+            for (size_t e = e0; e < e1; e++) {
+                ConstraintEntry& en = rep.constraints[e];
+                const uint64_t listed_rows = std::min<uint64_t>(en.failing_rows, R);
+                for (uint64_t j = 0; j < listed_rows; j++) en.rows.push_back({w[(size_t)en.constraint * R + j], w[(size_t)a.K * R + (size_t)en.constraint * R + j]});
+            }
+            e0 = e1;
+        }
+        VG_HIP_CHECK(hipEventRecord(ev1, st));
+        c.sync();
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
+    } catch (const BusAuditNoMemory&) {
+        throw;
+    } catch (const std::bad_alloc&) {
+        (void)hipStreamSynchronize(st);
+        throw BusAuditNoMemory("constraint_audit: the device pool cannot give the pass its scratch: 8 bytes per (constraint, workgroup of 256 rows) of every chip (" +
+                               std::to_string(scratch_words * 4) + " bytes for this witness), 8 more per listed row, plus the working-layout copies of uploaded traces");
+    }
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 }  // namespace vhost

@@ -7,6 +7,7 @@
 #include <memory>
 #include "bus_audit.hpp"
 #include "challenger.hpp"
+#include "constraint_audit.hpp"
 #include "machine.hpp"
 #include "pcs.hpp"
 
@@ -107,6 +108,11 @@ class Prover {
     // Scratch from the pool: BUS_AUDIT_BYTES_PER_SLOT per (row, interaction) pair, 24 more per unbalanced tuple.
     static constexpr uint64_t BUS_AUDIT_BYTES_PER_SLOT = 60;
     BusReport bus_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const BusAuditOpts& opts);
+
+    // Constraint audit of a witness (host/constraint_audit.hpp, kernels/constraint_audit.hip): the same trace handles as prove, queued on the
+    // context like a proof.  Scratch from the pool: 8 bytes per (constraint, workgroup of rows) of every chip with constraints, 8 per listed row.
+    ConstraintReport constraint_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
+                                      const ConstraintAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

@@ -165,6 +165,28 @@ void launch_ba_select(hipStream_t st, const uint32_t* desc, const uint32_t* ids,
                       uint32_t cap, unsigned long long* ukeys, uint32_t* uvals, uint32_t* counters);
 void launch_ba_report(hipStream_t st, const uint32_t* desc, const uint32_t* ids, const uint32_t* cnt, const uint32_t* head_pos, const unsigned long long* sums, const uint32_t* nrec,
                       const uint32_t* uvals, uint32_t n_rep, uint32_t R, uint32_t* out);
+// constraint_audit.hip — the passes of the constraint audit (host/constraint_audit.hpp: contract; Prover::constraint_audit drives them), per chip.
+// totals: [K + 1] u64 (zeroed), table / prefix: [K][NB] u32 (table zeroed), rows / values: [K][R] u32.
+constexpr uint32_t CA_MAX_CONSTRAINTS = 96, CA_MASK_WORDS = 3;  // the fail mask of a row: bitwise has 88 constraints, lt 60, cpu 53
+constexpr int CA_INTERPRET = -2;                                 // QuotientArgs::INTERPRET
+struct CaListed { uint32_t w[CA_MASK_WORDS]; };                   // bit k: constraint k of the chip is listed in the report
+struct CaArgs {
+    const uint32_t* main;  // column-major working layout (Montgomery), natural row order
+    uint64_t mstride;
+    const uint32_t* prep;  // null for a chip without preprocessed columns
+    uint64_t pstride;
+    uint64_t n;            // height, a power of two
+    uint32_t width, prep_width;
+    const vair::Instr* prog;
+    uint32_t n_instrs, n_regs, K;  // K = constraints of the chip, 1..CA_MAX_CONSTRAINTS
+    int native_chip;               // a vchips::ChipId with constraints, or CA_INTERPRET
+    uint32_t T, NB;                // rows per workgroup (ca_block_threads) and workgroups = ceil(n / T)
+};
+uint32_t ca_block_threads(const CaArgs& a);
+void launch_ca_count(hipStream_t st, const CaArgs& a, unsigned long long* totals, uint32_t* table);
+void launch_ca_scan(hipStream_t st, const CaArgs& a, const uint32_t* table, uint32_t* prefix, const CaListed& listed);
+void launch_ca_list(hipStream_t st, const CaArgs& a, const uint32_t* table, const uint32_t* prefix, const CaListed& listed, uint32_t R, uint32_t* rows);
+void launch_ca_values(hipStream_t st, const CaArgs& a, const unsigned long long* totals, const CaListed& listed, uint32_t R, const uint32_t* rows, uint32_t* values);
 // open.hip
 void launch_bary_weights(hipStream_t st, uint64_t n, const uint32_t* min_poly_dev, Fp shift, const DeviceTables& tb, uint32_t* w);
 // the same for several (height, point) pairs in one launch: job = { first block (u32), pad, n (u64), min-poly pointer, weight buffer, digit-plane image (or null) }
