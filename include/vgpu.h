@@ -396,6 +396,62 @@ const uint32_t* vgpu_constraint_report_words(const vgpu_constraint_report_t* r);
 void vgpu_constraint_report_timing(const vgpu_constraint_report_t* r, double out[2]);
 void vgpu_constraint_report_free(vgpu_constraint_report_t* r);
 
+/* ---- Mutation audit: WHICH cells of a witness could be changed without any AIR constraint or bus noticing — mutation testing of the AIRs, the
+ * converse of the two audits above (they are only as strong as the AIRs they evaluate).  Inputs: exactly what vgpu_prove and the audits take.
+ *   mutation      chip h with main matrix M (height n, width w), a row r, a main column c and a delta d: M' = M except M'[r][c] = M[r][c] + d
+ *                 mod p.  Preprocessed columns are never mutated.
+ *   AIR-detected  Air::eval of the chip on M' at rows r and (r - 1) mod n, over the constraint audit's domain (next = (row + 1) mod n,
+ *                 is_first_row / is_last_row / is_transition as 0/1 values): some constraint is non-zero there that was zero at the same row
+ *                 on M (a NEWLY failing constraint, so a witness that already fails can be audited).  For n = 1 the two rows are one row and
+ *                 the mutated cell is seen as `local` and as `next` in one evaluation.  The permutation constraints are not evaluated: the bus
+ *                 rule is their exact statement.
+ *   bus-detected  every interaction of the chip on row r, in Chip::all_interactions order, for M and for M': an interaction with count 0 is no
+ *                 record, otherwise the record is (count, fields), all canonical; detected when the record of some interaction differs.
+ *   counts        per (chip, column, delta index), exact over all n rows: `air` rows that are AIR-detected, `bus` rows that are bus-detected,
+ *                 `free` rows that are neither.  A column is UNBOUND when free = n for every delta.
+ *   order         an entry is a (chip, column, delta index) with free > 0; entries ascend by (chip, column, delta index), each with its first
+ *                 max_rows_per_entry free rows in ascending order.  Only the first max_entries entries are listed; the totals stay exact and
+ *                 `truncated` says the list was cut.  No challenge, no hash and no floating point enter: the same words run after run, for
+ *                 Machine.basic (compiled chip templates) and for captured AIRs (the interpreted program) alike.
+ * The report is a statement about single-cell slack on THIS witness; it is not a soundness proof (a bound cell may be bound only on the rows
+ * this witness has, and slack of two cells changed together is not looked for).
+ * Options: a zero field selects its default — max_entries 1024, max_rows_per_entry 4 (at most 2^24 and 4096), n_deltas 0 = the pair {1, p - 1};
+ * otherwise deltas[0 .. n_deltas) are 1 to 4 distinct canonical values in 1..p-1; opts may be NULL; reserved != 0 is refused.
+ * vgpu_mutation_audit runs on the device (kernels/mutation_audit.hip), queued on the prover context like a proof or the other audits; it accepts
+ * device-generated and uploaded traces.  Scratch comes from the prover's pool: 4 bytes per (column, delta, workgroup of T rows) twice (table and
+ * prefix), i.e. at most 8 w D / T bytes per row (T = 256 rows, less for a captured AIR with a large register file), 24 w D bytes of totals and
+ * 12 w of column flags per chip, 4 w D max_rows_per_entry bytes of listed rows for the widest chip, plus the working-layout copy of every
+ * uploaded (not device-generated) trace; VGPU_ERR_OOM with a message when the pool cannot give them; VGPU_ERR_INVALID_ARG for bad shapes, for
+ * a chip of more than 96 constraints and for one whose row tile (its columns and program registers) does not fit 160 KB of LDS at 64 rows.
+ * vgpu_mutation_audit_host is the same contract on the host over canonical row-major matrices (one thread, no device, any number of
+ * constraints).  Both validate shapes as vgpu_prove does.
+ * Report image (vgpu_mutation_report_words, u32 words; u64 values as lo, hi):
+ *   [0] 0x31524d56 "VMR1" [1] word count [2] n_deltas D [3] truncated [4,5] total_entries = (chip, column, delta) with free > 0 (exact even when
+ *   the list is cut) [6] reported [7] n_chips [8..11] the deltas (canonical; unused slots 0)
+ *   per chip, in machine order, 6 + 6 D words: width, constraints, height (u64), unbound columns, 0, then per delta the sums over the chip's
+ *   columns of free, air, bus (u64 each)
+ *   per reported entry: chip, column, delta index, n_listed, free, air, bus (u64 each), then n_listed rows. */
+typedef struct vgpu_mutation_audit_opts {
+    uint64_t max_entries;
+    uint32_t max_rows_per_entry;
+    uint32_t n_deltas;
+    uint32_t deltas[4];
+    uint32_t reserved[2];
+} vgpu_mutation_audit_opts_t;
+typedef struct vgpu_mutation_report vgpu_mutation_report_t;
+int32_t vgpu_mutation_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                            uint32_t n_prep, const vgpu_mutation_audit_opts_t* opts, vgpu_mutation_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_mutation_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                                 const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                                 const vgpu_mutation_audit_opts_t* opts, vgpu_mutation_report_t** out);
+uint64_t vgpu_mutation_report_len(const vgpu_mutation_report_t* r);
+const uint32_t* vgpu_mutation_report_words(const vgpu_mutation_report_t* r);
+/* out[0]: the device pass (events around it on the prover's stream, after the working-layout copies of uploaded traces; 0 for the host audit),
+ * out[1]: wall time of the whole call; milliseconds.  out[2]: the Air::eval row evaluations the audit performed (baselines included) */
+void vgpu_mutation_report_timing(const vgpu_mutation_report_t* r, double out[3]);
+void vgpu_mutation_report_free(vgpu_mutation_report_t* r);
+
 /* ---- RCCL inside the library: one process per GPU; the host's launcher distributes the 128-byte id that rank 0
  * obtains from vgpu_comm_unique_id (any out-of-band channel: MPI, a file, the Rust host's own RPC), every rank then calls
  * vgpu_comm_init with its prover.  vgpu_comm_allgather_roots is the path's one collective: each segment's commitment roots

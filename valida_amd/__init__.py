@@ -1101,6 +1101,115 @@ def constraint_audit_host(machine, main_matrices, preprocessed, max_constraints=
     return _constraint_report(h)
 
 
+class MutationAuditOpts(ctypes.Structure):  # vgpu_mutation_audit_opts_t
+    _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("n_deltas", ctypes.c_uint32), ("deltas", ctypes.c_uint32 * 4),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+class MutationReport:
+    """The mutation audit of a witness (vgpu_mutation_audit / vgpu_mutation_audit_host; the contract is stated in include/vgpu.h), as plain
+    Python values: deltas, truncated, total_entries ((chip, column, delta) with a free row), reported,
+    chips = [dict(chip, width, constraints, height, unbound, free=[per delta], air=[..], bus=[..])] (sums over the chip's columns),
+    entries = [dict(chip, column, delta, free, air, bus, rows=[first free rows])] ascending by (chip, column, delta index; `delta` is the index),
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (Air::eval row evaluations performed)."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 12 or w[0] != 0x31524D56 or w[1] != len(w) or not 1 <= w[2] <= 4:
+            raise ValueError("not a mutation report image")
+        self.words = np.array(w, dtype=np.uint32)
+        D = w[2]
+        self.deltas, self.truncated = w[8:8 + D], bool(w[3])
+        self.total_entries, self.reported = w[4] | (w[5] << 32), w[6]
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 12
+        self.chips = []
+        for c in range(w[7]):
+            self.chips.append(dict(chip=c, width=w[pos], constraints=w[pos + 1], height=u64(pos + 2), unbound=w[pos + 4], free=[u64(pos + 6 + 6 * i) for i in range(D)],
+                                   air=[u64(pos + 8 + 6 * i) for i in range(D)], bus=[u64(pos + 10 + 6 * i) for i in range(D)]))
+            pos += 6 + 6 * D
+        self.entries = []
+        for _ in range(self.reported):
+            n_listed = w[pos + 3]
+            e = dict(chip=w[pos], column=w[pos + 1], delta=w[pos + 2], free=u64(pos + 4), air=u64(pos + 6), bus=u64(pos + 8), rows=w[pos + 10:pos + 10 + n_listed])
+            pos += 10 + n_listed
+            self.entries.append(e)
+        assert pos == len(w)
+
+    def unbound_columns(self, chip):
+        """The columns of `chip` that are free on every row for every delta — as far as the list goes (exact when not truncated)."""
+        height, D = self.chips[chip]["height"], len(self.deltas)
+        full = {}
+        for e in self.entries:
+            if e["chip"] == chip and e["free"] == height:
+                full[e["column"]] = full.get(e["column"], 0) + 1
+        return sorted(c for c, k in full.items() if k == D)
+
+    def to_dict(self):
+        return dict(deltas=self.deltas, truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
+                    evaluations=self.evaluations, chips=self.chips, entries=self.entries)
+
+    def to_json(self):
+        import json
+
+        return json.dumps(self.to_dict())
+
+
+def _mutation_opts(deltas, max_entries, max_rows_per_entry):
+    # in the C struct a zero field selects its default, so the refusals of explicit zeros (and of an empty delta list) are made here, with the
+    # library's status code; the range and distinctness of the deltas are the library's to check
+    if int(max_entries) < 1 or int(max_rows_per_entry) < 1:
+        raise VgpuError(-1, "mutation_audit: max_entries and max_rows_per_entry must be at least 1")
+    ds = [int(d) for d in ((1, P - 1) if deltas is None else deltas)]
+    if not 1 <= len(ds) <= 4:
+        raise VgpuError(-1, "mutation_audit: 1 to 4 deltas (got %d)" % len(ds))
+    if any(d < 0 or d > 0xFFFFFFFF for d in ds):
+        raise VgpuError(-1, "mutation_audit: a delta must be a canonical value in 1..p-1")
+    return MutationAuditOpts(int(max_entries), int(max_rows_per_entry), len(ds), (ctypes.c_uint32 * 4)(*ds), (ctypes.c_uint32 * 2)(0, 0))
+
+
+def _mutation_report(h):
+    L = lib()
+    L.vgpu_mutation_report_len.restype = ctypes.c_uint64
+    L.vgpu_mutation_report_words.restype = c_u32p
+    L.vgpu_mutation_report_len.argtypes = L.vgpu_mutation_report_words.argtypes = L.vgpu_mutation_report_free.argtypes = [ctypes.c_void_p]
+    L.vgpu_mutation_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    try:
+        n = int(L.vgpu_mutation_report_len(h))
+        words = np.ctypeslib.as_array(L.vgpu_mutation_report_words(h), shape=(n,)).copy()
+        tm = (ctypes.c_double * 3)()
+        L.vgpu_mutation_report_timing(h, tm)
+    finally:
+        L.vgpu_mutation_report_free(h)
+    return MutationReport(words, tm[0], tm[1], tm[2])
+
+
+def mutation_audit_host(machine, main_matrices, preprocessed, deltas=None, max_entries=1024, max_rows_per_entry=4):
+    """The mutation audit on the HOST (vgpu_mutation_audit_host: no device, one thread): main_matrices = one canonical matrix per chip,
+    preprocessed = [(chip index, matrix)], deltas = 1 to 4 distinct values in 1..p-1 (default (1, p - 1)); a MutationReport back."""
+    opts = _mutation_opts(deltas, max_entries, max_rows_per_entry)
+    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
+    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
+    for m in mains + [m for _, m in preps]:
+        if m.ndim != 2:
+            raise VgpuError(-1, "mutation_audit: traces are two-dimensional matrices")
+
+    def arrays(ms):
+        n = max(1, len(ms))
+        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
+
+    mp, mh, mw = arrays(mains)
+    pp, ph, pw = arrays([m for _, m in preps])
+    chips = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
+    h = ctypes.c_void_p()
+    _check(lib().vgpu_mutation_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chips, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
+    return _mutation_report(h)
+
+
 class Ticket:
     """An outstanding asynchronous proof (vgpu_prove_async); keeps its inputs alive until waited for."""
 
@@ -1274,6 +1383,17 @@ class Prover:
         h = ctypes.c_void_p()
         _check(lib().vgpu_constraint_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
         return _constraint_report(h)
+
+    def mutation_audit(self, main, preprocessed, deltas=None, max_entries=1024, max_rows_per_entry=4):
+        """Which cells of this witness could be changed by a delta without any AIR constraint or bus noticing (vgpu_mutation_audit; mutation
+        testing of the AIRs): the arguments of prove, deltas = 1 to 4 distinct values in 1..p-1 (default (1, p - 1)); a MutationReport back."""
+        opts = _mutation_opts(deltas, max_entries, max_rows_per_entry)
+        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
+        chips = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
+        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_mutation_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
+        return _mutation_report(h)
 
     def prove_async(self, main, preprocessed, keep=None):
         """Start Machine::prove on a host thread of the library; returns a Ticket (wait() -> Proof).  `keep`: further objects

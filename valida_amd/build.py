@@ -25,6 +25,7 @@ SOURCES = [
     "kernels/verify.hip",
     "kernels/bus_audit.hip",
     "kernels/constraint_audit.hip",
+    "kernels/mutation_audit.hip",
     "host/prover.cpp",
     "host/sharded_prover.cpp",
     "capi.cpp",

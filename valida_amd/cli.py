@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--deltas D[,D..]]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
 ADVICE: a file whose bytes are the advice tape (FixedAdviceProvider); without it the tape is empty (the reference reads stdin instead).
@@ -28,6 +28,11 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         stdout gets one line per listed constraint, `<chip> constraint <k> fails on <count> rows: row r = value, ..` (for a cpu row also pc and
         opcode), and a summary line `satisfied: ..` or `violated: N constraints of M chips ..`; --max-constraints N cuts the list (default 64).
         Without the flag `check` does what it did before the flag existed, byte for byte.
+        --mutations adds the mutation audit of the same witness (vgpu_mutation_audit: which trace cells could be changed by a delta without any
+        AIR constraint or bus noticing — mutation testing of the AIRs), on the same path (device or --host); --deltas 1,-1,2 names 1 to 4 distinct
+        deltas (integers mod p; default 1,-1).  The JSON report gets one more key, "mutations" (MutationReport.to_json's object); after the other
+        lines stdout gets one line per chip that has a free cell, `<chip>: unbound columns 14, 15, 17; free cells 3131 (+1), 3047 (-1) of 13056`.
+        An unbound column is slack of the AIR, not a fault of the witness: the exit status does not depend on this flag.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -124,6 +129,40 @@ def constraint_lines(report, cpu_trace):
     return lines
 
 
+def parse_deltas(text):
+    """--deltas: comma-separated integers, taken mod p."""
+    import valida_amd as va
+
+    return [int(x) % va.P for x in text.split(",") if x.strip()]
+
+
+def mutation_lines(report):
+    """One line per chip of a mutation report that has a free cell: its unbound columns by index and its free cells per delta."""
+    import valida_amd as va
+
+    def signed(d):
+        return "%+d" % (d if d <= va.P // 2 else d - va.P)
+
+    def ranges(cols):
+        out = []
+        for c in cols:
+            if out and out[-1][1] == c - 1:
+                out[-1][1] = c
+            else:
+                out.append([c, c])
+        return ", ".join("%d" % a if a == b else "%d-%d" % (a, b) for a, b in out)
+
+    lines = []
+    for c in report.chips:
+        if not any(c["free"]):
+            continue
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        cols = report.unbound_columns(c["chip"])
+        lines.append("%s: %s; free cells %s of %d" % (name, "unbound columns " + ranges(cols) if cols else "no unbound column",
+                                                     ", ".join("%d (%s)" % (f, signed(d)) for f, d in zip(c["free"], report.deltas)), c["height"] * c["width"]))
+    return lines
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(prog="python -m valida_amd.cli", description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("action", choices=["run", "prove", "verify", "check"])
@@ -138,6 +177,8 @@ def main(argv=None):
     ap.add_argument("--max-records", type=int, default=4)
     ap.add_argument("--constraints", action="store_true", help="check: also the constraint audit (which AIR constraints fail on which rows)")
     ap.add_argument("--max-constraints", type=int, default=64)
+    ap.add_argument("--mutations", action="store_true", help="check: also the mutation audit (which trace cells no constraint or bus binds)")
+    ap.add_argument("--deltas", default="1,-1", help="check --mutations: 1 to 4 distinct deltas, comma-separated integers mod p (as --deltas=1,-1)")
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -165,6 +206,7 @@ def main(argv=None):
             if args.host:
                 report = va.bus_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_tuples=args.max_tuples, max_records_per_tuple=args.max_records)
                 creport = va.constraint_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_constraints=args.max_constraints) if args.constraints else None
+                mreport = va.mutation_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_entries=1 << 20) if args.mutations else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -172,12 +214,15 @@ def main(argv=None):
                 prep = [(chip, prover.upload(m)) for chip, m in w.preprocessed()]
                 report = prover.bus_audit(main, prep, max_tuples=args.max_tuples, max_records_per_tuple=args.max_records)
                 creport = prover.constraint_audit(main, prep, max_constraints=args.max_constraints) if args.constraints else None
+                mreport = prover.mutation_audit(main, prep, deltas=parse_deltas(args.deltas), max_entries=1 << 20) if args.mutations else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
+            if mreport is not None:
+                text = json.dumps(dict(json.loads(text), mutations=mreport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
-            for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []):
+            for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

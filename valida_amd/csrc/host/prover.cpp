@@ -1419,4 +1419,154 @@ ConstraintReport Prover::constraint_audit(const std::vector<const DeviceTrace*>&
     return rep;
 }
 
+// ---- mutation audit (host/mutation_audit.hpp; kernels/mutation_audit.hip) ------------------------------------------------------------------
+MutationReport Prover::mutation_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
+                                      const MutationAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const MutationAuditOpts o = mutation_audit_checked_opts(opts_in);
+    std::vector<ConstraintShape> ms, ps;
+    std::vector<int> prep_chips, prep_slot;
+    for (auto t : main) { if (!t) throw std::invalid_argument("mutation_audit: null trace"); ms.push_back({t->height, t->width}); }
+    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("mutation_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
+    mutation_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
+    const size_t NC = machine_.airs.size();
+    for (size_t i = 0; i < NC; i++)
+        if (machine_.airs[i].program.num_asserts > vk::CA_MAX_CONSTRAINTS)
+            throw std::invalid_argument("mutation_audit: chip " + machine_.airs[i].name + " has " + std::to_string(machine_.airs[i].program.num_asserts) + " constraints; the device audit handles up to " +
+                                        std::to_string(vk::CA_MAX_CONSTRAINTS) + " per chip (the host audit has no limit)");
+    const uint32_t D = o.n_deltas, R = o.max_rows_per_entry;
+
+    DeviceCtx& c = *ctx_;
+    c.activate();
+    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
+    c.activate();
+    struct Running {
+        std::atomic<int>& n;
+        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
+        ~Running() { n.fetch_sub(1); }
+    } running(c.proofs_running);
+    hipStream_t st = c.stream;
+
+    MutationReport rep;
+    rep.chips.resize(NC);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
+    VG_HIP_CHECK(hipEventCreate(&ev0));
+    VG_HIP_CHECK(hipEventCreate(&ev1));
+    uint64_t scratch_words = 0, rows_words = 0;
+    try {
+        // working-layout copies, as prove makes them (traces generated on the device are already column-major Montgomery)
+        std::vector<DMat> own;
+        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
+            if (!t->nat.empty()) return t->nat.view();
+            own.emplace_back(&c, t->height, t->width);
+            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
+            return own.back().view();
+        };
+        own.reserve(NC + preprocessed.size());
+        // per chip: the launch shape, its column flags and its slice of the scratch (u32 words): totals [6 E], table [E NB], prefix [E NB]
+        std::vector<vk::MaArgs> args(NC);
+        std::vector<uint64_t> tot_at(NC, 0), tab_at(NC, 0), pre_at(NC, 0), flag_at(NC, 0);
+        std::vector<uint32_t> flag_words;
+        uint64_t zeroed = 0;
+        for (size_t i = 0; i < NC; i++) {
+            const AirDesc& air = machine_.airs[i];
+            vk::MaArgs& a = args[i];
+            a = vk::MaArgs{};
+            a.K = air.program.num_asserts;
+            rep.chips[i].width = air.width; rep.chips[i].n_constraints = a.K; rep.chips[i].height = main[i]->height;
+            const double evaluations = ma_evaluations(air, main[i]->height, D);
+            rep.evaluations += evaluations;
+            if (!air.width) continue;
+            const vk::DMatView v = working(main[i]);
+            a.main = v.data; a.mstride = v.stride; a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
+            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
+            a.prog = (const vair::Instr*)prog_dev_[i].data;
+            a.n_instrs = (uint32_t)air.program.instrs.size();
+            a.n_regs = air.program.num_regs;
+            a.iw = iw_dev_[i].data;
+            a.evaluations = evaluations;
+            a.D = D;
+            for (uint32_t k = 0; k < D; k++) a.delta[k] = Fp::from_canonical(o.deltas[k]).v;
+            a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
+            a.T = vk::ma_block_threads(a);
+            a.NB = (uint32_t)((a.n + a.T - 1) / a.T);
+            a.CY = vk::ma_column_slices(a, a.NB);
+            const double baselines = a.K ? (a.n == 1 ? 1.0 : 2.0) * (double)a.n * (a.CY - 1) : 0;  // every column slice evaluates the baselines of its rows
+            a.evaluations += baselines; rep.evaluations += baselines;
+            const std::vector<uint32_t> fl = ma_column_flags(air);
+            bool masks_ok = false;
+            const std::vector<uint32_t> bm = ma_bus_masks(air, masks_ok);
+            a.bus_walk = masks_ok ? 0u : 1u;
+            flag_at[i] = flag_words.size();
+            flag_words.insert(flag_words.end(), fl.begin(), fl.end());
+            flag_words.insert(flag_words.end(), bm.begin(), bm.end());
+            const uint64_t E = (uint64_t)a.width * D;
+            tot_at[i] = zeroed; zeroed += 6 * E;
+            tab_at[i] = zeroed; zeroed += (E * a.NB + 1) & ~1ull;  // the next chip's u64 totals stay 8-byte aligned
+            rows_words = std::max<uint64_t>(rows_words, E * R);
+        }
+        scratch_words = zeroed;
+        for (size_t i = 0; i < NC; i++) if (args[i].width) { pre_at[i] = scratch_words; scratch_words += (uint64_t)args[i].width * D * args[i].NB; }
+        if (flag_words.empty()) flag_words.push_back(0);
+        DBuf flags(&c, flag_words);
+        for (size_t i = 0; i < NC; i++) args[i].flags = flags.data + flag_at[i];
+        c.check_launch("mutation_audit ingest");
+        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
+        DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
+        // the device pass: everything from here to the last download is between the two events (the working-layout copies of uploaded traces,
+        // which a proof makes as well, are before them)
+        VG_HIP_CHECK(hipEventRecord(ev0, st));
+        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)zeroed * 4, st));
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].width) vk::launch_ma_count(st, args[i], reinterpret_cast<unsigned long long*>(scratch.data + tot_at[i]), scratch.data + tab_at[i]);
+        c.check_launch("mutation_audit count");
+        std::vector<std::vector<uint64_t>> counts(NC);
+        {
+            std::vector<uint32_t> tw;
+            for (size_t i = 0; i < NC; i++) {
+                const size_t E = (size_t)args[i].width * D;
+                counts[i].assign(3 * E, 0);
+                if (!E) continue;
+                tw.resize(6 * E);
+                c.download_small(tw.data(), scratch.data + tot_at[i], tw.size() * 4);
+                for (size_t k = 0; k < 3 * E; k++) counts[i][k] = ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k];
+            }
+        }
+        mutation_audit_finish(rep, counts, o);
+        for (size_t e0 = 0; e0 < rep.entries.size();) {
+            // the listed entries of one chip: scan, list, one download
+            const uint32_t chip = rep.entries[e0].chip;
+            size_t e1 = e0;
+            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
+            const vk::MaArgs& a = args[chip];
+            const uint32_t e_cut = rep.entries[e1 - 1].column * D + rep.entries[e1 - 1].delta + 1;  // entries ascend: the listed ones of a chip are a prefix
+            vk::launch_ma_scan(st, a, reinterpret_cast<const unsigned long long*>(scratch.data + tot_at[chip]), scratch.data + tab_at[chip], scratch.data + pre_at[chip], e_cut);
+            vk::launch_ma_list(st, a, scratch.data + tab_at[chip], scratch.data + pre_at[chip], e_cut, R, out.data);
+            c.check_launch("mutation_audit list");
+            std::vector<uint32_t> w((size_t)e_cut * R);
+            c.download_small(w.data(), out.data, w.size() * 4);
+            for (size_t e = e0; e < e1; e++) {
+                MutationEntry& en = rep.entries[e];
+                const uint64_t listed = std::min<uint64_t>(en.free_, R);
+                const size_t at = ((size_t)en.column * D + en.delta) * R;
+                en.rows.assign(w.begin() + at, w.begin() + at + listed);
+            }
+            e0 = e1;
+        }
+        VG_HIP_CHECK(hipEventRecord(ev1, st));
+        c.sync();
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
+    } catch (const BusAuditNoMemory&) {
+        throw;
+    } catch (const std::bad_alloc&) {
+        (void)hipStreamSynchronize(st);
+        throw BusAuditNoMemory("mutation_audit: the device pool cannot give the pass its scratch: 8 bytes per (column, delta, workgroup of rows) and 24 per (column, delta) of every chip (" +
+                               std::to_string(scratch_words * 4) + " bytes for this witness), " + std::to_string(rows_words * 4) + " bytes of listed rows (4 x columns x deltas x max_rows_per_entry of the widest chip), plus the working-layout copies of uploaded traces");
+    }
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 }  // namespace vhost

@@ -9,6 +9,7 @@
 #include "challenger.hpp"
 #include "constraint_audit.hpp"
 #include "machine.hpp"
+#include "mutation_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -113,6 +114,11 @@ class Prover {
     // context like a proof.  Scratch from the pool: 8 bytes per (constraint, workgroup of rows) of every chip with constraints, 8 per listed row.
     ConstraintReport constraint_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
                                       const ConstraintAuditOpts& opts);
+
+    // Mutation audit of a witness (host/mutation_audit.hpp, kernels/mutation_audit.hip): the same trace handles as prove, queued on the context
+    // like a proof.  Scratch from the pool: 8 bytes per (column, delta, workgroup of rows), 24 per (column, delta), 4 per listed row slot.
+    MutationReport mutation_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
+                                  const MutationAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

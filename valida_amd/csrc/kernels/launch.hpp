@@ -187,6 +187,36 @@ void launch_ca_count(hipStream_t st, const CaArgs& a, unsigned long long* totals
 void launch_ca_scan(hipStream_t st, const CaArgs& a, const uint32_t* table, uint32_t* prefix, const CaListed& listed);
 void launch_ca_list(hipStream_t st, const CaArgs& a, const uint32_t* table, const uint32_t* prefix, const CaListed& listed, uint32_t R, uint32_t* rows);
 void launch_ca_values(hipStream_t st, const CaArgs& a, const unsigned long long* totals, const CaListed& listed, uint32_t R, const uint32_t* rows, uint32_t* values);
+// mutation_audit.hip — the passes of the mutation audit (host/mutation_audit.hpp: contract; Prover::mutation_audit drives them), per chip.
+// An ENTRY of a chip is e = column * D + delta index, E = width * D of them.  totals: [E][3] u64 {free, air, bus} (zeroed), table / prefix:
+// [E][NB] u32 free rows per workgroup and their exclusive prefix (table zeroed), rows: [E][R] u32.
+constexpr int MA_BUS_ONLY = -1;  // a chip without constraints: only its interactions are walked
+constexpr uint32_t MA_COUNT = 0, MA_LIST = 1;
+struct MaArgs {
+    const uint32_t* main;  // column-major working layout (Montgomery), natural row order
+    uint64_t mstride;
+    const uint32_t* prep;  // null for a chip without preprocessed columns
+    uint64_t pstride;
+    uint64_t n;            // height, a power of two
+    uint32_t width, prep_width;
+    const vair::Instr* prog;
+    uint32_t n_instrs, n_regs, K;  // K = constraints of the chip, 0..CA_MAX_CONSTRAINTS
+    const uint32_t* iw;            // the chip's interactions (interactions.hpp: encode_interactions)
+    const uint32_t* flags;         // [width] MA_COL_* of host/mutation_audit.hpp: bit 0 read as local, bit 1 as next, bit 2 by an interaction;
+                                   // then [width][2] the bus masks of the column (ma_bus_masks): interactions whose count / some field changes
+    uint32_t bus_walk;             // 1: more than 32 interactions, no masks: every interaction is evaluated per mutation
+    uint32_t CY;                   // column slices = gridDim.y (ma_column_slices)
+    uint32_t D, delta[4];          // the deltas, Montgomery
+    int native_chip;               // a vchips::ChipId with constraints, CA_INTERPRET, or MA_BUS_ONLY
+    uint32_t T, NB;                // rows per workgroup (ma_block_threads) and workgroups = ceil(n / T)
+    double evaluations;            // Air::eval row evaluations of the counting pass (ma_evaluations): the profile's `ops` column of k_ma_count.*
+};
+uint32_t ma_block_threads(const MaArgs& a);
+uint32_t ma_column_slices(const MaArgs& a, uint32_t NB);
+void launch_ma_count(hipStream_t st, const MaArgs& a, unsigned long long* totals, uint32_t* table);
+// entries below e_cut with a free row are listed
+void launch_ma_scan(hipStream_t st, const MaArgs& a, const unsigned long long* totals, const uint32_t* table, uint32_t* prefix, uint32_t e_cut);
+void launch_ma_list(hipStream_t st, const MaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t e_cut, uint32_t R, uint32_t* rows);
 // open.hip
 void launch_bary_weights(hipStream_t st, uint64_t n, const uint32_t* min_poly_dev, Fp shift, const DeviceTables& tb, uint32_t* w);
 // the same for several (height, point) pairs in one launch: job = { first block (u32), pad, n (u64), min-poly pointer, weight buffer, digit-plane image (or null) }
