@@ -452,6 +452,67 @@ const uint32_t* vgpu_mutation_report_words(const vgpu_mutation_report_t* r);
 void vgpu_mutation_report_timing(const vgpu_mutation_report_t* r, double out[3]);
 void vgpu_mutation_report_free(vgpu_mutation_report_t* r);
 
+/* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
+ * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
+ *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct
+ *                 deltas (default {1, p - 1}); preprocessed columns are never mutated.
+ *   detectors     of a chip with K constraints and M interactions: 0 .. K - 1 the constraints in assert_zero call order (the constraint audit's
+ *                 numbering), K .. K + M - 1 the interactions in Chip::all_interactions order.
+ *   kills         constraint k KILLS (r, c, j) when on the mutated trace it is non-zero at row r or at row (r - 1) mod n and was zero at that same
+ *                 row on the unmutated trace (newly failing, as in the mutation audit; for n = 1 one evaluation, the cell local and next).
+ *                 Interaction m kills it when its record on row r differs before and after (count 0: no record; otherwise (count, fields),
+ *                 canonical).
+ *   counts        S(r, c, j) = the set of detectors that kill the mutation.  Per cell (chip, detector t, column c, delta j), exact over all n
+ *                 rows: kills = #{r : t in S}, sole = #{r : S = {t}}, first_row = min{r : t in S}, first_sole_row = min{r : S = {t}} or
+ *                 0xFFFFFFFF when there is none.
+ *   classes       per detector, over all columns and deltas: DEAD every kills is 0; SHADOWED some kills > 0 and every sole is 0; ESSENTIAL
+ *                 anything else.
+ *   per chip and delta   detected = #{(r, c) : S not empty}, free = n w - detected: the mutation audit's free for the same witness and deltas.
+ *   order         cells with kills > 0 ascend by (chip, detector, column, delta index); only the first max_cells are listed, the chip blocks and
+ *                 total_cells stay exact and `truncated` says the list was cut.  No challenge, no hash and no floating point enter: the same
+ *                 words run after run, from the device and from the host, for Machine.basic and for captured AIRs alike.
+ * What it is not: "dead" is a statement about THIS witness and single-cell mutations by these deltas — it measures what the test program
+ * reaches, and is not a fault of the witness or of the AIR.  "Shadowed" does not mean removable: a constraint that is never alone against
+ * one-cell changes may be the only guard against a two-cell change.
+ * Options: a zero field selects its default — max_cells 8192 (at most 2^24), n_deltas 0 = the pair {1, p - 1}; otherwise deltas[0 .. n_deltas)
+ * are 1 to 4 distinct canonical values in 1..p-1; max_workgroups 0 = the device's default number of workgroups along a chip's rows (a tuning
+ * knob: the report never depends on it; the host audit ignores it); opts may be NULL; reserved != 0 is refused.
+ * vgpu_coverage_audit runs on the device (kernels/coverage_audit.hip), queued on the prover context like a proof or the other audits; it accepts
+ * device-generated and uploaded traces.  Scratch comes from the prover's pool: per chip 16 bytes per cell (detector, column, delta) and workgroup
+ * along its rows (at most 1024 workgroups per chip by default, fewer for a chip of fewer than 1024 row tiles of 256; cpu at 2^20 rows: 95 MB),
+ * 24 bytes per cell, 16 per (detector, delta), 32 per listed cell (at most max_cells per chip), 12 w of column flags, plus the working-layout
+ * copy of every uploaded trace; VGPU_ERR_OOM with a message when the pool cannot give them; VGPU_ERR_INVALID_ARG for bad shapes, for a chip of more than 96
+ * constraints and for one whose row tile with one column's cells does not fit 160 KB of LDS at 64 rows.  Only the chip blocks and the listed
+ * cells are copied to the host.  vgpu_coverage_audit_host is the same contract on the host over canonical row-major matrices (one thread, no
+ * device, no limits).  Both validate shapes as vgpu_prove does.
+ * Report image (vgpu_coverage_report_words, u32 words; u64 values as lo, hi):
+ *   [0] 0x31524b56 "VKR1" [1] word count [2] n_deltas D [3] truncated [4,5] total_cells = cells with kills > 0 (exact even when the list is cut)
+ *   [6] reported [7] n_chips [8..11] the deltas (canonical; unused slots 0)
+ *   per chip, in machine order, 10 + 4 D + 4 D (K + M) words: width, K, M, 0, height (u64); the numbers of dead constraints, shadowed
+ *   constraints, dead interactions, shadowed interactions; per delta detected, free (u64 each); per detector, per delta, kills and sole summed
+ *   over the chip's columns (u64 each)
+ *   per reported cell, 10 words: chip, detector, column, delta index, kills, sole (u64 each), first_row, first_sole_row. */
+typedef struct vgpu_coverage_audit_opts {
+    uint64_t max_cells;
+    uint32_t n_deltas;
+    uint32_t deltas[4];
+    uint32_t max_workgroups;
+    uint32_t reserved[2];
+} vgpu_coverage_audit_opts_t;
+typedef struct vgpu_coverage_report vgpu_coverage_report_t;
+int32_t vgpu_coverage_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                            uint32_t n_prep, const vgpu_coverage_audit_opts_t* opts, vgpu_coverage_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_coverage_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                                 const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                                 const vgpu_coverage_audit_opts_t* opts, vgpu_coverage_report_t** out);
+uint64_t vgpu_coverage_report_len(const vgpu_coverage_report_t* r);
+const uint32_t* vgpu_coverage_report_words(const vgpu_coverage_report_t* r);
+/* out[0]: the device pass (events around it on the prover's stream, after the working-layout copies of uploaded traces; 0 for the host audit),
+ * out[1]: wall time of the whole call; milliseconds.  out[2]: the Air::eval row evaluations the audit performed (baselines included) */
+void vgpu_coverage_report_timing(const vgpu_coverage_report_t* r, double out[3]);
+void vgpu_coverage_report_free(vgpu_coverage_report_t* r);
+
 /* ---- RCCL inside the library: one process per GPU; the host's launcher distributes the 128-byte id that rank 0
  * obtains from vgpu_comm_unique_id (any out-of-band channel: MPI, a file, the Rust host's own RPC), every rank then calls
  * vgpu_comm_init with its prover.  vgpu_comm_allgather_roots is the path's one collective: each segment's commitment roots

@@ -52,12 +52,14 @@ def short(d):
 
 def main():
     files = ["kernels/ntt.hip", "kernels/layout.hip", "kernels/merkle.hip", "kernels/poseidon_mmcs.hip", "kernels/perm.hip", "kernels/quotient.hip", "kernels/open.hip", "kernels/tracegen.hip"]
-    # python tools/isa_mix.py [OUT.txt] [--only kernels/x.hip] [-DFLAG=v ...]: one file and / or an A/B build's flags (the table of a variant before GPU minutes go into it)
+    # python tools/isa_mix.py [OUT.txt] [--only kernels/x.hip] [--loops] [-DFLAG=v ...]: one file and / or an A/B build's flags (the table of a variant before GPU minutes go into it)
     argv, defs = [a for a in sys.argv[1:] if not a.startswith("-D")], [a for a in sys.argv[1:] if a.startswith("-D")]
     if "--only" in argv:
         i = argv.index("--only")
         files = [argv[i + 1]]
         del argv[i:i + 2]
+    all_loops = "--loops" in argv  # also one line per backward-branch loop of every kernel (a kernel whose hot loop is not its largest)
+    argv = [a for a in argv if a != "--loops"]
     sys.argv[1:] = argv
     rows = []
     with tempfile.TemporaryDirectory() as td:
@@ -92,11 +94,14 @@ def main():
                     c = classify(mn)
                     cls[c] = cls.get(c, 0) + 1
                 best = None
+                loops = []
                 for addr, mn, line in ins:
                     if mn.startswith("s_cbranch") or mn == "s_branch":
                         t = re.search(r"<\S+\+0x([0-9a-f]+)>", line)
                         if t:
                             target = ins[0][0] + int(t.group(1), 16)
+                            if target < addr:
+                                loops.append((target, addr))
                             if target < addr and (best is None or addr - target > best[1] - best[0]):
                                 best = (target, addr)
                 loop = {}
@@ -115,6 +120,11 @@ def main():
                     m["waves"] = min(8, 512 // max(v, 8))
                 except (KeyError, ValueError):
                     m["waves"] = "?"
+                m["loops"] = []
+                for lo, hi in loops if all_loops else []:
+                    body = [classify(mn) for addr, mn, _ in ins if lo <= addr <= hi]
+                    m["loops"].append("#   loop +0x%x..+0x%x: %d instructions, vfull %d vhalf %d lds %d vmem %d salu %d" % (
+                        lo - ins[0][0], hi - ins[0][0], len(body), body.count("valu_full"), body.count("valu_half"), body.count("lds"), body.count("vmem"), body.count("salu")))
                 rows.append((base, short(dm.get(sym, sym)), len(ins), cls, loop, m))
     out = ["# sspill / vspill = the kernel descriptor's sgpr_spill_count / vgpr_spill_count; lanemov = v_writelane + v_readlane instructions (SGPRs parked in VGPR lanes);",
            "# waves = waves per SIMD the VGPR count allows (512 / round-up-to-8(vgpr), at most 8); scratch = private segment bytes per lane; lds_B = STATIC LDS only (dynamic LDS is set at launch)",
@@ -127,6 +137,7 @@ def main():
             base, name[:58], n, cls.get("valu_full", 0), cls.get("valu_half", 0), cls.get("mfma", 0), cls.get("lds", 0), cls.get("vmem", 0), cls.get("salu", 0), cls.get("sync", 0),
             loop.get("valu_full", 0), loop.get("valu_half", 0), loop.get("lds", 0), loop.get("vmem", 0), m.get("vgpr", "?"), m.get("sgpr", "?"), m.get("lds", "?"), m.get("scratch", "?"),
             m.get("sspill", "?"), m.get("vspill", "?"), m.get("lanemov", "?"), m.get("waves", "?")))
+        out += m.get("loops", [])
     text = "\n".join(out) + "\n"
     if len(sys.argv) > 1:
         open(sys.argv[1], "w").write(text)

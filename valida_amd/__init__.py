@@ -1210,6 +1210,198 @@ def mutation_audit_host(machine, main_matrices, preprocessed, deltas=None, max_e
     return _mutation_report(h)
 
 
+class CoverageAuditOpts(ctypes.Structure):  # vgpu_coverage_audit_opts_t
+    _fields_ = [("max_cells", ctypes.c_uint64), ("n_deltas", ctypes.c_uint32), ("deltas", ctypes.c_uint32 * 4), ("max_workgroups", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 2)]
+
+
+NO_ROW = 0xFFFFFFFF
+
+
+class CoverageReport:
+    """The coverage audit of a witness (vgpu_coverage_audit / vgpu_coverage_audit_host; the contract is stated in include/vgpu.h), as plain
+    Python values: deltas, truncated, total_cells ((chip, detector, column, delta) with kills > 0), reported,
+    chips = [dict(chip, width, constraints, interactions, height, dead_constraints, shadowed_constraints, dead_interactions,
+    shadowed_interactions (numbers), detected=[per delta], free=[..], kills=[[per delta] per detector], sole=[..])] (sums over the chip's columns),
+    cells = [dict(chip, detector, column, delta, kills, sole, first_row, first_sole_row)] ascending by (chip, detector, column, delta index),
+    device_ms, host_ms, evaluations.  Detectors 0..K-1 are the constraints, K..K+M-1 the interactions.  "Dead" and "shadowed" speak of this
+    witness and of single-cell mutations by these deltas only: neither is a fault, and shadowed does not mean removable."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 12 or w[0] != 0x31524B56 or w[1] != len(w) or not 1 <= w[2] <= 4:
+            raise ValueError("not a coverage report image")
+        self.words = np.array(w, dtype=np.uint32)
+        D = w[2]
+        self.deltas, self.truncated = w[8:8 + D], bool(w[3])
+        self.total_cells, self.reported = w[4] | (w[5] << 32), w[6]
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 12
+        self.chips = []
+        for c in range(w[7]):
+            K, M = w[pos + 1], w[pos + 2]
+            at = pos + 10 + 4 * D
+            self.chips.append(dict(chip=c, width=w[pos], constraints=K, interactions=M, height=u64(pos + 4), dead_constraints=w[pos + 6], shadowed_constraints=w[pos + 7],
+                                   dead_interactions=w[pos + 8], shadowed_interactions=w[pos + 9], detected=[u64(pos + 10 + 4 * i) for i in range(D)],
+                                   free=[u64(pos + 12 + 4 * i) for i in range(D)], kills=[[u64(at + 4 * (t * D + i)) for i in range(D)] for t in range(K + M)],
+                                   sole=[[u64(at + 4 * (t * D + i) + 2) for i in range(D)] for t in range(K + M)]))
+            pos = at + 4 * D * (K + M)
+        self.cells = []
+        for _ in range(self.reported):
+            self.cells.append(dict(chip=w[pos], detector=w[pos + 1], column=w[pos + 2], delta=w[pos + 3], kills=u64(pos + 4), sole=u64(pos + 6), first_row=w[pos + 8],
+                                   first_sole_row=w[pos + 9]))
+            pos += 10
+        assert pos == len(w)
+
+    def _split(self, chip, pred):
+        c = self.chips[chip]
+        K = c["constraints"]
+        hit = [t for t in range(K + c["interactions"]) if pred(sum(c["kills"][t]), sum(c["sole"][t]))]
+        return [t for t in hit if t < K], [t - K for t in hit if t >= K]
+
+    def dead(self, chip):
+        """(constraints, interactions) of `chip` that no mutation of any cell makes fail / changes: indices, the interactions counted from 0."""
+        return self._split(chip, lambda k, s: k == 0)
+
+    def shadowed(self, chip):
+        """(constraints, interactions) of `chip` that detect some mutation and are never the only detector of one."""
+        return self._split(chip, lambda k, s: k > 0 and s == 0)
+
+    def essential(self, chip):
+        return self._split(chip, lambda k, s: s > 0)
+
+    def to_dict(self):
+        return dict(deltas=self.deltas, truncated=self.truncated, total_cells=self.total_cells, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
+                    evaluations=self.evaluations, chips=self.chips, cells=self.cells)
+
+    def to_json(self):
+        import json
+
+        return json.dumps(self.to_dict())
+
+    @staticmethod
+    def _image(deltas, truncated, total_cells, chips, cells):
+        def u64(v):
+            return [v & 0xFFFFFFFF, v >> 32]
+
+        D = len(deltas)
+        w = [0x31524B56, 0, D, int(truncated)] + u64(total_cells) + [len(cells), len(chips)] + (list(deltas) + [0] * 4)[:4]
+        for c in chips:
+            w += [c["width"], c["constraints"], c["interactions"], 0] + u64(c["height"])
+            w += [c["dead_constraints"], c["shadowed_constraints"], c["dead_interactions"], c["shadowed_interactions"]]
+            for i in range(D):
+                w += u64(c["detected"][i]) + u64(c["free"][i])
+            for t in range(c["constraints"] + c["interactions"]):
+                for i in range(D):
+                    w += u64(c["kills"][t][i]) + u64(c["sole"][t][i])
+        for e in cells:
+            w += [e["chip"], e["detector"], e["column"], e["delta"]] + u64(e["kills"]) + u64(e["sole"]) + [e["first_row"], e["first_sole_row"]]
+        w[1] = len(w)
+        return np.array(w, dtype=np.uint32)
+
+    @classmethod
+    def from_dict(cls, d):
+        """The report of to_dict()'s object (a `check --coverage` JSON report's "coverage" key)."""
+        return cls(cls._image(d["deltas"], d["truncated"], d["total_cells"], d["chips"], d["cells"]), d.get("device_ms", 0.0), d.get("host_ms", 0.0), d.get("evaluations", 0.0))
+
+    @classmethod
+    def merge(cls, reports):
+        """The corpus-level report of several witnesses of ONE machine audited with ONE delta set: kills, sole, detected and free add cell-wise,
+        heights add, the classes are recomputed, and the row minima are dropped (0xFFFFFFFF: rows of different witnesses do not compare).
+        Reports of differing machines or deltas, and cut ones (their cell lists are not whole), are refused."""
+        reports = list(reports)
+        if not reports:
+            raise ValueError("merge: no report")
+        first = reports[0]
+        shape = [(c["width"], c["constraints"], c["interactions"]) for c in first.chips]
+        D = len(first.deltas)
+        chips = [dict(c, height=0, detected=[0] * D, free=[0] * D, kills=[[0] * D for _ in c["kills"]], sole=[[0] * D for _ in c["sole"]]) for c in first.chips]
+        cells = {}
+        for r in reports:
+            if r.deltas != first.deltas:
+                raise ValueError("merge: the reports were made with different deltas")
+            if [(c["width"], c["constraints"], c["interactions"]) for c in r.chips] != shape:
+                raise ValueError("merge: the reports are of different machines")
+            if r.truncated:
+                raise ValueError("merge: a report's cell list was cut (max_cells)")
+            for c, m in zip(r.chips, chips):
+                m["height"] += c["height"]
+                for i in range(D):
+                    m["detected"][i] += c["detected"][i]
+                    m["free"][i] += c["free"][i]
+                for t in range(len(m["kills"])):
+                    for i in range(D):
+                        m["kills"][t][i] += c["kills"][t][i]
+                        m["sole"][t][i] += c["sole"][t][i]
+            for e in r.cells:
+                key = (e["chip"], e["detector"], e["column"], e["delta"])
+                k, s = cells.get(key, (0, 0))
+                cells[key] = (k + e["kills"], s + e["sole"])
+        for m in chips:
+            K = m["constraints"]
+            cls_of = ["dead" if sum(k) == 0 else "shadowed" if sum(s) == 0 else "essential" for k, s in zip(m["kills"], m["sole"])]
+            m["dead_constraints"], m["shadowed_constraints"] = cls_of[:K].count("dead"), cls_of[:K].count("shadowed")
+            m["dead_interactions"], m["shadowed_interactions"] = cls_of[K:].count("dead"), cls_of[K:].count("shadowed")
+        listed = [dict(chip=key[0], detector=key[1], column=key[2], delta=key[3], kills=k, sole=s, first_row=NO_ROW, first_sole_row=NO_ROW) for key, (k, s) in sorted(cells.items())]
+        return cls(cls._image(first.deltas, False, len(listed), chips, listed))
+
+
+def _coverage_opts(deltas, max_cells, max_workgroups):
+    # as _mutation_opts: explicit zeros and an empty delta list are refused here, with the library's status code
+    if int(max_cells) < 1:
+        raise VgpuError(-1, "coverage_audit: max_cells must be at least 1")
+    ds = [int(d) for d in ((1, P - 1) if deltas is None else deltas)]
+    if not 1 <= len(ds) <= 4:
+        raise VgpuError(-1, "coverage_audit: 1 to 4 deltas (got %d)" % len(ds))
+    if any(d < 0 or d > 0xFFFFFFFF for d in ds):
+        raise VgpuError(-1, "coverage_audit: a delta must be a canonical value in 1..p-1")
+    if not 0 <= int(max_workgroups) <= 0xFFFFFFFF:
+        raise VgpuError(-1, "coverage_audit: max_workgroups is a 32-bit count (0: the default)")
+    return CoverageAuditOpts(int(max_cells), len(ds), (ctypes.c_uint32 * 4)(*ds), int(max_workgroups), (ctypes.c_uint32 * 2)(0, 0))
+
+
+def _coverage_report(h):
+    L = lib()
+    L.vgpu_coverage_report_len.restype = ctypes.c_uint64
+    L.vgpu_coverage_report_words.restype = c_u32p
+    L.vgpu_coverage_report_len.argtypes = L.vgpu_coverage_report_words.argtypes = L.vgpu_coverage_report_free.argtypes = [ctypes.c_void_p]
+    L.vgpu_coverage_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    try:
+        n = int(L.vgpu_coverage_report_len(h))
+        words = np.ctypeslib.as_array(L.vgpu_coverage_report_words(h), shape=(n,)).copy()
+        tm = (ctypes.c_double * 3)()
+        L.vgpu_coverage_report_timing(h, tm)
+    finally:
+        L.vgpu_coverage_report_free(h)
+    return CoverageReport(words, tm[0], tm[1], tm[2])
+
+
+def coverage_audit_host(machine, main_matrices, preprocessed, deltas=None, max_cells=8192):
+    """The coverage audit on the HOST (vgpu_coverage_audit_host: no device, one thread, no limits): main_matrices = one canonical matrix per
+    chip, preprocessed = [(chip index, matrix)], deltas = 1 to 4 distinct values in 1..p-1 (default (1, p - 1)); a CoverageReport back."""
+    opts = _coverage_opts(deltas, max_cells, 0)
+    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
+    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
+    for m in mains + [m for _, m in preps]:
+        if m.ndim != 2:
+            raise VgpuError(-1, "coverage_audit: traces are two-dimensional matrices")
+
+    def arrays(ms):
+        n = max(1, len(ms))
+        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
+
+    mp, mh, mw = arrays(mains)
+    pp, ph, pw = arrays([m for _, m in preps])
+    chips = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
+    h = ctypes.c_void_p()
+    _check(lib().vgpu_coverage_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chips, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
+    return _coverage_report(h)
+
+
 class Ticket:
     """An outstanding asynchronous proof (vgpu_prove_async); keeps its inputs alive until waited for."""
 
@@ -1394,6 +1586,18 @@ class Prover:
         h = ctypes.c_void_p()
         _check(lib().vgpu_mutation_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
         return _mutation_report(h)
+
+    def coverage_audit(self, main, preprocessed, deltas=None, max_cells=8192, max_workgroups=0):
+        """Which constraint or interaction detects each mutation of the mutation audit (vgpu_coverage_audit): the arguments of prove, deltas as
+        in mutation_audit; max_workgroups is a tuning knob (workgroups along a chip's rows, 0: the default) on which the report never depends.
+        A CoverageReport back."""
+        opts = _coverage_opts(deltas, max_cells, max_workgroups)
+        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
+        chips = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
+        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_coverage_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
+        return _coverage_report(h)
 
     def prove_async(self, main, preprocessed, keep=None):
         """Start Machine::prove on a host thread of the library; returns a Ticket (wait() -> Proof).  `keep`: further objects

@@ -26,6 +26,7 @@ SOURCES = [
     "kernels/bus_audit.hip",
     "kernels/constraint_audit.hip",
     "kernels/mutation_audit.hip",
+    "kernels/coverage_audit.hip",
     "host/prover.cpp",
     "host/sharded_prover.cpp",
     "capi.cpp",

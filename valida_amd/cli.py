@@ -4,7 +4,8 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--deltas D[,D..]]
+    python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
 ADVICE: a file whose bytes are the advice tape (FixedAdviceProvider); without it the tape is empty (the reference reads stdin instead).
@@ -33,6 +34,13 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         deltas (integers mod p; default 1,-1).  The JSON report gets one more key, "mutations" (MutationReport.to_json's object); after the other
         lines stdout gets one line per chip that has a free cell, `<chip>: unbound columns 14, 15, 17; free cells 3131 (+1), 3047 (-1) of 13056`.
         An unbound column is slack of the AIR, not a fault of the witness: the exit status does not depend on this flag.
+        --coverage adds the coverage audit of the same witness (vgpu_coverage_audit: per constraint and per bus interaction of every chip, which
+        of the mutation audit's mutations it detects and of which it is the ONLY detector), on the same path (device or --host) and with the same
+        --deltas.  The JSON report gets one more key, "coverage" (CoverageReport.to_json's object); after the other lines stdout gets one line per
+        chip that has a dead or shadowed detector, `lt: dead constraints 21, 29-30, 32, 34; never the only detector: constraints 0-1, 6-17; 1
+        interaction essential`.  "Dead" says what THIS program reaches with single-cell changes by these deltas — not a fault of the witness or of
+        the AIR; "never the only detector" does not mean removable (it may be the only guard against a two-cell change).  The exit status does not
+        depend on this flag.  coverage_merge adds the "coverage" keys of several reports of one machine and one delta set into a corpus report.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -136,6 +144,17 @@ def parse_deltas(text):
     return [int(x) % va.P for x in text.split(",") if x.strip()]
 
 
+def index_ranges(cols):
+    """Ascending indices in range notation: 21, 29-30, 32."""
+    out = []
+    for c in cols:
+        if out and out[-1][1] == c - 1:
+            out[-1][1] = c
+        else:
+            out.append([c, c])
+    return ", ".join("%d" % a if a == b else "%d-%d" % (a, b) for a, b in out)
+
+
 def mutation_lines(report):
     """One line per chip of a mutation report that has a free cell: its unbound columns by index and its free cells per delta."""
     import valida_amd as va
@@ -143,14 +162,7 @@ def mutation_lines(report):
     def signed(d):
         return "%+d" % (d if d <= va.P // 2 else d - va.P)
 
-    def ranges(cols):
-        out = []
-        for c in cols:
-            if out and out[-1][1] == c - 1:
-                out[-1][1] = c
-            else:
-                out.append([c, c])
-        return ", ".join("%d" % a if a == b else "%d-%d" % (a, b) for a, b in out)
+    ranges = index_ranges
 
     lines = []
     for c in report.chips:
@@ -160,6 +172,33 @@ def mutation_lines(report):
         cols = report.unbound_columns(c["chip"])
         lines.append("%s: %s; free cells %s of %d" % (name, "unbound columns " + ranges(cols) if cols else "no unbound column",
                                                      ", ".join("%d (%s)" % (f, signed(d)) for f, d in zip(c["free"], report.deltas)), c["height"] * c["width"]))
+    return lines
+
+
+def coverage_lines(report):
+    """One line per chip of a coverage report that has a dead or shadowed detector: the dead constraints / interactions by index, those that
+    are never the only detector of a mutation, and how many detectors are essential."""
+    import valida_amd as va
+
+    def plural(n, word):
+        return "%d %s%s" % (n, word, "" if n == 1 else "s")
+
+    lines = []
+    for c in report.chips:
+        (dc, di), (sc, si), (ec, ei) = report.dead(c["chip"]), report.shadowed(c["chip"]), report.essential(c["chip"])
+        if not (dc or di or sc or si):
+            continue
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        parts = []
+        if dc:
+            parts.append("dead constraints " + index_ranges(dc))
+        if di:
+            parts.append("dead interactions " + index_ranges(di))
+        if sc or si:
+            parts.append("never the only detector: " + " and ".join(([("constraints " + index_ranges(sc))] if sc else []) + ([("interactions " + index_ranges(si))] if si else [])))
+        ess = ([plural(len(ec), "constraint")] if ec else []) + ([plural(len(ei), "interaction")] if ei else [])
+        parts.append(" and ".join(ess) + " essential" if ess else "no detector essential")
+        lines.append("%s: %s" % (name, "; ".join(parts)))
     return lines
 
 
@@ -178,7 +217,9 @@ def main(argv=None):
     ap.add_argument("--constraints", action="store_true", help="check: also the constraint audit (which AIR constraints fail on which rows)")
     ap.add_argument("--max-constraints", type=int, default=64)
     ap.add_argument("--mutations", action="store_true", help="check: also the mutation audit (which trace cells no constraint or bus binds)")
-    ap.add_argument("--deltas", default="1,-1", help="check --mutations: 1 to 4 distinct deltas, comma-separated integers mod p (as --deltas=1,-1)")
+    ap.add_argument("--deltas", default="1,-1", help="check --mutations / --coverage: 1 to 4 distinct deltas, comma-separated integers mod p (as --deltas=1,-1)")
+    ap.add_argument("--coverage", action="store_true", help="check: also the coverage audit (which constraint or bus interaction detects each mutation; "
+                    "dead = not reached by this witness, not a fault; never changes the exit status)")
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -207,6 +248,7 @@ def main(argv=None):
                 report = va.bus_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_tuples=args.max_tuples, max_records_per_tuple=args.max_records)
                 creport = va.constraint_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_constraints=args.max_constraints) if args.constraints else None
                 mreport = va.mutation_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_entries=1 << 20) if args.mutations else None
+                kreport = va.coverage_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_cells=1 << 20) if args.coverage else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -215,14 +257,18 @@ def main(argv=None):
                 report = prover.bus_audit(main, prep, max_tuples=args.max_tuples, max_records_per_tuple=args.max_records)
                 creport = prover.constraint_audit(main, prep, max_constraints=args.max_constraints) if args.constraints else None
                 mreport = prover.mutation_audit(main, prep, deltas=parse_deltas(args.deltas), max_entries=1 << 20) if args.mutations else None
+                kreport = prover.coverage_audit(main, prep, deltas=parse_deltas(args.deltas), max_cells=1 << 20) if args.coverage else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
             if mreport is not None:
                 text = json.dumps(dict(json.loads(text), mutations=mreport.to_dict()))
+            if kreport is not None:
+                text = json.dumps(dict(json.loads(text), coverage=kreport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
-            for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []):
+            for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
+                    coverage_lines(kreport) if kreport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

@@ -1569,4 +1569,170 @@ MutationReport Prover::mutation_audit(const std::vector<const DeviceTrace*>& mai
     return rep;
 }
 
+// ---- coverage audit (host/coverage_audit.hpp; kernels/coverage_audit.hip) ------------------------------------------------------------------
+CoverageReport Prover::coverage_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
+                                      const CoverageAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const CoverageAuditOpts o = coverage_audit_checked_opts(opts_in);
+    std::vector<ConstraintShape> ms, ps;
+    std::vector<int> prep_chips, prep_slot;
+    for (auto t : main) { if (!t) throw std::invalid_argument("coverage_audit: null trace"); ms.push_back({t->height, t->width}); }
+    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("coverage_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
+    coverage_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
+    const size_t NC = machine_.airs.size();
+    for (size_t i = 0; i < NC; i++)
+        if (machine_.airs[i].program.num_asserts > vk::CA_MAX_CONSTRAINTS)
+            throw std::invalid_argument("coverage_audit: chip " + machine_.airs[i].name + " has " + std::to_string(machine_.airs[i].program.num_asserts) + " constraints; the device audit handles up to " +
+                                        std::to_string(vk::CA_MAX_CONSTRAINTS) + " per chip (the host audit has no limit)");
+    const uint32_t D = o.n_deltas;
+
+    DeviceCtx& c = *ctx_;
+    c.activate();
+    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
+    c.activate();
+    struct Running {
+        std::atomic<int>& n;
+        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
+        ~Running() { n.fetch_sub(1); }
+    } running(c.proofs_running);
+    hipStream_t st = c.stream;
+
+    CoverageReport rep;
+    rep.deltas.assign(o.deltas, o.deltas + D);
+    rep.chips.resize(NC);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
+    VG_HIP_CHECK(hipEventCreate(&ev0));
+    VG_HIP_CHECK(hipEventCreate(&ev1));
+    uint64_t scratch_words = 0, total_cells_all = 0, table_words = 0;
+    try {
+        // working-layout copies, as prove makes them (traces generated on the device are already column-major Montgomery)
+        std::vector<DMat> own;
+        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
+            if (!t->nat.empty()) return t->nat.view();
+            own.emplace_back(&c, t->height, t->width);
+            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
+            return own.back().view();
+        };
+        own.reserve(NC + preprocessed.size());
+        // per chip: the launch shape, its column flags and its slices of the scratch (u32 words; launch.hpp).  Zeroed: the workgroup tables
+        // [GX][cells][4], detected [4] u64; written whole by merge and pack: counts [cells][2] u64, rows [cells][2], packed
+        std::vector<vk::CovArgs> args(NC);
+        std::vector<uint64_t> wg_at(NC, 0), det_at(NC, 0), cnt_at(NC, 0), row_at(NC, 0), pack_at(NC, 0), cap(NC, 0), flag_at(NC, 0);
+        std::vector<uint32_t> flag_words;
+        uint64_t zeroed = 0, packed = 0;
+        for (size_t i = 0; i < NC; i++) {
+            const AirDesc& air = machine_.airs[i];
+            vk::CovArgs& v = args[i];
+            v = vk::CovArgs{};
+            vk::MaArgs& a = v.m;
+            a.K = air.program.num_asserts;
+            v.M = (uint32_t)air.interactions.size();
+            CoverageChipStat& cs = rep.chips[i];
+            cs.width = air.width; cs.n_constraints = a.K; cs.n_interactions = v.M; cs.height = main[i]->height;
+            cs.kills.assign((size_t)(a.K + v.M) * D, 0); cs.sole.assign((size_t)(a.K + v.M) * D, 0);
+            const double evaluations = ma_evaluations(air, main[i]->height, D);
+            rep.evaluations += evaluations;
+            if (!air.width) continue;
+            const vk::DMatView mv = working(main[i]);
+            a.main = mv.data; a.mstride = mv.stride; a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
+            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
+            a.prog = (const vair::Instr*)prog_dev_[i].data;
+            a.n_instrs = (uint32_t)air.program.instrs.size();
+            a.n_regs = air.program.num_regs;
+            a.iw = iw_dev_[i].data;
+            a.evaluations = evaluations;
+            a.D = D;
+            for (uint32_t k = 0; k < D; k++) a.delta[k] = Fp::from_canonical(o.deltas[k]).v;
+            a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
+            try {
+                vk::cov_shape(v, o.max_workgroups);
+            } catch (const std::invalid_argument& e) {
+                throw std::invalid_argument(std::string(e.what()) + " (chip " + air.name + ")");
+            }
+            const double baselines = a.K ? (a.n == 1 ? 1.0 : 2.0) * (double)a.n * (a.CY - 1) : 0;  // every column slice evaluates the baselines of its rows
+            a.evaluations += baselines; rep.evaluations += baselines;
+            const std::vector<uint32_t> fl = ma_column_flags(air);
+            bool masks_ok = false;
+            const std::vector<uint32_t> bm = ma_bus_masks(air, masks_ok);
+            a.bus_walk = masks_ok ? 0u : 1u;
+            flag_at[i] = flag_words.size();
+            flag_words.insert(flag_words.end(), fl.begin(), fl.end());
+            flag_words.insert(flag_words.end(), bm.begin(), bm.end());
+            const uint64_t cells = vk::cov_cells(v);
+            total_cells_all += cells;
+            table_words += 4 * cells * v.GX;
+            det_at[i] = zeroed; zeroed += 8;
+            wg_at[i] = zeroed; zeroed += 4 * cells * v.GX;
+            cap[i] = std::min<uint64_t>(cells, o.max_cells);
+            cnt_at[i] = packed; packed += 4 * cells;  // u64s: every offset of this region is even
+            row_at[i] = packed; packed += 2 * cells;
+            pack_at[i] = packed; packed += vk::cov_packed_words(v, cap[i]);
+        }
+        scratch_words = zeroed + packed;
+        if (flag_words.empty()) flag_words.push_back(0);
+        DBuf flags(&c, flag_words);
+        for (size_t i = 0; i < NC; i++) args[i].m.flags = flags.data + flag_at[i];
+        c.check_launch("coverage_audit ingest");
+        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
+        uint32_t* const z = scratch.data;
+        uint32_t* const pk = z + zeroed;
+        // the device pass: everything from here to the last download is between the two events
+        VG_HIP_CHECK(hipEventRecord(ev0, st));
+        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(z, 0, (size_t)zeroed * 4, st));
+        for (size_t i = 0; i < NC; i++) {
+            if (!args[i].m.width) continue;
+            vk::launch_cov_audit(st, args[i], z + wg_at[i], reinterpret_cast<unsigned long long*>(z + det_at[i]));
+            vk::launch_cov_merge(st, args[i], z + wg_at[i], reinterpret_cast<unsigned long long*>(pk + cnt_at[i]), pk + row_at[i]);
+            vk::launch_cov_pack(st, args[i], reinterpret_cast<const unsigned long long*>(pk + cnt_at[i]), pk + row_at[i], (uint32_t)cap[i], pk + pack_at[i]);
+        }
+        c.check_launch("coverage_audit");
+        // downloads: per chip its block (detected, the pack's head and sums), then the listed cells — never the cell table itself
+        std::vector<uint32_t> w;
+        for (size_t i = 0; i < NC; i++) {
+            const vk::CovArgs& v = args[i];
+            CoverageChipStat& cs = rep.chips[i];
+            if (v.m.width) {
+                uint32_t dw[8];
+                c.download_small(dw, z + det_at[i], sizeof dw);
+                for (uint32_t k = 0; k < D; k++) cs.detected[k] = ((uint64_t)dw[2 * k + 1] << 32) | dw[2 * k];
+                const size_t TDD = (size_t)(v.m.K + v.M) * D;
+                w.resize(2 + 4 * TDD);
+                c.download_small(w.data(), pk + pack_at[i], w.size() * 4);
+                const uint64_t nonzero = w[0];
+                for (size_t k = 0; k < TDD; k++) { cs.kills[k] = ((uint64_t)w[3 + 4 * k] << 32) | w[2 + 4 * k]; cs.sole[k] = ((uint64_t)w[5 + 4 * k] << 32) | w[4 + 4 * k]; }
+                rep.total_cells += nonzero;
+                const uint64_t take = std::min<uint64_t>(std::min<uint64_t>(nonzero, cap[i]), o.max_cells - rep.cells.size());
+                if (take) {
+                    w.resize(8 * (size_t)take);
+                    c.download_small(w.data(), pk + pack_at[i] + 2 + 4 * TDD, w.size() * 4);
+                    for (size_t k = 0; k < take; k++) {
+                        const uint32_t* e = &w[8 * k];
+                        CoverageCell cell;
+                        cell.chip = (uint32_t)i; cell.delta = e[0] % D; cell.column = (e[0] / D) % v.m.width; cell.detector = e[0] / D / v.m.width;
+                        cell.kills = ((uint64_t)e[2] << 32) | e[1]; cell.sole = ((uint64_t)e[4] << 32) | e[3]; cell.first_row = e[5]; cell.first_sole_row = e[6];
+                        rep.cells.push_back(cell);
+                    }
+                }
+            }
+            coverage_classify(cs, D);
+        }
+        rep.truncated = rep.total_cells > rep.cells.size();
+        VG_HIP_CHECK(hipEventRecord(ev1, st));
+        c.sync();
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
+    } catch (const BusAuditNoMemory&) {
+        throw;
+    } catch (const std::bad_alloc&) {
+        (void)hipStreamSynchronize(st);
+        throw BusAuditNoMemory("coverage_audit: the device pool cannot give the pass its scratch: per chip 16 bytes per cell (detector, column, delta) and workgroup along its rows (" +
+                               std::to_string(table_words * 4) + " bytes for this witness; max_workgroups bounds it), 24 per cell (" + std::to_string(total_cells_all) +
+                               " cells for this machine), 16 per (detector, delta), 32 per listed cell (max_cells per chip at most): " + std::to_string(scratch_words * 4) +
+                               " bytes in all, plus 12 per column of flags and the working-layout copies of uploaded traces");
+    }
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 }  // namespace vhost

@@ -10,6 +10,7 @@
 #include "constraint_audit.hpp"
 #include "machine.hpp"
 #include "mutation_audit.hpp"
+#include "coverage_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -119,6 +120,12 @@ class Prover {
     // like a proof.  Scratch from the pool: 8 bytes per (column, delta, workgroup of rows), 24 per (column, delta), 4 per listed row slot.
     MutationReport mutation_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
                                   const MutationAuditOpts& opts);
+
+    // Coverage audit of a witness (host/coverage_audit.hpp, kernels/coverage_audit.hip): which constraint or interaction detects each of the
+    // mutation audit's mutations; the same trace handles, queued on the context like a proof.  Scratch from the pool: per chip 16 bytes
+    // per cell (detector, column, delta) and workgroup along its rows, 24 per cell, 16 per (detector, delta), 32 per listed cell.
+    CoverageReport coverage_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
+                                  const CoverageAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

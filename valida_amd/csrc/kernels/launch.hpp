@@ -217,6 +217,26 @@ void launch_ma_count(hipStream_t st, const MaArgs& a, unsigned long long* totals
 // entries below e_cut with a free row are listed
 void launch_ma_scan(hipStream_t st, const MaArgs& a, const unsigned long long* totals, const uint32_t* table, uint32_t* prefix, uint32_t e_cut);
 void launch_ma_list(hipStream_t st, const MaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t e_cut, uint32_t R, uint32_t* rows);
+// coverage_audit.hip — the passes of the coverage audit (host/coverage_audit.hpp: contract; Prover::coverage_audit drives them), per chip.  The
+// evaluations are the mutation audit's (MaArgs; mutation_eval.hpp).  A CELL of a chip is ((detector * width + column) * D + delta index),
+// cells = (K + M) * width * D of them.  audit: wg_tables [GX][cells][4] u32 {kills, sole, ~first_row, ~first_sole_row} (zeroed), one table per
+// workgroup along the rows; detected: [4] u64 per delta (zeroed).  merge (folds wg_tables in place): counts [cells][2] u64, rows [cells][2] u32,
+// every cell written.  pack: packed[0] = cells with kills > 0, [1] = 0, then [(K + M) * D][2] u64 the sums over columns of kills /
+// sole (4 words each), then per listed cell (the first `cap`, ascending) 8 words: cell index, kills lo / hi, sole lo / hi, first_row,
+// first_sole_row, 0.
+struct CovArgs {
+    MaArgs m;     // T, NB, CY as cov_shape chose them
+    uint32_t M;   // interactions of the chip
+    uint32_t GX;  // workgroups along the rows: workgroup x walks the row tiles x, x + GX, .. below NB
+};
+// Rows per workgroup, column slices and workgroups along the rows (max_workgroups != 0: at most that many) of a chip's launch; throws
+// std::invalid_argument when no tile of the chip fits the LDS
+void cov_shape(CovArgs& v, uint32_t max_workgroups);
+inline uint64_t cov_cells(const CovArgs& v) { return (uint64_t)(v.m.K + v.M) * v.m.width * v.m.D; }
+inline uint64_t cov_packed_words(const CovArgs& v, uint64_t cap) { return 2 + 4ull * (v.m.K + v.M) * v.m.D + 8 * cap; }
+void launch_cov_audit(hipStream_t st, const CovArgs& v, uint32_t* wg_tables, unsigned long long* detected);
+void launch_cov_merge(hipStream_t st, const CovArgs& v, uint32_t* wg_tables, unsigned long long* counts, uint32_t* rows);
+void launch_cov_pack(hipStream_t st, const CovArgs& v, const unsigned long long* counts, const uint32_t* rows, uint32_t cap, uint32_t* packed);
 // open.hip
 void launch_bary_weights(hipStream_t st, uint64_t n, const uint32_t* min_poly_dev, Fp shift, const DeviceTables& tb, uint32_t* w);
 // the same for several (height, point) pairs in one launch: job = { first block (u32), pad, n (u64), min-poly pointer, weight buffer, digit-plane image (or null) }
