@@ -19,12 +19,16 @@ $B --inflight 1 > "$OUT/bench_inflight1.json" 2> "$OUT/bench_inflight1.err"
 rocprofv3 --kernel-trace --stats -d "$OUT/stats2" -o run -- $B $Q --no-extra-legs --steps 24 --warmup 3 > "$OUT/stats2.json" 2> "$OUT/stats2.err"
 rocprofv3 --kernel-trace --stats -d "$OUT/stats1" -o run -- $B $Q --no-extra-legs --inflight 1 --steps 10 --warmup 1 > "$OUT/stats1.json" 2> "$OUT/stats1.err"
 # 2) counters, separate passes, one proof in flight, few steps
-P="env VGPU_BENCH_SHARDED=0 $B $Q --inflight 1 --steps 2 --warmup 1"  # without the sharded-prover leg: its shard-size launches would mix into the per-launch averages
+# without the sharded-prover leg: its shard-size launches would mix into the per-launch averages.  The switch is exported rather than set through `env`
+# behind the `--`: rocprofv3 has the GPU open when it starts the command, and a launcher in between would replace a process that holds the device
+export VGPU_BENCH_SHARDED=0
+P="$B $Q --inflight 1 --steps 2 --warmup 1"
 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY -d "$OUT/pmc_valu" -o run -- $P > "$OUT/pmc_valu.json" 2> "$OUT/pmc_valu.err"
 # VALU issue utilisation per SIMD: busy cycles of the CUs and of the whole GPU next to the VALU-active wave cycles
 rocprofv3 --kernel-trace --pmc SQ_BUSY_CU_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU SQ_WAVE_CYCLES GRBM_GUI_ACTIVE -d "$OUT/pmc_busy" -o run -- $P > "$OUT/pmc_busy.json" 2> "$OUT/pmc_busy.err"
 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d "$OUT/pmc_fetch" -o run -- $P > "$OUT/pmc_fetch.json" 2> "$OUT/pmc_fetch.err"
 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d "$OUT/pmc_write" -o run -- $P > "$OUT/pmc_write.json" 2> "$OUT/pmc_write.err"
+unset VGPU_BENCH_SHARDED
 # full default bench line (with the CPU baseline leg) and the other single-GPU configs
 python $ROOT/bench.py --full > "$OUT/bench_full.json" 2> "$OUT/bench_full.err"
 for w in c3 c4; do $B --workload $w --steps 6 --warmup 2 > "$OUT/bench_$w.json" 2> /dev/null; done

@@ -60,7 +60,11 @@ template <int N> __device__ __forceinline__ void rotl_pair(uint32_t lo, uint32_t
 }
 // gfx950 v_bitop3_b32: any 3-input boolean function in one instruction (truth table over a=0xF0, b=0xCC, c=0xAA).
 // Operands known to be zero at compile time (the capacity lanes of a freshly padded block, in the peeled first
-// round) fold away instead of occupying an issue slot.
+// round) fold away instead of occupying an issue slot.  That reaches compress2 (lanes 9..15 and 17..24 are literal
+// zeros) and, since the row width became a template parameter, the FIRST block of a row hashed by hash_row<Cols, N>
+// with N > 0 (merkle.hip): every lane above word N — all but 5 data lanes, the pad and the end word for the 10-word
+// rows — so most of round 0's parity and theta-apply instructions go.  It never reaches the run-time width (N = 0),
+// where which lanes are zero depends on n_elems, nor a row's later blocks (the state is live).
 #define VK_KNOWN_ZERO(v) (__builtin_constant_p(v) && (v) == 0)
 __device__ __forceinline__ uint32_t xor3(uint32_t a, uint32_t b, uint32_t c) {
     if (VK_KNOWN_ZERO(c)) return a ^ b;

@@ -38,8 +38,64 @@ struct StridedCols {  // one column-major matrix: no pointer table needed (FRI l
     uint64_t stride;
     __device__ __forceinline__ const uint32_t* operator[](int k) const { return base + (uint64_t)k * stride; }
 };
-template <class Cols>
+// ---- rows of a width known at COMPILE time (N > 0: the widths the proving paths really launch, VK_LEAF_WIDTHS / VK_INJECT_WIDTHS below) ----
+// Against the generic code behind it: no `k < rem` test per word (34 uniform compares and branches a wave), the pad word and the end word at
+// constant positions, every load of a block issued before the first is waited for (the generic code's guarded loads wait one by one), and —
+// through kstate_zero + constant positions — lanes above the data that are LITERAL zeros when keccak_f1600 inlines its peeled first round
+// (keccak.hpp, VK_KNOWN_ZERO: a 10-word row leaves at most two live lanes per column).
+// One word at byte offset `off` behind a wave-uniform column base: global_load_dword with the base in SGPRs and the 32-bit offset in ONE VGPR
+// shared by all columns, instead of a 64-bit address per word (v_lshl_add_u64 + flat_load).  The callers keep 4 * rows below 2^32.
+__device__ __forceinline__ uint32_t load_word_at(const uint32_t* base, uint32_t off) {
+#ifdef __HIPCC__
+    typedef const __attribute__((address_space(1))) char* gbytes;  // every column is device (global) memory
+    return *(const __attribute__((address_space(1))) uint32_t*)((gbytes)base + off);
+#else
+    return *reinterpret_cast<const uint32_t*>(reinterpret_cast<const char*>(base) + off);
+#endif
+}
+// words BASE .. BASE + CNT - 1 of the row into the rate: the column addresses first (wave-uniform: wide scalar loads of the pointer table),
+// then all loads, then the conversions
+template <class Cols, int BASE, int CNT>
+__device__ __forceinline__ void absorb_words(KState& a, const Cols cols, uint32_t off) {
+    if constexpr (CNT > 0) {
+        const uint32_t* p[CNT];
+        uint32_t w[CNT];
+#pragma unroll
+        for (int k = 0; k < CNT; k++) p[k] = cols[BASE + k];
+#pragma unroll
+        for (int k = 0; k < CNT; k++) w[k] = load_word_at(p[k], off);
+#pragma unroll
+        for (int k = 0; k < CNT; k++) absorb_word(a, k, Fp::raw(w[k]).canonical());
+    }
+}
+// the full blocks from word BASE on, each followed by its permutation, then the data words of the last block
+template <class Cols, int BASE, int N>
+__device__ __forceinline__ void absorb_blocks(KState& a, const Cols cols, uint32_t off) {
+    if constexpr (N - BASE >= 34) {
+        absorb_words<Cols, BASE, 34>(a, cols, off);
+        keccak_f1600<false>(a);
+        absorb_blocks<Cols, BASE + 34, N>(a, cols, off);
+    } else {
+        absorb_words<Cols, BASE, N - BASE>(a, cols, off);
+    }
+}
+template <class Cols, int N>
+__device__ __forceinline__ void hash_row_fixed(const Cols cols, uint64_t r, uint32_t (&out)[8]) {
+    KState a;
+    kstate_zero(a);
+    absorb_blocks<Cols, 0, N>(a, cols, (uint32_t)r << 2);
+    absorb_word(a, N % 34, 0x01u);      // Keccak (not SHA-3) domain padding ...
+    absorb_word(a, 33, 0x80000000u);    // ... and the end bit: one word 0x80000001 when N % 34 == 33
+    keccak_f1600<true>(a);
+    squeeze_digest(a, out);
+}
+// whether a launch over n_rows rows may take a compile-time width (load_word_at's 32-bit byte offset)
+constexpr uint64_t KECCAK_FIXED_MAX_ROWS = 1ull << 30;
+
+// N = 0: the width at run time (AIRs captured at run time, any width not in the tables); N > 0: n_elems == N is the caller's word
+template <class Cols, int N = 0>
 __device__ __forceinline__ void hash_row(const Cols cols, int n_elems, uint64_t r, uint32_t (&out)[8]) {
+    if constexpr (N > 0) { hash_row_fixed<Cols, N>(cols, r, out); return; }
     KState a;
     kstate_zero(a);
     int base = 0;
@@ -82,17 +138,18 @@ __device__ __forceinline__ void store_digest(uint32_t* p, const uint32_t (&d)[8]
     q[1] = make_uint4(d[4], d[5], d[6], d[7]);
 }
 
-// leaf layer: digests[r] = H(row r)
-template <class Cols>
+// leaf layer: digests[r] = H(row r).  N > 0: n_elems == N, compiled in (launch_keccak_leaves picks the instance)
+template <class Cols, int N = 0>
 __global__ void __launch_bounds__(256) k_keccak_leaves(const Cols cols, int n_elems, uint64_t n_rows, uint32_t* __restrict__ digests) {
     uint64_t r = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= n_rows) return;
     uint32_t d[8];
-    hash_row(cols, n_elems, r, d);
+    hash_row<Cols, N>(cols, n_elems, r, d);
     store_digest(digests + 8 * r, d);
 }
 
-// next[i] = C(prev[2i], prev[2i+1]); if n_elems > 0: next[i] = C(next[i], H(row i of cols))
+// next[i] = C(prev[2i], prev[2i+1]); if n_elems > 0: next[i] = C(next[i], H(row i of cols)).  N > 0: n_elems == N, compiled in
+template <int N = 0>
 __global__ void __launch_bounds__(256) k_keccak_compress(const uint32_t* __restrict__ prev, const uint32_t* const* __restrict__ cols, int n_elems, uint64_t n_out,
                                   uint32_t* __restrict__ next) {
     uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -101,9 +158,9 @@ __global__ void __launch_bounds__(256) k_keccak_compress(const uint32_t* __restr
     load_digest(prev + 16 * i, l);
     load_digest(prev + 16 * i + 8, r);
     compress2(l, r, d);
-    if (n_elems > 0) {
+    if (N > 0 || n_elems > 0) {
         uint32_t h[8], d2[8];
-        hash_row(PtrCols{cols}, n_elems, i, h);
+        hash_row<PtrCols, N>(PtrCols{cols}, n_elems, i, h);
         compress2(d, h, d2);
         store_digest(next + 8 * i, d2);
     } else {
@@ -399,35 +456,80 @@ void launch_keccak_bottom_q(hipStream_t st, const uint32_t* jobs_dev, uint32_t n
     VK_LAUNCH(k_keccak_bottom_q, dim3((4 * n_jobs + 255) / 256), dim3(256), 0, st, jobs_dev, n_jobs, indices_dev, dst);
 }
 
+// ---- the thread-per-node launches: a kernel instance with the row width compiled in where there is one ----
+// The widths the C2 and C4 proving paths launch, logged from these launchers over one proof of each (profiles/r10_keccak_row_widths.txt):
+//   leaves of the tallest matrices, column lists:     10 (two of the three commitment rounds), 14 (the third) — 2^23 rows each in C2 and C4
+//   leaves of the big FRI layers, one strided matrix: 10 (a pair of Ext5 values per row)
+//   injected rows (concatenated widths of a height):  C2 20, 55, 67;  C4 10, 20, 25, 40, 51, 61, 95
+// Any other width — AIRs captured at run time, other machines — runs the N = 0 instance.  An instance is 900 (leaves) to 5300 (three-block
+// injection) static instructions: the tables hold what the list needs, not 1..68.
+#define VK_LEAF_WIDTHS(X) X(10) X(14)
+#define VK_LEAF_WIDTHS_STRIDED(X) X(10)
+#define VK_INJECT_WIDTHS(X) X(10) X(20) X(25) X(40) X(51) X(55) X(61) X(67) X(95)
+// the width to dispatch on: n_elems, or 0 (generic) where load_word_at's 32-bit byte offset does not reach
+static int keccak_fixed_width(int n_elems, uint64_t n_rows) { return n_rows <= KECCAK_FIXED_MAX_ROWS ? n_elems : 0; }
+// launch_*_n / *_instance return the width compiled into the instance they launched (0: the generic one) — the emulation tests read it
+template <class Cols, int N> static int launch_leaves_n(hipStream_t st, Cols cols, int n_elems, uint64_t n_rows, uint32_t* digests) {
+    auto k = &k_keccak_leaves<Cols, N>;
+    VK_LAUNCH(k, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, st, cols, n_elems, n_rows, digests);
+    return N;
+}
+template <int N> static int launch_compress_n(hipStream_t st, const uint32_t* prev, const uint32_t* const* cols_dev, int n_elems, uint64_t n_out, uint32_t* next) {
+    auto k = &k_keccak_compress<N>;
+    VK_LAUNCH(k, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, st, prev, cols_dev, n_elems, n_out, next);
+    return N;
+}
+static int launch_leaves_instance(hipStream_t st, PtrCols cols, int n_elems, uint64_t n_rows, uint32_t* digests) {
+    switch (keccak_fixed_width(n_elems, n_rows)) {
+#define X(W) case W: return launch_leaves_n<PtrCols, W>(st, cols, n_elems, n_rows, digests);
+        VK_LEAF_WIDTHS(X)
+#undef X
+    }
+    return launch_leaves_n<PtrCols, 0>(st, cols, n_elems, n_rows, digests);
+}
+static int launch_leaves_instance(hipStream_t st, StridedCols cols, int n_elems, uint64_t n_rows, uint32_t* digests) {
+    switch (keccak_fixed_width(n_elems, n_rows)) {
+#define X(W) case W: return launch_leaves_n<StridedCols, W>(st, cols, n_elems, n_rows, digests);
+        VK_LEAF_WIDTHS_STRIDED(X)
+#undef X
+    }
+    return launch_leaves_n<StridedCols, 0>(st, cols, n_elems, n_rows, digests);
+}
+static int launch_compress_instance(hipStream_t st, const uint32_t* prev, const uint32_t* const* cols_dev, int n_elems, uint64_t n_out, uint32_t* next) {
+    switch (keccak_fixed_width(n_elems, n_out)) {
+#define X(W) case W: return launch_compress_n<W>(st, prev, cols_dev, n_elems, n_out, next);
+        VK_INJECT_WIDTHS(X)
+#undef X
+    }
+    return launch_compress_n<0>(st, prev, cols_dev, n_elems, n_out, next);
+}
+
 void launch_keccak_leaves(hipStream_t st, const uint32_t* const* cols_dev, int n_elems, uint64_t n_rows, uint32_t* digests) {
-    unsigned blocks = (unsigned)((n_rows + 255) / 256);
     const bool pairs = keccak_pairs_enabled() && n_rows <= KECCAK_PAIR_MAX_NODES;
     ProfScope ps(pairs ? "k_keccak_leaves_pair" : "k_keccak_leaves", st, (double)n_rows * (4.0 * n_elems + 32.0), (double)n_rows * row_perms(n_elems) * KECCAK_VALU_PER_PERM / 64.0);
     if (pairs) {
         VK_LAUNCH(k_keccak_leaves_pair<PtrCols>, dim3((unsigned)((2 * n_rows + 255) / 256)), dim3(256), 0, st, PtrCols{cols_dev}, n_elems, n_rows, digests);
         return;
     }
-    VK_LAUNCH(k_keccak_leaves<PtrCols>, dim3(blocks), dim3(256), 0, st, PtrCols{cols_dev}, n_elems, n_rows, digests);
+    launch_leaves_instance(st, PtrCols{cols_dev}, n_elems, n_rows, digests);
 }
 void launch_keccak_leaves_strided(hipStream_t st, const uint32_t* base, uint64_t stride, int n_elems, uint64_t n_rows, uint32_t* digests) {
-    unsigned blocks = (unsigned)((n_rows + 255) / 256);
     const bool pairs = keccak_pairs_enabled() && n_rows <= KECCAK_PAIR_MAX_NODES;
     ProfScope ps(pairs ? "k_keccak_leaves_pair" : "k_keccak_leaves", st, (double)n_rows * (4.0 * n_elems + 32.0), (double)n_rows * row_perms(n_elems) * KECCAK_VALU_PER_PERM / 64.0);
     if (pairs) {
         VK_LAUNCH(k_keccak_leaves_pair<StridedCols>, dim3((unsigned)((2 * n_rows + 255) / 256)), dim3(256), 0, st, StridedCols{base, stride}, n_elems, n_rows, digests);
         return;
     }
-    VK_LAUNCH(k_keccak_leaves<StridedCols>, dim3(blocks), dim3(256), 0, st, StridedCols{base, stride}, n_elems, n_rows, digests);
+    launch_leaves_instance(st, StridedCols{base, stride}, n_elems, n_rows, digests);
 }
 void launch_keccak_compress(hipStream_t st, const uint32_t* prev, const uint32_t* const* cols_dev, int n_elems, uint64_t n_out, uint32_t* next) {
-    unsigned blocks = (unsigned)((n_out + 255) / 256);
     const bool pairs = keccak_pairs_enabled() && n_out <= KECCAK_PAIR_MAX_NODES;
     ProfScope ps(pairs ? "k_keccak_compress_pair" : "k_keccak_compress", st, (double)n_out * (96.0 + 4.0 * n_elems), (double)n_out * node_perms(n_elems) * KECCAK_VALU_PER_PERM / 64.0);
     if (pairs) {
         VK_LAUNCH(k_keccak_compress_pair, dim3((unsigned)((2 * n_out + 255) / 256)), dim3(256), 0, st, prev, cols_dev, n_elems, n_out, next);
         return;
     }
-    VK_LAUNCH(k_keccak_compress, dim3(blocks), dim3(256), 0, st, prev, cols_dev, n_elems, n_out, next);
+    launch_compress_instance(st, prev, cols_dev, n_elems, n_out, next);
 }
 
 }  // namespace vk
