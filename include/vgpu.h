@@ -414,7 +414,7 @@ void vgpu_constraint_report_free(vgpu_constraint_report_t* r);
  *                 `truncated` says the list was cut.  No challenge, no hash and no floating point enter: the same words run after run, for
  *                 Machine.basic (compiled chip templates) and for captured AIRs (the interpreted program) alike.
  * The report is a statement about single-cell slack on THIS witness; it is not a soundness proof (a bound cell may be bound only on the rows
- * this witness has, and slack of two cells changed together is not looked for).
+ * this witness has; slack of two cells of one row changed together is the pair audit's subject, below).
  * Options: a zero field selects its default — max_entries 1024, max_rows_per_entry 4 (at most 2^24 and 4096), n_deltas 0 = the pair {1, p - 1};
  * otherwise deltas[0 .. n_deltas) are 1 to 4 distinct canonical values in 1..p-1; opts may be NULL; reserved != 0 is refused.
  * vgpu_mutation_audit runs on the device (kernels/mutation_audit.hip), queued on the prover context like a proof or the other audits; it accepts
@@ -451,6 +451,70 @@ const uint32_t* vgpu_mutation_report_words(const vgpu_mutation_report_t* r);
  * out[1]: wall time of the whole call; milliseconds.  out[2]: the Air::eval row evaluations the audit performed (baselines included) */
 void vgpu_mutation_report_timing(const vgpu_mutation_report_t* r, double out[3]);
 void vgpu_mutation_report_free(vgpu_mutation_report_t* r);
+
+/* ---- Pair audit: WHICH TWO cells of one row could be changed together without any AIR constraint or bus noticing although changing one of them
+ * alone is noticed — the next order of slack after the mutation audit (a column that `a + b - c = 0` or a bus field `a + b` mentions looks bound
+ * to single mutations; a prover can still move a by +1 and b by -1).  Inputs: exactly what vgpu_prove and the audits take.
+ *   pair mutation  chip h with main matrix M (height n, width w), a row r, two main columns c1 < c2 and a delta pair q = i D + j over the
+ *                  option's deltas: M'' = M except M''[r][c1] = M[r][c1] + d_i and M''[r][c2] = M[r][c2] + d_j mod p.  Both cells are on the
+ *                  same row.  Preprocessed columns are never mutated.
+ *   detected       exactly the mutation audit's two rules applied to M'': AIR-detected when a constraint is non-zero at row r or (r - 1) mod n
+ *                  that was zero at that same row on M (for n = 1 one evaluation, both cells seen as local and as next); bus-detected when the
+ *                  record of some interaction of row r differs (count 0 is no record).
+ *   counts         per (chip, c1, c2, q), exact over all n rows: `free` rows where the pair mutation is neither AIR- nor bus-detected;
+ *                  `compensated` rows that are free although at least one of the single mutations (r, c1, d_i), (r, c2, d_j) is detected by
+ *                  the mutation audit's rules.  Compensated rows are the finding; the other free rows are already in the mutation report.
+ *   coupled        a pair is coupled when some constraint of the chip's Program reads both columns in any role, or some single interaction's
+ *                  virtual columns (count or fields) reference both, or n = 1.  For an uncoupled pair the detectors of the pair mutation are
+ *                  the union of the two singles' detectors, so compensated = 0 and free = the rows where both singles are free: both passes
+ *                  skip uncoupled pairs.  The report never depends on a shortcut or on a tuning knob.
+ *   order          an entry is a (chip, c1, c2, q) with compensated > 0; entries ascend by (chip, c1, c2, q), each with its first
+ *                  max_rows_per_entry compensated rows in ascending order.  Only the first max_entries entries are listed; the totals stay
+ *                  exact and `truncated` says the list was cut.  No challenge, no hash and no floating point enter: the same words run after
+ *                  run, from device and host, for Machine.basic and for captured AIRs.
+ * What it is not: it covers same-row pairs only; cross-row pairs and triples are not looked for; it is a statement about THIS witness, not a
+ * soundness proof; `check`'s exit status never depends on it.
+ * Options: a zero field selects its default — max_entries 1024, max_rows_per_entry 4 (at most 2^24 and 4096), n_deltas 0 = the pair {1, p - 1},
+ * otherwise deltas[0 .. n_deltas) are 1 to 4 distinct canonical values in 1..p-1 (the mutation audit's limits); chip_mask bit h = audit chip h,
+ * 0 = all chips (a bit beyond the machine's chips is refused); unselected chips keep their block with audited = 0 and zero counts; opts may
+ * be NULL; reserved != 0 is refused.
+ * vgpu_pair_audit runs on the device (kernels/pair_audit.hip), queued on the prover context like a proof or the other audits; it accepts
+ * device-generated and uploaded traces.  Scratch comes from the prover's pool, with E = coupled pairs x D^2 entries per chip: 16 E + 256 bytes
+ * of totals, 8 E bytes of bus masks and 4 bytes per pair, 8 E bytes per workgroup of T rows (table and prefix; T = 256 rows, less for a chip
+ * whose tile is large), 4 max_rows_per_entry bytes per entry up to the last listed one of the chip with the most, plus the working-layout copy
+ * of every uploaded trace; VGPU_ERR_OOM with a message when the pool cannot give them (chip_mask audits fewer chips at a time);
+ * VGPU_ERR_INVALID_ARG for bad shapes, for a chip of more than 96 constraints, of more than 4096 columns, and for one whose row tile does not
+ * fit 160 KB of LDS at 64 rows (about 620 columns).
+ * vgpu_pair_audit_host is the same contract on the host over canonical row-major matrices (one thread, no device, no limits).  Both validate
+ * shapes as vgpu_prove does.
+ * Report image (vgpu_pair_report_words, u32 words; u64 values as lo, hi):
+ *   [0] 0x31525056 "VPR1" [1] word count [2] n_deltas D [3] truncated [4,5] total_entries = (chip, c1, c2, q) with compensated > 0 (exact even
+ *   when the list is cut) [6] reported [7] n_chips [8..11] the deltas (canonical; unused slots 0)
+ *   per chip, in machine order, 8 + 4 D^2 words: width, constraints, interactions, audited (0 / 1), height (u64), coupled pairs, slack pairs
+ *   (pairs with compensated > 0 for some q), then per q the sums over ALL the chip's pairs of free and compensated (u64 each; an uncoupled
+ *   pair contributes its exact free and 0)
+ *   per reported entry: chip, c1, c2, q, n_listed, 0, free, compensated (u64 each), then n_listed rows. */
+typedef struct vgpu_pair_audit_opts {
+    uint64_t max_entries;
+    uint32_t max_rows_per_entry;
+    uint32_t n_deltas;
+    uint32_t deltas[4];
+    uint32_t chip_mask;
+    uint32_t reserved;
+} vgpu_pair_audit_opts_t;
+typedef struct vgpu_pair_report vgpu_pair_report_t;
+int32_t vgpu_pair_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                        uint32_t n_prep, const vgpu_pair_audit_opts_t* opts, vgpu_pair_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_pair_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                             const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                             const vgpu_pair_audit_opts_t* opts, vgpu_pair_report_t** out);
+uint64_t vgpu_pair_report_len(const vgpu_pair_report_t* r);
+const uint32_t* vgpu_pair_report_words(const vgpu_pair_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: the Air::eval row evaluations the
+ * audit performed (baselines and single mutations included) */
+void vgpu_pair_report_timing(const vgpu_pair_report_t* r, double out[3]);
+void vgpu_pair_report_free(vgpu_pair_report_t* r);
 
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.

@@ -41,6 +41,7 @@ enum { hipFuncAttributeMaxDynamicSharedMemorySize = 8 };
 inline const char* hipGetErrorString(hipError_t) { return "hipemu"; }
 inline hipError_t hipGetLastError() { return hipSuccess; }
 inline hipError_t hipFuncSetAttribute(const void*, int, int) { return hipSuccess; }
+inline hipError_t hipGetDevice(int* dev) { *dev = 0; return hipSuccess; }
 inline hipError_t hipEventCreate(hipEvent_t*) { return hipSuccess; }
 inline hipError_t hipEventDestroy(hipEvent_t) { return hipSuccess; }
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0; return hipSuccess; }

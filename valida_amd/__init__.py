@@ -1210,6 +1210,117 @@ def mutation_audit_host(machine, main_matrices, preprocessed, deltas=None, max_e
     return _mutation_report(h)
 
 
+class PairAuditOpts(ctypes.Structure):  # vgpu_pair_audit_opts_t
+    _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("n_deltas", ctypes.c_uint32), ("deltas", ctypes.c_uint32 * 4),
+                ("chip_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class PairReport:
+    """The pair audit of a witness (vgpu_pair_audit / vgpu_pair_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
+    deltas, truncated, total_entries ((chip, c1, c2, q) with a compensated row), reported,
+    chips = [dict(chip, width, constraints, interactions, audited, height, coupled, slack, free=[per q], compensated=[per q])] (sums over all
+    the chip's pairs; q = i * len(deltas) + j adds deltas[i] to c1 and deltas[j] to c2),
+    entries = [dict(chip, c1, c2, q, free, compensated, rows=[first compensated rows])] ascending by (chip, c1, c2, q),
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (Air::eval row evaluations performed)."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 12 or w[0] != 0x31525056 or w[1] != len(w) or not 1 <= w[2] <= 4:
+            raise ValueError("not a pair report image")
+        self.words = np.array(w, dtype=np.uint32)
+        D = w[2]
+        self.deltas, self.truncated = w[8:8 + D], bool(w[3])
+        self.total_entries, self.reported = w[4] | (w[5] << 32), w[6]
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 12
+        self.chips = []
+        for c in range(w[7]):
+            self.chips.append(dict(chip=c, width=w[pos], constraints=w[pos + 1], interactions=w[pos + 2], audited=bool(w[pos + 3]), height=u64(pos + 4), coupled=w[pos + 6],
+                                   slack=w[pos + 7], free=[u64(pos + 8 + 4 * q) for q in range(D * D)], compensated=[u64(pos + 10 + 4 * q) for q in range(D * D)]))
+            pos += 8 + 4 * D * D
+        self.entries = []
+        for _ in range(self.reported):
+            n_listed = w[pos + 4]
+            self.entries.append(dict(chip=w[pos], c1=w[pos + 1], c2=w[pos + 2], q=w[pos + 3], free=u64(pos + 6), compensated=u64(pos + 8), rows=w[pos + 10:pos + 10 + n_listed]))
+            pos += 10 + n_listed
+        assert pos == len(w)
+
+    def slack_pairs(self, chip):
+        """The pairs (c1, c2) of `chip` with a compensated row for some delta pair — as far as the list goes (exact when not truncated)."""
+        return sorted(set((e["c1"], e["c2"]) for e in self.entries if e["chip"] == chip))
+
+    def to_dict(self):
+        return dict(deltas=self.deltas, truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
+                    evaluations=self.evaluations, chips=self.chips, entries=self.entries)
+
+    def to_json(self):
+        import json
+
+        return json.dumps(self.to_dict())
+
+
+def _pair_opts(deltas, max_entries, max_rows_per_entry, chips):
+    # as _mutation_opts: explicit zeros and an empty delta list are refused here, with the library's status code
+    if int(max_entries) < 1 or int(max_rows_per_entry) < 1:
+        raise VgpuError(-1, "pair_audit: max_entries and max_rows_per_entry must be at least 1")
+    ds = [int(d) for d in ((1, P - 1) if deltas is None else deltas)]
+    if not 1 <= len(ds) <= 4:
+        raise VgpuError(-1, "pair_audit: 1 to 4 deltas (got %d)" % len(ds))
+    if any(d < 0 or d > 0xFFFFFFFF for d in ds):
+        raise VgpuError(-1, "pair_audit: a delta must be a canonical value in 1..p-1")
+    mask = 0
+    if chips is not None:
+        cs = [int(c) for c in chips]
+        if not cs or any(c < 0 or c > 31 for c in cs):
+            raise VgpuError(-1, "pair_audit: chips is a non-empty list of chip indices below 32")
+        for c in cs:
+            mask |= 1 << c
+    return PairAuditOpts(int(max_entries), int(max_rows_per_entry), len(ds), (ctypes.c_uint32 * 4)(*ds), mask, 0)
+
+
+def _pair_report(h):
+    L = lib()
+    L.vgpu_pair_report_len.restype = ctypes.c_uint64
+    L.vgpu_pair_report_words.restype = c_u32p
+    L.vgpu_pair_report_len.argtypes = L.vgpu_pair_report_words.argtypes = L.vgpu_pair_report_free.argtypes = [ctypes.c_void_p]
+    L.vgpu_pair_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    try:
+        n = int(L.vgpu_pair_report_len(h))
+        words = np.ctypeslib.as_array(L.vgpu_pair_report_words(h), shape=(n,)).copy()
+        tm = (ctypes.c_double * 3)()
+        L.vgpu_pair_report_timing(h, tm)
+    finally:
+        L.vgpu_pair_report_free(h)
+    return PairReport(words, tm[0], tm[1], tm[2])
+
+
+def pair_audit_host(machine, main_matrices, preprocessed, deltas=None, max_entries=1024, max_rows_per_entry=4, chips=None):
+    """The pair audit on the HOST (vgpu_pair_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
+    [(chip index, matrix)], deltas = 1 to 4 distinct values in 1..p-1 (default (1, p - 1)), chips = the chip indices to audit (default: all);
+    a PairReport back."""
+    opts = _pair_opts(deltas, max_entries, max_rows_per_entry, chips)
+    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
+    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
+    for m in mains + [m for _, m in preps]:
+        if m.ndim != 2:
+            raise VgpuError(-1, "pair_audit: traces are two-dimensional matrices")
+
+    def arrays(ms):
+        n = max(1, len(ms))
+        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
+
+    mp, mh, mw = arrays(mains)
+    pp, ph, pw = arrays([m for _, m in preps])
+    chip_ids = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
+    h = ctypes.c_void_p()
+    _check(lib().vgpu_pair_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chip_ids, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
+    return _pair_report(h)
+
+
 class CoverageAuditOpts(ctypes.Structure):  # vgpu_coverage_audit_opts_t
     _fields_ = [("max_cells", ctypes.c_uint64), ("n_deltas", ctypes.c_uint32), ("deltas", ctypes.c_uint32 * 4), ("max_workgroups", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32 * 2)]
@@ -1586,6 +1697,18 @@ class Prover:
         h = ctypes.c_void_p()
         _check(lib().vgpu_mutation_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
         return _mutation_report(h)
+
+    def pair_audit(self, main, preprocessed, deltas=None, max_entries=1024, max_rows_per_entry=4, chips=None):
+        """Which two cells of one row of this witness could be changed together without any AIR constraint or bus noticing although one of the
+        changes alone is noticed (vgpu_pair_audit): the arguments of prove, deltas as in mutation_audit, chips = the chip indices to audit
+        (default: all); a PairReport back."""
+        opts = _pair_opts(deltas, max_entries, max_rows_per_entry, chips)
+        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
+        chip_ids = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
+        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_pair_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
+        return _pair_report(h)
 
     def coverage_audit(self, main, preprocessed, deltas=None, max_cells=8192, max_workgroups=0):
         """Which constraint or interaction detects each mutation of the mutation audit (vgpu_coverage_audit): the arguments of prove, deltas as

@@ -27,6 +27,7 @@ SOURCES = [
     "kernels/constraint_audit.hip",
     "kernels/mutation_audit.hip",
     "kernels/coverage_audit.hip",
+    "kernels/pair_audit.hip",
     "host/prover.cpp",
     "host/sharded_prover.cpp",
     "capi.cpp",

@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -41,6 +41,11 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         interaction essential`.  "Dead" says what THIS program reaches with single-cell changes by these deltas — not a fault of the witness or of
         the AIR; "never the only detector" does not mean removable (it may be the only guard against a two-cell change).  The exit status does not
         depend on this flag.  coverage_merge adds the "coverage" keys of several reports of one machine and one delta set into a corpus report.
+        --pairs adds the pair audit of the same witness (vgpu_pair_audit: which two cells of one row could be changed together without any AIR
+        constraint or bus noticing although one of the changes alone is noticed), on the same path (device or --host) and with the same --deltas;
+        --chips=cpu,3 restricts it to those chips (names or indices).  The JSON report gets one more key, "pairs" (PairReport.to_json's object);
+        after the other lines stdout gets one line per chip that has a slack pair, `add: 6 slack pairs of 136 coupled: (0,4) (0,8) ..`.  Same-row
+        pairs on THIS witness only, not a soundness proof: the exit status does not depend on this flag.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -175,6 +180,39 @@ def mutation_lines(report):
     return lines
 
 
+def parse_chips(text):
+    """--chips: comma-separated chip names or indices; None (all chips) when empty."""
+    import valida_amd as va
+
+    out = []
+    for x in (text or "").split(","):
+        x = x.strip()
+        if not x:
+            continue
+        if x in va.CHIP_NAMES:
+            out.append(list(va.CHIP_NAMES).index(x))
+        elif x.isdigit() and int(x) < va.NUM_CHIPS:
+            out.append(int(x))
+        else:
+            raise va.VgpuError(-1, "check --chips: %r is neither a chip name (%s) nor an index below %d" % (x, ", ".join(va.CHIP_NAMES), va.NUM_CHIPS))
+    return out or None
+
+
+def pair_lines(report, limit=12):
+    """One line per chip of a pair report that has a slack pair: how many of its coupled pairs, and the first of them as (c1,c2)."""
+    import valida_amd as va
+
+    lines = []
+    for c in report.chips:
+        if not c["slack"]:
+            continue
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        pairs = report.slack_pairs(c["chip"])
+        shown = " ".join("(%d,%d)" % p for p in pairs[:limit]) + (" .." if c["slack"] > min(limit, len(pairs)) else "")
+        lines.append("%s: %d slack pair%s of %d coupled: %s" % (name, c["slack"], "" if c["slack"] == 1 else "s", c["coupled"], shown))
+    return lines
+
+
 def coverage_lines(report):
     """One line per chip of a coverage report that has a dead or shadowed detector: the dead constraints / interactions by index, those that
     are never the only detector of a mutation, and how many detectors are essential."""
@@ -217,9 +255,12 @@ def main(argv=None):
     ap.add_argument("--constraints", action="store_true", help="check: also the constraint audit (which AIR constraints fail on which rows)")
     ap.add_argument("--max-constraints", type=int, default=64)
     ap.add_argument("--mutations", action="store_true", help="check: also the mutation audit (which trace cells no constraint or bus binds)")
-    ap.add_argument("--deltas", default="1,-1", help="check --mutations / --coverage: 1 to 4 distinct deltas, comma-separated integers mod p (as --deltas=1,-1)")
+    ap.add_argument("--deltas", default="1,-1", help="check --mutations / --coverage / --pairs: 1 to 4 distinct deltas, comma-separated integers mod p (as --deltas=1,-1)")
     ap.add_argument("--coverage", action="store_true", help="check: also the coverage audit (which constraint or bus interaction detects each mutation; "
                     "dead = not reached by this witness, not a fault; never changes the exit status)")
+    ap.add_argument("--pairs", action="store_true", help="check: also the pair audit (two cells of one row that can change together unnoticed although one "
+                    "alone is noticed; never changes the exit status)")
+    ap.add_argument("--chips", default="", help="check --pairs: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -249,6 +290,7 @@ def main(argv=None):
                 creport = va.constraint_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_constraints=args.max_constraints) if args.constraints else None
                 mreport = va.mutation_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_entries=1 << 20) if args.mutations else None
                 kreport = va.coverage_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_cells=1 << 20) if args.coverage else None
+                preport = va.pair_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.pairs else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -258,6 +300,7 @@ def main(argv=None):
                 creport = prover.constraint_audit(main, prep, max_constraints=args.max_constraints) if args.constraints else None
                 mreport = prover.mutation_audit(main, prep, deltas=parse_deltas(args.deltas), max_entries=1 << 20) if args.mutations else None
                 kreport = prover.coverage_audit(main, prep, deltas=parse_deltas(args.deltas), max_cells=1 << 20) if args.coverage else None
+                preport = prover.pair_audit(main, prep, deltas=parse_deltas(args.deltas), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.pairs else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -265,10 +308,12 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), mutations=mreport.to_dict()))
             if kreport is not None:
                 text = json.dumps(dict(json.loads(text), coverage=kreport.to_dict()))
+            if preport is not None:
+                text = json.dumps(dict(json.loads(text), pairs=preport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
-                    coverage_lines(kreport) if kreport is not None else []):
+                    coverage_lines(kreport) if kreport is not None else []) + (pair_lines(preport) if preport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

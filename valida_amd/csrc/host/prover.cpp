@@ -1569,6 +1569,188 @@ MutationReport Prover::mutation_audit(const std::vector<const DeviceTrace*>& mai
     return rep;
 }
 
+// ---- pair audit (host/pair_audit.hpp; kernels/pair_audit.hip) ------------------------------------------------------------------------------
+PairReport Prover::pair_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const PairAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const PairAuditOpts o = pair_audit_checked_opts(opts_in, machine_.airs.size());
+    std::vector<ConstraintShape> ms, ps;
+    std::vector<int> prep_chips, prep_slot;
+    for (auto t : main) { if (!t) throw std::invalid_argument("pair_audit: null trace"); ms.push_back({t->height, t->width}); }
+    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("pair_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
+    pair_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
+    const size_t NC = machine_.airs.size();
+    for (size_t i = 0; i < NC; i++) {
+        if (!pair_audit_selected(o, i)) continue;
+        if (machine_.airs[i].program.num_asserts > vk::CA_MAX_CONSTRAINTS)
+            throw std::invalid_argument("pair_audit: chip " + machine_.airs[i].name + " has " + std::to_string(machine_.airs[i].program.num_asserts) + " constraints; the device audit handles up to " +
+                                        std::to_string(vk::CA_MAX_CONSTRAINTS) + " per chip (the host audit has no limit)");
+        if (machine_.airs[i].width > 4096)
+            throw std::invalid_argument("pair_audit: chip " + machine_.airs[i].name + " has more than 4096 columns; the device audit handles up to 4096 (the host audit up to 65535)");
+    }
+    const uint32_t D = o.n_deltas, DD = D * D, R = o.max_rows_per_entry;
+
+    DeviceCtx& c = *ctx_;
+    c.activate();
+    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
+    c.activate();
+    struct Running {
+        std::atomic<int>& n;
+        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
+        ~Running() { n.fetch_sub(1); }
+    } running(c.proofs_running);
+    hipStream_t st = c.stream;
+
+    PairReport rep;
+    rep.chips.resize(NC);
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
+    VG_HIP_CHECK(hipEventCreate(&ev0));
+    VG_HIP_CHECK(hipEventCreate(&ev1));
+    uint64_t scratch_words = 0, rows_words = 0, desc_words_n = 0;
+    try {
+        std::vector<DMat> own;
+        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
+            if (!t->nat.empty()) return t->nat.view();
+            own.emplace_back(&c, t->height, t->width);
+            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
+            return own.back().view();
+        };
+        own.reserve(NC + preprocessed.size());
+        // per chip: the launch shape, its descriptor words (column flags and bus masks, the coupled pairs, the pairs' bus masks) and its slice
+        // of the scratch (u32 words): totals, table [E NB], prefix [E NB]
+        std::vector<vk::PaArgs> args(NC);
+        std::vector<std::vector<uint32_t>> pairs(NC);
+        std::vector<uint64_t> tot_at(NC, 0), tab_at(NC, 0), pre_at(NC, 0), flag_at(NC, 0), pair_at(NC, 0), mask_at(NC, 0);
+        std::vector<uint32_t> desc_words;
+        uint64_t zeroed = 0;
+        for (size_t i = 0; i < NC; i++) {
+            const AirDesc& air = machine_.airs[i];
+            vk::PaArgs& v = args[i];
+            v = vk::PaArgs{};
+            vk::MaArgs& a = v.m;
+            a.K = air.program.num_asserts;
+            PairChipStat& cs = rep.chips[i];
+            cs.width = air.width; cs.n_constraints = a.K; cs.n_interactions = (uint32_t)air.interactions.size(); cs.height = main[i]->height;
+            cs.audited = pair_audit_selected(o, i) ? 1u : 0u;
+            if (!cs.audited || !air.width) continue;
+            const vk::DMatView mv = working(main[i]);
+            a.main = mv.data; a.mstride = mv.stride; a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
+            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
+            a.prog = (const vair::Instr*)prog_dev_[i].data;
+            a.n_instrs = (uint32_t)air.program.instrs.size();
+            a.n_regs = air.program.num_regs;
+            a.iw = iw_dev_[i].data;
+            a.D = D;
+            for (uint32_t k = 0; k < D; k++) a.delta[k] = Fp::from_canonical(o.deltas[k]).v;
+            a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
+            pairs[i] = pa_coupled_pairs(air, a.n);
+            v.P = (uint32_t)pairs[i].size();
+            vk::pa_shape(v);
+            a.evaluations = pa_device_evaluations(air, a.n, D, pairs[i], v.PPS, a.CY);
+            rep.evaluations += a.evaluations;
+            const std::vector<uint32_t> fl = ma_column_flags(air);
+            bool masks_ok = false;
+            const std::vector<uint32_t> bm = ma_bus_masks(air, masks_ok);
+            const std::vector<uint32_t> pmk = pa_bus_masks(air, pairs[i], o.deltas, D, masks_ok);
+            a.bus_walk = masks_ok ? 0u : 1u;
+            flag_at[i] = desc_words.size();
+            desc_words.insert(desc_words.end(), fl.begin(), fl.end());
+            desc_words.insert(desc_words.end(), bm.begin(), bm.end());
+            pair_at[i] = desc_words.size();
+            desc_words.insert(desc_words.end(), pairs[i].begin(), pairs[i].end());
+            desc_words.push_back(0);
+            mask_at[i] = desc_words.size();
+            desc_words.insert(desc_words.end(), pmk.begin(), pmk.end());
+            const uint64_t E = (uint64_t)v.P * DD;
+            tot_at[i] = zeroed; zeroed += vk::pa_totals_words(v);
+            tab_at[i] = zeroed; zeroed += (E * a.NB + 1) & ~1ull;  // the next chip's u64 totals stay 8-byte aligned
+        }
+        scratch_words = zeroed;
+        for (size_t i = 0; i < NC; i++) if (args[i].m.width) { pre_at[i] = scratch_words; scratch_words += (uint64_t)args[i].P * DD * args[i].m.NB; }
+        if (desc_words.empty()) desc_words.push_back(0);
+        desc_words_n = desc_words.size();
+        DBuf desc(&c, desc_words);
+        for (size_t i = 0; i < NC; i++) { args[i].m.flags = desc.data + flag_at[i]; args[i].pairs = desc.data + pair_at[i]; args[i].pmasks = desc.data + mask_at[i]; }
+        c.check_launch("pair_audit ingest");
+        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
+        // the device pass: everything from here to the last download is between the two events
+        VG_HIP_CHECK(hipEventRecord(ev0, st));
+        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)zeroed * 4, st));
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].m.width) vk::launch_pa_count(st, args[i], reinterpret_cast<unsigned long long*>(scratch.data + tot_at[i]), scratch.data + tab_at[i]);
+        c.check_launch("pair_audit count");
+        std::vector<std::vector<uint64_t>> counts(NC), ufree(NC);
+        {
+            std::vector<uint32_t> tw;
+            for (size_t i = 0; i < NC; i++) {
+                const size_t E = (size_t)args[i].P * DD;
+                counts[i].assign(2 * E, 0);
+                ufree[i].assign(DD, 0);
+                if (!args[i].m.width) continue;
+                tw.resize(vk::pa_totals_words(args[i]));
+                c.download_small(tw.data(), scratch.data + tot_at[i], tw.size() * 4);
+                auto u64 = [&](size_t k) { return ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k]; };
+                for (size_t k = 0; k < 2 * E; k++) counts[i][k] = u64(k);
+                for (uint32_t q = 0; q < DD; q++) ufree[i][q] = u64(2 * E + q) - u64(2 * E + 16 + q);  // all pairs - coupled pairs: both singles free
+            }
+        }
+        pair_audit_finish(rep, pairs, counts, ufree, o);
+        // entry index of a listed entry within its chip: its pair's position in the coupled list
+        auto entry_index = [&](const PairEntry& en) {
+            const auto& pl = pairs[en.chip];
+            size_t lo = 0, hi = pl.size();
+            while (lo < hi) {  // ascending (c1, c2)
+                const size_t mid = (lo + hi) / 2;
+                const uint32_t m1 = pl[mid] & 0xffffu, m2 = pl[mid] >> 16;
+                if (m1 < en.c1 || (m1 == en.c1 && m2 < en.c2)) lo = mid + 1; else hi = mid;
+            }
+            return (uint64_t)lo * DD + en.q;
+        };
+        for (size_t e0 = 0; e0 < rep.entries.size();) {
+            const uint32_t chip = rep.entries[e0].chip;
+            size_t e1 = e0;
+            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
+            const uint64_t cut = entry_index(rep.entries[e1 - 1]) + 1;
+            rows_words = std::max<uint64_t>(rows_words, cut * R);
+            e0 = e1;
+        }
+        DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
+        for (size_t e0 = 0; e0 < rep.entries.size();) {
+            // the listed entries of one chip: scan, list, one download
+            const uint32_t chip = rep.entries[e0].chip;
+            size_t e1 = e0;
+            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
+            const vk::PaArgs& v = args[chip];
+            const uint32_t e_cut = (uint32_t)(entry_index(rep.entries[e1 - 1]) + 1);  // entries ascend: the listed ones of a chip are below it
+            vk::launch_pa_scan(st, v, reinterpret_cast<const unsigned long long*>(scratch.data + tot_at[chip]), scratch.data + tab_at[chip], scratch.data + pre_at[chip], e_cut);
+            vk::launch_pa_list(st, v, scratch.data + tab_at[chip], scratch.data + pre_at[chip], e_cut, R, out.data);
+            c.check_launch("pair_audit list");
+            std::vector<uint32_t> w((size_t)e_cut * R);
+            c.download_small(w.data(), out.data, w.size() * 4);
+            for (size_t e = e0; e < e1; e++) {
+                PairEntry& en = rep.entries[e];
+                const uint64_t listed = std::min<uint64_t>(en.compensated, R);
+                const size_t at = (size_t)entry_index(en) * R;
+                en.rows.assign(w.begin() + at, w.begin() + at + listed);
+            }
+            e0 = e1;
+        }
+        VG_HIP_CHECK(hipEventRecord(ev1, st));
+        c.sync();
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
+    } catch (const BusAuditNoMemory&) {
+        throw;
+    } catch (const std::bad_alloc&) {
+        (void)hipStreamSynchronize(st);
+        throw BusAuditNoMemory("pair_audit: the device pool cannot give the pass its scratch: 16 bytes per (coupled pair, delta pair) and 8 per (coupled pair, delta pair, workgroup of rows) of every chip (" +
+                               std::to_string(scratch_words * 4) + " bytes for this witness), " + std::to_string(desc_words_n * 4) + " bytes of pair lists and bus masks, " + std::to_string(rows_words * 4) +
+                               " bytes of listed rows, plus the working-layout copies of uploaded traces; chip_mask audits fewer chips at a time");
+    }
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 // ---- coverage audit (host/coverage_audit.hpp; kernels/coverage_audit.hip) ------------------------------------------------------------------
 CoverageReport Prover::coverage_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
                                       const CoverageAuditOpts& opts_in) {

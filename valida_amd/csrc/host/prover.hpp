@@ -11,6 +11,7 @@
 #include "machine.hpp"
 #include "mutation_audit.hpp"
 #include "coverage_audit.hpp"
+#include "pair_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -126,6 +127,11 @@ class Prover {
     // per cell (detector, column, delta) and workgroup along its rows, 24 per cell, 16 per (detector, delta), 32 per listed cell.
     CoverageReport coverage_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
                                   const CoverageAuditOpts& opts);
+
+    // Pair audit of a witness (host/pair_audit.hpp, kernels/pair_audit.hip): two-cell slack in a row that single mutations miss; the same trace
+    // handles, queued on the context like a proof.  Scratch from the pool: per chip 16 bytes per entry (coupled pair, delta pair) + 256, 8 per
+    // (entry, workgroup of rows), 8 per entry of bus masks, 4 x max_rows_per_entry per listed entry slot of the chip with the most.
+    PairReport pair_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const PairAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

@@ -217,6 +217,26 @@ void launch_ma_count(hipStream_t st, const MaArgs& a, unsigned long long* totals
 // entries below e_cut with a free row are listed
 void launch_ma_scan(hipStream_t st, const MaArgs& a, const unsigned long long* totals, const uint32_t* table, uint32_t* prefix, uint32_t e_cut);
 void launch_ma_list(hipStream_t st, const MaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t e_cut, uint32_t R, uint32_t* rows);
+// pair_audit.hip — the passes of the pair audit (host/pair_audit.hpp: contract; Prover::pair_audit drives them), per chip.  The launch shape and
+// the single mutations are the mutation audit's (MaArgs; m.CY = pair slices = gridDim.y).  An ENTRY of a chip is e = p * D * D + q for coupled
+// pair p (ascending (c1, c2)) and delta pair q = i * D + j; E = P * D * D.  totals: [E][2] u64 {free, compensated}, then [16] u64 per q the sum
+// over ALL pairs c1 < c2 of the rows where both single mutations are free, then [16] u64 the same sum over the coupled pairs (their difference
+// is the uncoupled pairs' exact `free`) (all zeroed); table / prefix: [E][NB] u32 compensated rows per workgroup and their exclusive prefix
+// (table zeroed); rows: [E][R] u32.
+constexpr uint32_t PA_SLICE_ENTRIES = 1024;  // entries a workgroup accumulates in LDS: 8 KB of counters, 36 KB of row bits at 256 rows
+struct PaArgs {
+    MaArgs m;
+    const uint32_t* pairs;   // [P] c1 | c2 << 16 (pa_coupled_pairs)
+    const uint32_t* pmasks;  // [E][2] the bus masks of the entry (pa_bus_masks): interactions whose count / some field changes
+    uint32_t P, PPS;         // coupled pairs; pairs per slice (pa_shape): slice y walks pairs [y PPS, y PPS + PPS)
+};
+inline uint64_t pa_totals_words(const PaArgs& v) { return 2 * (2ull * v.P * v.m.D * v.m.D + 32); }  // u32 words of the u64 totals
+// Rows per workgroup, workgroups, pairs per slice and slices of a chip's launch; throws std::invalid_argument when no tile of the chip fits the LDS
+void pa_shape(PaArgs& v);
+void launch_pa_count(hipStream_t st, const PaArgs& v, unsigned long long* totals, uint32_t* table);
+// entries below e_cut with a compensated row are listed
+void launch_pa_scan(hipStream_t st, const PaArgs& v, const unsigned long long* totals, const uint32_t* table, uint32_t* prefix, uint32_t e_cut);
+void launch_pa_list(hipStream_t st, const PaArgs& v, const uint32_t* table, const uint32_t* prefix, uint32_t e_cut, uint32_t R, uint32_t* rows);
 // coverage_audit.hip — the passes of the coverage audit (host/coverage_audit.hpp: contract; Prover::coverage_audit drives them), per chip.  The
 // evaluations are the mutation audit's (MaArgs; mutation_eval.hpp).  A CELL of a chip is ((detector * width + column) * D + delta index),
 // cells = (K + M) * width * D of them.  audit: wg_tables [GX][cells][4] u32 {kills, sole, ~first_row, ~first_sole_row} (zeroed), one table per
