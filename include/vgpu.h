@@ -138,6 +138,14 @@ void vgpu_prover_memory(const vgpu_prover_t* p, uint64_t* live_bytes, uint64_t* 
 uint64_t vgpu_prover_trim(vgpu_prover_t* p);
 /* The pool's peak restarts from what is held now (a host that wants the high-water mark of ONE phase: bench.py reports the proving path's own). */
 void vgpu_prover_memory_reset_peak(vgpu_prover_t* p);
+/* The device's dense lane: the contexts of one device take turns in the big Merkle-tree launches of vgpu_prove / vgpu_prove_async (a thread per
+ * node; they fill the chip's VALU issue slots on their own), so that one proof's tree phase runs beside the others' LDE, quotient and opening
+ * phases instead of beside their tree phases.  Scheduling only: no proof word depends on it.  On by default for trees of at least 2^18 leaf
+ * rows; `on` = 0 switches it off for this context, `min_nodes` > 0 sets the smallest tree that takes it (0 keeps the current value).  Takes
+ * effect with the next proof.  (The Python binding calls this at context creation from VGPU_DENSE_LANE and VGPU_DENSE_LANE_MIN_NODES.) */
+void vgpu_prover_set_dense_lane(vgpu_prover_t* p, uint32_t on, uint64_t min_nodes);
+/* how many trees of this context entered the lane, and how many of those had to wait for ANOTHER context's event; both stay 0 with the lane off */
+void vgpu_prover_lane_stats(const vgpu_prover_t* p, uint64_t* entered, uint64_t* waited);
 
 /* per-kernel HIP-event timing (bench): switch on/off (resets the accumulators); the profile is text,
  * one line per kernel: "name launches total_ms total_algorithmic_bytes".  Returns the size needed. */

@@ -1546,7 +1546,18 @@ class Prover:
         ctypes.memmove(cfg.poseidon_rc, rc.ctypes.data, 480 * 4)
         self.machine, self.rc, self.log_blowup, self.num_queries, self.pow_bits = machine, rc, log_blowup, num_queries, pow_bits
         self._h = ctypes.c_void_p()
+        # the dense lane's switch, read once, here: VGPU_DENSE_LANE=0 turns it off for this context (A/B runs, parity tests),
+        # VGPU_DENSE_LANE_MIN_NODES sets the smallest tree that takes it (the tests' small trees); parsed before the context exists
+        lane_off, lane_min = os.environ.get("VGPU_DENSE_LANE", "1") == "0", os.environ.get("VGPU_DENSE_LANE_MIN_NODES", "").strip()
+        if lane_min and not lane_min.isdigit():
+            raise ValueError("VGPU_DENSE_LANE_MIN_NODES must be a number of leaf rows, not %r" % lane_min)
         _check(lib().vgpu_prover_create(ctypes.byref(cfg), machine._h, ctypes.byref(self._h)))
+        if lane_off or int(lane_min or 0) > 0:
+            self.set_dense_lane(not lane_off, int(lane_min or 0))
+
+    def set_dense_lane(self, on, min_nodes=0):
+        """vgpu_prover_set_dense_lane: the device's dense lane on / off for this context; min_nodes > 0 = the smallest tree that takes it."""
+        lib().vgpu_prover_set_dense_lane(self._h, ctypes.c_uint32(1 if on else 0), ctypes.c_uint64(int(min_nodes)))
 
     def upload(self, matrix):
         m = np.ascontiguousarray(matrix, dtype=np.uint32)
@@ -1765,6 +1776,12 @@ class Prover:
         live, peak = ctypes.c_uint64(), ctypes.c_uint64()
         lib().vgpu_prover_memory(self._h, ctypes.byref(live), ctypes.byref(peak))
         return live.value, peak.value
+
+    def lane_stats(self):
+        """(trees of this context that entered the device's dense lane, those that waited for another context's event)."""
+        entered, waited = ctypes.c_uint64(), ctypes.c_uint64()
+        lib().vgpu_prover_lane_stats(self._h, ctypes.byref(entered), ctypes.byref(waited))
+        return int(entered.value), int(waited.value)
 
     def __del__(self):
         if getattr(self, "_h", None):

@@ -308,6 +308,19 @@ void vgpu_prover_memory(const vgpu_prover_t* p, uint64_t* live, uint64_t* peak) 
     if (live) *live = c.live;
     if (peak) *peak = c.peak_live;
 }
+void vgpu_prover_set_dense_lane(vgpu_prover_t* p, uint32_t on, uint64_t min_nodes) {
+    if (!p) return;
+    DeviceCtx& c = p->p->ctx();
+    std::lock_guard<std::mutex> lk(c.prove_mu);  // between proofs: a running proof keeps the setting it started with
+    c.lane_on = on != 0;
+    if (min_nodes) c.lane_min_nodes = min_nodes;
+}
+void vgpu_prover_lane_stats(const vgpu_prover_t* p, uint64_t* entered, uint64_t* waited) {
+    if (!p) return;
+    auto& c = const_cast<vgpu_prover_t*>(p)->p->ctx();
+    if (entered) *entered = c.lane_entered.load();
+    if (waited) *waited = c.lane_waited.load();
+}
 void vgpu_prover_memory_reset_peak(vgpu_prover_t* p) {
     if (!p) return;
     DeviceCtx& c = p->p->ctx();

@@ -113,6 +113,18 @@ struct DeviceTree {
         const bool pos = c->hash_kind == 1;
         const uint32_t* tab = c->poseidon_tab;
         bool leaves_in_top = false, leaves_in_mid = false;
+        // The dense lane (dense_lane.hpp): a big tree of a proof on the main stream enters it in front of its first thread-per-node launch and leaves it
+        // behind the last one — the mid / top launches below are latency-bound and overlap freely.  A tree whose leaves go into the mid or top launch has no
+        // dense launch; one on the auxiliary stream (the preprocessed rider) never takes the lane.  The lane's mutex is held until leave(): across the dense
+        // launch calls AND the pool allocations of their layers below (a map look-up in the steady state; a pool miss that reaches hipMalloc — a context's first
+        // proof of a shape — or a launch that blocks on a full queue holds up the other contexts' host threads at their enter() for that long, never the GPU).
+        HipDenseLane::Guard lane_guard;
+        const bool fused_leaves = !pos && single && (vk::keccak_top_takes_leaves(maxh) || (maxh / 2 > TOP_FIRST_LEN && vk::keccak_levels_take_leaves(maxh)));
+        if (c->lane_open_here() && st == c->stream && maxh >= c->lane_min_nodes && !fused_leaves) {
+            lane_guard = c->lane->enter(c->lane_slot, st);
+            c->lane_entered.fetch_add(1);
+            if (lane_guard.waited()) c->lane_waited.fetch_add(1);
+        }
         if (pos) {
             if (single) vk::launch_poseidon_leaves_strided(st, tab, c->poseidon_sparse, single_view->data, single_view->stride, (int)single_view->width, maxh, layers[0].data);
             else vk::launch_poseidon_leaves(st, tab, c->poseidon_sparse, pd + groups[0].first, (int)groups[0].count, maxh, layers[0].data);
@@ -151,7 +163,9 @@ struct DeviceTree {
             layers.emplace_back(c, (size_t)len * 8);
             layer_len.push_back(len);
             const Group* inj = (gi < groups.size() && groups[gi].height == len) ? &groups[gi] : nullptr;
+            // (with the dense lane held this runs under the device-wide lane mutex: a callback passed here must only enqueue, never join or synchronise on the host)
             if (inj && before_injection_) { (*before_injection_)(); before_injection_ = nullptr; }
+            if (pos ? vk::poseidon_levels_take(len) : (len <= TOP_FIRST_LEN || vk::keccak_levels_fused(len))) lane_guard.leave();  // the first layer that is no thread-per-node launch
             // Layers of more than TOP_FIRST_LEN parents are spread over the whole GPU (the big ones a launch each); the rest of the tree is one
             // single-workgroup launch.  256, not the 1024 a workgroup could take: inside one workgroup a 1024-parent layer puts four
             // waves on each SIMD of ONE CU and costs 27 us (512 parents: 15 us), as a launch of its own across the CUs 9 + 2 us.
@@ -173,6 +187,7 @@ struct DeviceTree {
             if (inj) gi++;
             if (len == 1) break;
         }
+        lane_guard.leave();
         flush_mid();
         if (leaves_in_mid && layers.size() < 2) throw std::logic_error("mmcs: leaf prologue on a tree without parents");
         if (leaves_in_top) {

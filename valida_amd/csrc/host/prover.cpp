@@ -319,6 +319,8 @@ std::vector<uint32_t> Prover::prove(const std::vector<const DeviceTrace*>& main,
         explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
         ~Running() { n.fetch_sub(1); }
     } running(c.proofs_running);
+    // the big trees of THIS call (the commitment rounds, the first FRI layers) go through the device's dense lane; nothing else built on this context does
+    struct LaneOpen { explicit LaneOpen(const DeviceCtx* x) { DeviceCtx::lane_thread_ctx() = x; } ~LaneOpen() { DeviceCtx::lane_thread_ctx() = nullptr; } } lane_open(&c);
     const size_t NC = machine_.airs.size();
     if (main.size() != NC) throw std::invalid_argument("prove: need one main trace per chip");
     const Fp s = Fp::from_canonical(vg::GENERATOR);  // pcs.coset_shift()

@@ -15,10 +15,31 @@
 #include <tuple>
 #include <vector>
 #include "../kernels/launch.hpp"
+#include "dense_lane.hpp"
 
 namespace vhost {
 using vg::Ext5;
 using vg::Fp;
+
+// The dense lane over HIP events (dense_lane.hpp): one lane per device, found through a registry that lives as long as the process.
+struct HipLaneApi {
+    using Event = hipEvent_t;
+    using Stream = hipStream_t;
+    static Event create() { hipEvent_t e = nullptr; VG_HIP_CHECK(hipEventCreateWithFlags(&e, hipEventDisableTiming)); return e; }
+    static void destroy(Event e) noexcept { if (e) (void)hipEventDestroy(e); }
+    static bool record(Event e, Stream s) noexcept { return hipEventRecord(e, s) == hipSuccess; }
+    static void wait(Stream s, Event e) { VG_HIP_CHECK(hipStreamWaitEvent(s, e, 0)); }
+};
+using HipDenseLane = DenseLane<HipLaneApi>;
+inline HipDenseLane& dense_lane_of(int device) {
+    // never destroyed: a tail event released by a static destructor would call into a HIP runtime that may already be gone
+    static std::mutex* mu = new std::mutex;
+    static std::map<int, HipDenseLane*>* lanes = new std::map<int, HipDenseLane*>;
+    std::lock_guard<std::mutex> lk(*mu);
+    HipDenseLane*& l = (*lanes)[device];
+    if (!l) l = new HipDenseLane;
+    return *l;
+}
 
 struct DeviceCtx {
     int device = 0;
@@ -56,6 +77,16 @@ struct DeviceCtx {
     hipEvent_t rider_ev = nullptr;
     uint32_t* rider_root_pin = nullptr;
     bool in_section = false;
+    // The device's dense lane (dense_lane.hpp).  Only trees of at least lane_min_nodes leaf rows built on the main stream by a thread inside
+    // Prover::prove take it (lane_open_here), so the sharded provers, the audits and the stand-alone commits never touch the lane.
+    // lane_on / lane_min_nodes: vgpu_prover_set_dense_lane, set between proofs (the switch of the A/B and of the parity tests).
+    HipDenseLane* lane = nullptr;
+    HipDenseLane::SlotPtr lane_slot;
+    bool lane_on = true;
+    uint64_t lane_min_nodes = 1ull << 18;
+    std::atomic<uint64_t> lane_entered{0}, lane_waited{0};  // vgpu_prover_lane_stats
+    static const DeviceCtx*& lane_thread_ctx() { static thread_local const DeviceCtx* c = nullptr; return c; }
+    bool lane_open_here() const { return lane_on && lane && lane_thread_ctx() == this; }
     std::vector<void*> deferred;  // blocks released inside a section return to the pool at the join
     // The pool is shared by the thread that drives a proof (vgpu_prove_async's worker) and by whichever host thread frees a
     // handle meanwhile (vgpu_trace_free / vgpu_oplog_free / a garbage collector): every pool operation takes this lock.
@@ -81,6 +112,8 @@ struct DeviceCtx {
         VG_HIP_CHECK(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
         VG_HIP_CHECK(hipEventCreateWithFlags(&rider_ev, hipEventDisableTiming));
         VG_HIP_CHECK(hipHostMalloc((void**)&rider_root_pin, 64));
+        lane = &dense_lane_of(dev);
+        lane_slot = std::make_shared<HipDenseLane::Slot>();
         init_tables();
     }
     // Every C-ABI entry that launches work calls this first: binds the calling thread to this context's
@@ -93,6 +126,7 @@ struct DeviceCtx {
         if (vk::g_profiler == &profiler) vk::g_profiler = nullptr;
         (void)hipSetDevice(device);
         (void)hipStreamSynchronize(stream);
+        if (lane) lane->retire(lane_slot);  // the stream has drained: nothing of this context is left to wait for
         for (int i = 0; i < NUM_AUX; i++) { (void)hipStreamSynchronize(aux[i]); (void)hipStreamDestroy(aux[i]); (void)hipEventDestroy(join_ev[i]); }
         (void)hipEventDestroy(fork_ev);
         if (rider_ev) (void)hipEventDestroy(rider_ev);
