@@ -524,6 +524,79 @@ const uint32_t* vgpu_pair_report_words(const vgpu_pair_report_t* r);
 void vgpu_pair_report_timing(const vgpu_pair_report_t* r, double out[3]);
 void vgpu_pair_report_free(vgpu_pair_report_t* r);
 
+/* ---- Rank audit: every first-order degree of freedom of one trace row.  At row r of chip h, which directions in the space of the row's w main
+ * cells leave every constraint and every bus record unchanged to first order?  That is the null space of the Jacobian of everything that reads
+ * the row: its dimension counts the degrees of freedom, its zero columns are the cells free on their own, the rest is every compensated
+ * combination of any arity and with any coefficients (pairs, triples, a + 256 b limb trades) — what a sweep over +-1 deltas never tries.  All bus
+ * records are affine, and so are most constraints, so for them the answer is exact.  Inputs: exactly what vgpu_prove and the audits take.
+ *   Jacobian       chip h with main matrix M (height n, width w) and a row r: J_r has w columns, one per main cell M[r][c] (preprocessed columns
+ *                  are never varied).  Its rows: for every constraint k the partial derivatives dC_k / dM[r][c] of Air::eval at evaluation q = r,
+ *                  where the cell is read as `local`, and the same at q = (r - 1) mod n, where it is read as `next`, on the constraint audit's
+ *                  domain (next = (q + 1) mod n; is_first_row = [q = 0], is_last_row = [q = n - 1], is_transition = [q != n - 1] as 0 / 1).  For
+ *                  n = 1 there is one evaluation, the cell local and next at once, the derivative the sum over both roles.  Derivatives are
+ *                  taken at the witness as it is, whether or not the constraint holds there.  Permutation constraints are not evaluated; the
+ *                  bus rows are their exact statement: for every interaction m (Chip::all_interactions order) one row holds the main-column
+ *                  weights of its count and, when that count is non-zero at row r on M, one further row per field holds that field's
+ *                  main-column weights.  A direction v in F_p^w is TANGENT-FREE iff J_r v = 0; for the bus part that is exact: the record of m
+ *                  is unchanged along M[r] + t v for every t iff v is orthogonal to those rows.
+ *   per row        from the reduced row echelon form R of J_r (unique, so no elimination order can change a word): rank rho, nullity
+ *                  nu = w - rho, z = the zero columns of J_r.  The row is COUPLED when nu > z (a compensated direction that is not made of
+ *                  single free cells).  Column c is PINNED iff e_c lies in the row space (c is a pivot column whose row of R has no other
+ *                  non-zero entry), otherwise LOOSE (some tangent-free direction moves it); ZERO when column c of J_r is zero (a zero column is
+ *                  loose); COUPLED at r when loose and not zero — the finding: the cell is bound alone and slack together.
+ *   null vector    the canonical null vector of a loose column c: if c is a non-pivot column, the basis vector of c (v_c = 1, v_p = -R[row of
+ *                  p][c] for every pivot column p, 0 on the other non-pivot columns); if c is a pivot column with row i, the basis vector of the
+ *                  smallest non-pivot column f with R[i][f] != 0.
+ *   order          an entry is a (chip, column) with a coupled row; entries ascend, each with its first max_rows_per_entry coupled rows in
+ *                  ascending order.  Only the first max_entries entries are listed; the totals stay exact and `truncated` says the list was
+ *                  cut.  No challenge, no hash and no floating point enter: the same words run after run, from device and host, for
+ *                  Machine.basic and for captured AIRs.
+ * What it is not: it is FIRST ORDER — for a constraint of degree >= 2 in the row's cells a tangent-free direction is necessary for a CURVE of
+ * unnoticed changes and says nothing about a finite jump: b (b - 1) = 0 pins b here although b -> 1 - b passes it; x^2 = 0 at x = 0 reports x as
+ * zero / loose although it is bound.  Finite flips stay the subject of the mutation and pair audits.  It covers the cells of one row only;
+ * cross-row combinations are not looked for.  It is a statement about THIS witness, not a soundness proof; `check`'s exit status never depends on it.
+ * Options: a zero field selects its default — max_entries 1024 (at most 2^24), max_rows_per_entry 4 (at most 4096); chip_mask bit h = audit chip
+ * h, 0 = all chips (a bit beyond the machine's chips is refused); unselected chips keep their block with audited = 0 and zero counts; opts may be
+ * NULL; reserved != 0 is refused.
+ * vgpu_rank_audit runs on the device (kernels/rank_audit.hip: one wave per trace row, one lane per column, the elimination in LDS), queued on the
+ * prover context like a proof or the other audits; it accepts device-generated and uploaded traces.  Scratch comes from the prover's pool: per
+ * chip 32 + 16 w bytes of totals, 8 w bytes per workgroup of T rows (table and prefix; T = 1 to 64 rows), the interaction weight rows (4 w bytes
+ * per count and field), 72 max_rows_per_entry bytes per column up to the last listed one of the chip with the most, plus the working-layout copy
+ * of every uploaded trace; VGPU_ERR_OOM with the arithmetic in the message when the pool cannot give them (chip_mask audits fewer chips at a
+ * time).  VGPU_ERR_INVALID_ARG for bad shapes, for a chip of more than 192 columns, and for a chip that does not fit 160 KB of LDS with one wave
+ * per workgroup: 4 x (w (w | 1) [basis] + K w [the K constraints' raw Jacobian rows of one evaluation] + 128 registers [captured AIR under the
+ * interpreting prover: (value, derivative) x 64 lanes per program register] + 10 w + 12 + 3 (w + preprocessed w) [tile of one row, halo, flags])
+ * bytes <= 163840.  There is no fixed limit on the number of constraints: no fail mask is kept, K enters through that sum alone.
+ * vgpu_rank_audit_host is the same contract on the host over canonical row-major matrices (a dual-number evaluation of the chip's Program, RREF
+ * by row insertion; one thread, no device, no limits).  Both validate shapes as vgpu_prove does.
+ * Report image (vgpu_rank_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x31525256 "VRR1" [1] word count [2] terms per listed row, always 8 [3] truncated [4,5] total_entries = (chip, column) with a coupled row
+ *   (exact even when the list is cut) [6] reported [7] n_chips
+ *   per chip, in machine order, 16 + 4 w words: width, constraints, interactions, audited (0 / 1), height (u64), sum over rows of nu (u64), sum
+ *   over rows of z (u64), coupled rows (u64), max nullity, columns loose on some row, columns pinned on every row, columns coupled on some row,
+ *   then per column c: loose rows (u64), zero rows (u64)
+ *   per reported entry: chip, column, n_listed, 0, coupled rows (u64), then n_listed rows of 18 words: row, n_support (exact), then the first 8
+ *   (column, coefficient) terms of the canonical null vector in ascending column order, unused slots 0. */
+typedef struct vgpu_rank_audit_opts {
+    uint64_t max_entries;
+    uint32_t max_rows_per_entry;
+    uint32_t chip_mask;
+    uint32_t reserved[2];
+} vgpu_rank_audit_opts_t;
+typedef struct vgpu_rank_report vgpu_rank_report_t;
+int32_t vgpu_rank_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                        uint32_t n_prep, const vgpu_rank_audit_opts_t* opts, vgpu_rank_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_rank_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                             const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                             const vgpu_rank_audit_opts_t* opts, vgpu_rank_report_t** out);
+uint64_t vgpu_rank_report_len(const vgpu_rank_report_t* r);
+const uint32_t* vgpu_rank_report_words(const vgpu_rank_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: the dual row evaluations of the
+ * contract, 2 w per row of a chip with constraints (w for n = 1); the device pass ends a row early once its rank is w */
+void vgpu_rank_report_timing(const vgpu_rank_report_t* r, double out[3]);
+void vgpu_rank_report_free(vgpu_rank_report_t* r);
+
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
  *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct

@@ -1321,6 +1321,120 @@ def pair_audit_host(machine, main_matrices, preprocessed, deltas=None, max_entri
     return _pair_report(h)
 
 
+class RankAuditOpts(ctypes.Structure):  # vgpu_rank_audit_opts_t
+    _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
+
+
+class RankReport:
+    """The rank audit of a witness (vgpu_rank_audit / vgpu_rank_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
+    truncated, total_entries ((chip, column) with a coupled row), reported,
+    chips = [dict(chip, width, constraints, interactions, audited, height, nullity, zero, coupled_rows (sums over the rows), max_nullity,
+    loose_columns, pinned_columns, coupled_columns (counts), loose=[rows per column], zeros=[rows per column])],
+    entries = [dict(chip, column, coupled, rows=[dict(row, n_support, terms=[(column, coefficient)])])] ascending by (chip, column),
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (dual row evaluations of the contract).
+    First order, one row, THIS witness: not a soundness proof."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 8 or w[0] != 0x31525256 or w[1] != len(w) or w[2] != 8:
+            raise ValueError("not a rank report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.truncated = bool(w[3])
+        self.total_entries, self.reported = w[4] | (w[5] << 32), w[6]
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 8
+        self.chips = []
+        for c in range(w[7]):
+            wd = w[pos]
+            self.chips.append(dict(chip=c, width=wd, constraints=w[pos + 1], interactions=w[pos + 2], audited=bool(w[pos + 3]), height=u64(pos + 4), nullity=u64(pos + 6),
+                                   zero=u64(pos + 8), coupled_rows=u64(pos + 10), max_nullity=w[pos + 12], loose_columns=w[pos + 13], pinned_columns=w[pos + 14],
+                                   coupled_columns=w[pos + 15], loose=[u64(pos + 16 + 4 * k) for k in range(wd)], zeros=[u64(pos + 18 + 4 * k) for k in range(wd)]))
+            pos += 16 + 4 * wd
+        self.entries = []
+        for _ in range(self.reported):
+            rows = []
+            for k in range(w[pos + 2]):
+                at = pos + 6 + 18 * k
+                rows.append(dict(row=w[at], n_support=w[at + 1], terms=[(w[at + 2 + 2 * i], w[at + 3 + 2 * i]) for i in range(min(8, w[at + 1]))]))
+            self.entries.append(dict(chip=w[pos], column=w[pos + 1], coupled=u64(pos + 4), rows=rows))
+            pos += 6 + 18 * w[pos + 2]
+        assert pos == len(w)
+
+    def loose_columns(self, chip):
+        """The columns of `chip` that are loose on some row (zero columns included)."""
+        return [k for k, n in enumerate(self.chips[chip]["loose"]) if n]
+
+    def coupled_columns(self, chip):
+        """The columns of `chip` that are coupled on some row: bound alone, slack together (exact, from the per-column counts)."""
+        c = self.chips[chip]
+        return [k for k in range(c["width"]) if c["loose"][k] > c["zeros"][k]]
+
+    def to_dict(self):
+        return dict(truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
+                    evaluations=self.evaluations, chips=self.chips, entries=self.entries)
+
+    def to_json(self):
+        import json
+
+        return json.dumps(self.to_dict())
+
+
+def _rank_opts(max_entries, max_rows_per_entry, chips):
+    # as _pair_opts: explicit zeros are refused here, with the library's status code
+    if int(max_entries) < 1 or int(max_rows_per_entry) < 1:
+        raise VgpuError(-1, "rank_audit: max_entries and max_rows_per_entry must be at least 1")
+    mask = 0
+    if chips is not None:
+        cs = [int(c) for c in chips]
+        if not cs or any(c < 0 or c > 31 for c in cs):
+            raise VgpuError(-1, "rank_audit: chips is a non-empty list of chip indices below 32")
+        for c in cs:
+            mask |= 1 << c
+    return RankAuditOpts(int(max_entries), int(max_rows_per_entry), mask, (ctypes.c_uint32 * 2)(0, 0))
+
+
+def _rank_report(h):
+    L = lib()
+    L.vgpu_rank_report_len.restype = ctypes.c_uint64
+    L.vgpu_rank_report_words.restype = c_u32p
+    L.vgpu_rank_report_len.argtypes = L.vgpu_rank_report_words.argtypes = L.vgpu_rank_report_free.argtypes = [ctypes.c_void_p]
+    L.vgpu_rank_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    try:
+        n = int(L.vgpu_rank_report_len(h))
+        words = np.ctypeslib.as_array(L.vgpu_rank_report_words(h), shape=(n,)).copy()
+        tm = (ctypes.c_double * 3)()
+        L.vgpu_rank_report_timing(h, tm)
+    finally:
+        L.vgpu_rank_report_free(h)
+    return RankReport(words, tm[0], tm[1], tm[2])
+
+
+def rank_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
+    """The rank audit on the HOST (vgpu_rank_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
+    [(chip index, matrix)], chips = the chip indices to audit (default: all); a RankReport back."""
+    opts = _rank_opts(max_entries, max_rows_per_entry, chips)
+    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
+    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
+    for m in mains + [m for _, m in preps]:
+        if m.ndim != 2:
+            raise VgpuError(-1, "rank_audit: traces are two-dimensional matrices")
+
+    def arrays(ms):
+        n = max(1, len(ms))
+        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
+
+    mp, mh, mw = arrays(mains)
+    pp, ph, pw = arrays([m for _, m in preps])
+    chip_ids = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
+    h = ctypes.c_void_p()
+    _check(lib().vgpu_rank_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chip_ids, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
+    return _rank_report(h)
+
+
 class CoverageAuditOpts(ctypes.Structure):  # vgpu_coverage_audit_opts_t
     _fields_ = [("max_cells", ctypes.c_uint64), ("n_deltas", ctypes.c_uint32), ("deltas", ctypes.c_uint32 * 4), ("max_workgroups", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32 * 2)]
@@ -1720,6 +1834,18 @@ class Prover:
         h = ctypes.c_void_p()
         _check(lib().vgpu_pair_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
         return _pair_report(h)
+
+    def rank_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
+        """Every first-order degree of freedom of each trace row of this witness (vgpu_rank_audit): per row the null space of the Jacobian of
+        all constraints and bus records that read the row; the arguments of prove, chips = the chip indices to audit (default: all); a
+        RankReport back."""
+        opts = _rank_opts(max_entries, max_rows_per_entry, chips)
+        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
+        chip_ids = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
+        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_rank_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
+        return _rank_report(h)
 
     def coverage_audit(self, main, preprocessed, deltas=None, max_cells=8192, max_workgroups=0):
         """Which constraint or interaction detects each mutation of the mutation audit (vgpu_coverage_audit): the arguments of prove, deltas as

@@ -28,6 +28,7 @@ SOURCES = [
     "kernels/mutation_audit.hip",
     "kernels/coverage_audit.hip",
     "kernels/pair_audit.hip",
+    "kernels/rank_audit.hip",
     "host/prover.cpp",
     "host/sharded_prover.cpp",
     "capi.cpp",

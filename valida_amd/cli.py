@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -46,6 +46,11 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         --chips=cpu,3 restricts it to those chips (names or indices).  The JSON report gets one more key, "pairs" (PairReport.to_json's object);
         after the other lines stdout gets one line per chip that has a slack pair, `add: 6 slack pairs of 136 coupled: (0,4) (0,8) ..`.  Same-row
         pairs on THIS witness only, not a soundness proof: the exit status does not depend on this flag.
+        --rank adds the rank audit of the same witness (vgpu_rank_audit: per trace row the null space of the Jacobian of every constraint and bus
+        record that reads the row — every first-order degree of freedom, of any arity and with any coefficients), on the same path (device or
+        --host), restricted by the same --chips.  The JSON report gets one more key, "rank" (RankReport.to_json's object); stdout gets one line
+        per chip that has a coupled column (bound alone, slack together), `add: 12 coupled columns: 0 1 2 ..; max nullity 8; 23 coupled rows`.
+        First order, one row, THIS witness, not a soundness proof: the exit status does not depend on this flag.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -213,6 +218,22 @@ def pair_lines(report, limit=12):
     return lines
 
 
+def rank_lines(report, limit=16):
+    """One line per chip of a rank report that has a coupled column: the columns, the largest nullity of a row, the coupled rows."""
+    import valida_amd as va
+
+    lines = []
+    for c in report.chips:
+        cols = report.coupled_columns(c["chip"])
+        if not cols:
+            continue
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        shown = " ".join(str(k) for k in cols[:limit]) + (" .." if len(cols) > limit else "")
+        lines.append("%s: %d coupled column%s: %s; max nullity %d; %d coupled row%s" % (name, len(cols), "" if len(cols) == 1 else "s", shown, c["max_nullity"], c["coupled_rows"],
+                                                                                  "" if c["coupled_rows"] == 1 else "s"))
+    return lines
+
+
 def coverage_lines(report):
     """One line per chip of a coverage report that has a dead or shadowed detector: the dead constraints / interactions by index, those that
     are never the only detector of a mutation, and how many detectors are essential."""
@@ -260,7 +281,9 @@ def main(argv=None):
                     "dead = not reached by this witness, not a fault; never changes the exit status)")
     ap.add_argument("--pairs", action="store_true", help="check: also the pair audit (two cells of one row that can change together unnoticed although one "
                     "alone is noticed; never changes the exit status)")
-    ap.add_argument("--chips", default="", help="check --pairs: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
+    ap.add_argument("--rank", action="store_true", help="check: also the rank audit (per row the null space of the Jacobian of all constraints and bus records: "
+                    "every first-order degree of freedom; never changes the exit status)")
+    ap.add_argument("--chips", default="", help="check --pairs / --rank: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -291,6 +314,7 @@ def main(argv=None):
                 mreport = va.mutation_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_entries=1 << 20) if args.mutations else None
                 kreport = va.coverage_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_cells=1 << 20) if args.coverage else None
                 preport = va.pair_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.pairs else None
+                rreport = va.rank_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.rank else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -301,6 +325,7 @@ def main(argv=None):
                 mreport = prover.mutation_audit(main, prep, deltas=parse_deltas(args.deltas), max_entries=1 << 20) if args.mutations else None
                 kreport = prover.coverage_audit(main, prep, deltas=parse_deltas(args.deltas), max_cells=1 << 20) if args.coverage else None
                 preport = prover.pair_audit(main, prep, deltas=parse_deltas(args.deltas), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.pairs else None
+                rreport = prover.rank_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips)) if args.rank else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -310,10 +335,13 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), coverage=kreport.to_dict()))
             if preport is not None:
                 text = json.dumps(dict(json.loads(text), pairs=preport.to_dict()))
+            if rreport is not None:
+                text = json.dumps(dict(json.loads(text), rank=rreport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
-                    coverage_lines(kreport) if kreport is not None else []) + (pair_lines(preport) if preport is not None else []):
+                    coverage_lines(kreport) if kreport is not None else []) + (pair_lines(preport) if preport is not None else []) + (
+                    rank_lines(rreport) if rreport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

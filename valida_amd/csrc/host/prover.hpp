@@ -12,6 +12,7 @@
 #include "mutation_audit.hpp"
 #include "coverage_audit.hpp"
 #include "pair_audit.hpp"
+#include "rank_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -132,6 +133,11 @@ class Prover {
     // handles, queued on the context like a proof.  Scratch from the pool: per chip 16 bytes per entry (coupled pair, delta pair) + 256, 8 per
     // (entry, workgroup of rows), 8 per entry of bus masks, 4 x max_rows_per_entry per listed entry slot of the chip with the most.
     PairReport pair_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const PairAuditOpts& opts);
+
+    // Rank audit of a witness (host/rank_audit.hpp, kernels/rank_audit.hip): per row the null space of the Jacobian of everything that reads the
+    // row; the same trace handles, queued on the context like a proof.  Scratch from the pool: per chip 32 + 16 bytes per column, 8 per (column,
+    // workgroup of rows), the interaction weight rows, 72 x max_rows_per_entry per listed column slot of the chip with the most.
+    RankReport rank_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const RankAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

@@ -237,6 +237,33 @@ void launch_pa_count(hipStream_t st, const PaArgs& v, unsigned long long* totals
 // entries below e_cut with a compensated row are listed
 void launch_pa_scan(hipStream_t st, const PaArgs& v, const unsigned long long* totals, const uint32_t* table, uint32_t* prefix, uint32_t e_cut);
 void launch_pa_list(hipStream_t st, const PaArgs& v, const uint32_t* table, const uint32_t* prefix, uint32_t e_cut, uint32_t R, uint32_t* rows);
+// rank_audit.hip — the passes of the rank audit (host/rank_audit.hpp: contract; Prover::rank_audit drives them), per chip.  One wave per trace
+// row, NW waves per workgroup, each wave RPW rows: T = NW * RPW rows per workgroup, NB workgroups.  totals: u64 [0] sum of nullities, [1] sum of
+// zero columns, [2] coupled rows, [3] max nullity, then per column [4 + 2 c] loose rows, [5 + 2 c] zero rows (all zeroed); table / prefix:
+// [width][NB] u32 coupled rows of the column per workgroup and their exclusive prefix (table zeroed); rows: [width][R][18] u32 (zeroed).
+struct RaArgs {
+    const uint32_t* main;  // column-major working layout (Montgomery), natural row order
+    uint64_t mstride;
+    const uint32_t* prep;  // null for a chip without preprocessed columns
+    uint64_t pstride;
+    uint64_t n;            // height, a power of two
+    uint32_t width, prep_width;
+    const vair::Instr* prog;
+    uint32_t n_instrs, n_regs, K;  // K = constraints of the chip
+    const uint32_t* iw;            // the chip's interactions (interactions.hpp: encode_interactions): the counts, for liveness
+    const uint32_t* wr;            // the interaction rows of the Jacobian (host/rank_audit.hpp: ra_weight_rows)
+    int native_chip;               // a vchips::ChipId with constraints, CA_INTERPRET, or MA_BUS_ONLY
+    uint32_t NW, RPW, T, NB;       // ra_shape
+    double evaluations;            // dual row evaluations of the counting pass at most (full rank ends a row early): the profile's `ops`
+};
+inline uint64_t ra_totals_words(const RaArgs& a) { return 2 * (4ull + 2ull * a.width); }  // u32 words of the u64 totals
+// Waves per workgroup, rows per wave and workgroups of a chip's launch; throws std::invalid_argument when the chip does not fit the LDS with one wave
+void ra_shape(RaArgs& a);
+size_t ra_lds_bytes(const RaArgs& a, uint32_t NW, uint32_t T);
+void launch_ra_count(hipStream_t st, const RaArgs& a, unsigned long long* totals, uint32_t* table);
+// columns below c_cut with a coupled row are listed
+void launch_ra_scan(hipStream_t st, const RaArgs& a, const uint32_t* table, uint32_t* prefix, uint32_t c_cut);
+void launch_ra_list(hipStream_t st, const RaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t c_cut, uint32_t R, uint32_t* rows);
 // coverage_audit.hip — the passes of the coverage audit (host/coverage_audit.hpp: contract; Prover::coverage_audit drives them), per chip.  The
 // evaluations are the mutation audit's (MaArgs; mutation_eval.hpp).  A CELL of a chip is ((detector * width + column) * D + delta index),
 // cells = (K + M) * width * D of them.  audit: wg_tables [GX][cells][4] u32 {kills, sole, ~first_row, ~first_sole_row} (zeroed), one table per
