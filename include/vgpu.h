@@ -597,6 +597,68 @@ const uint32_t* vgpu_rank_report_words(const vgpu_rank_report_t* r);
 void vgpu_rank_report_timing(const vgpu_rank_report_t* r, double out[3]);
 void vgpu_rank_report_free(vgpu_rank_report_t* r);
 
+/* ---- Field audit: which FIELDS of a chip's bus records its constraints leave undetermined.  The row audits above share one rule: a changed bus
+ * record detects, so a cell that feeds a record counts as bound in every one of them.  That leaves them blind to a chip that receives
+ * (opcode, a, b, c) and never ties c to a and b.  The field audit asks the rank audit's Jacobian per record field instead of per cell.  Inputs:
+ * exactly what vgpu_prove and the audits take.  Chip h, main matrix M (height n, width w), row r; the rows are those of the rank audit's
+ * Jacobian J_r (the same domain, the same n = 1 rule, derivatives at the witness as it is):
+ *   C              the constraint rows dC_k / dM[r][c] at q = r and at q = (r - 1) mod n.
+ *   psi_m          the main-column weights of the count of every interaction m, live or not.
+ *   phi_{m,j}      the main-column weights of field j of interaction m; they exist only when m is LIVE at r: its count is non-zero on M.
+ *   per field      of a live interaction m: the field is CONSTANT when phi_{m,j} = 0 (it reads only constants or preprocessed columns); a
+ *                  constant field is never audited and never floats.  Otherwise S_{m,j} = C + {psi_*} + {phi_{m,i} : i != j}; the field is
+ *                  DETERMINED at r iff phi_{m,j} lies in the row space of S_{m,j}, otherwise it FLOATS: there is a direction v in the row's
+ *                  cells that leaves every constraint, every count and every other field of that record unchanged to first order and moves this
+ *                  field.
+ *   not held fixed the records of the chip's OTHER interactions, deliberately.  The same cell often also goes to the range bus (the output
+ *                  bytes of add and sub) or to a sister record (cpu's channel values, shift's two records); holding that copy fixed would hide
+ *                  exactly the holes this audit is for.
+ *   direction      of a floating field: R = the reduced row echelon form of S_{m,j}, b_f = the null-space basis vector of non-pivot column f
+ *                  (the rank audit's definition: 1 at f, -R[row of p][f] at every pivot column p), f the smallest with phi_{m,j} . b_f != 0,
+ *                  v = b_f / (phi_{m,j} . b_f): S v = 0 and phi v = 1.  R is unique, so no elimination order changes a word.
+ *   order          an entry is a (chip, interaction, field) with a floating row; entries ascend, each with its first max_rows_per_entry
+ *                  floating rows in ascending order.  Only the first max_entries entries are listed; the totals stay exact and `truncated` says
+ *                  the list was cut.  The same words run after run, from device and host, for Machine.basic and for captured AIRs.
+ * What it is not: it is FIRST ORDER, on THIS witness, with the other rows' cells held fixed.  b (b - 1) = 0 pins b here (this is why add's
+ * carries count as bound); x^2 = 0 at x = 0 makes x look free; a field determined only for y != 0 (z = x y, field x) floats on the rows where
+ * y = 0.  A floating field on a SEND usually means "this chip delegates" (cpu's read values, shift's output): the finding is a field that also
+ * floats on the receiving chip.  Inputs are not functions of outputs, so lt's operands are expected to float.  `check`'s exit status never
+ * depends on this audit.
+ * Options are exactly the rank audit's (vgpu_rank_audit_opts_t: max_entries, max_rows_per_entry, chip_mask, reserved), with the same defaults
+ * and refusals; unselected chips keep their block with audited = 0 and zero counts.
+ * vgpu_field_audit runs on the device (kernels/field_audit.hip: one wave per trace row, one lane per column, the base elimination of C and the
+ * counts once per row in LDS, each live record's fields in a small quotient), queued on the prover context like a proof or the other audits; it
+ * accepts device-generated and uploaded traces.  Scratch comes from the prover's pool: per chip 24 bytes + 8 per interaction and per field of
+ * totals, 8 bytes per (field, workgroup of T rows; T = 1 to 64), the interaction weight rows (4 w bytes per count and field),
+ * 72 max_rows_per_entry bytes per field up to the last listed one of the chip with the most, plus the working-layout copy of every uploaded
+ * trace; VGPU_ERR_OOM with the arithmetic in the message when the pool cannot give them.  VGPU_ERR_INVALID_ARG for bad shapes, for a chip of
+ * more than 192 columns, for an interaction of more than 32 fields, and for a chip that does not fit 160 KB of LDS with one wave per workgroup:
+ * with F = the most fields of one interaction, 4 x (w (w | 1) [basis] + K w [raw Jacobian rows] + F ((w + F) | 1) [quotient] + 128 registers
+ * [captured AIR under the interpreting prover] + 4 w + 3 F + 12 + 3 fields + 5 interactions + 3 (w + preprocessed w)) bytes <= 163840.
+ * vgpu_field_audit_host is the same contract on the host over canonical row-major matrices (dual-number evaluation of the chip's Program, RREF
+ * by row insertion, one elimination per field; one thread, no device, no limits).  Both validate shapes as vgpu_prove does.
+ * Report image (vgpu_field_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x31414656 "VFA1" [1] word count [2] terms per listed row, always 8 [3] truncated [4,5] total_entries = (chip, interaction, field) with
+ *   a floating row (exact even when the list is cut) [6] reported [7] n_chips
+ *   per chip, in machine order: width, constraints, interactions, audited (0 / 1), height (u64), live records = sum over rows of live
+ *   interactions (u64), floating fields = sum over rows and fields (u64), rows with at least one floating field (u64); then per interaction:
+ *   is_send, bus kind (0 local, 1 global), bus index, n_fields, live rows (u64), then per field: constant (0 / 1), floating rows (u64)
+ *   per reported entry: chip, interaction, field, n_listed, floating rows (u64), then n_listed rows of 18 words: row, n_support (exact), then
+ *   the first 8 (column, coefficient) terms of the direction v in ascending column order, unused slots 0. */
+typedef struct vgpu_field_report vgpu_field_report_t;
+int32_t vgpu_field_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                         uint32_t n_prep, const vgpu_rank_audit_opts_t* opts, vgpu_field_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_field_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                              const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                              const vgpu_rank_audit_opts_t* opts, vgpu_field_report_t** out);
+uint64_t vgpu_field_report_len(const vgpu_field_report_t* r);
+const uint32_t* vgpu_field_report_words(const vgpu_field_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: the dual row evaluations: 2 w per
+ * row of a chip with constraints and interactions (w for n = 1); the listing pass evaluates its listed rows again, uncounted */
+void vgpu_field_report_timing(const vgpu_field_report_t* r, double out[3]);
+void vgpu_field_report_free(vgpu_field_report_t* r);
+
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
  *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct

@@ -1435,6 +1435,110 @@ def rank_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max_
     return _rank_report(h)
 
 
+class FieldReport:
+    """The field audit of a witness (vgpu_field_audit / vgpu_field_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
+    truncated, total_entries ((chip, interaction, field) with a floating row), reported,
+    chips = [dict(chip, width, constraints, interactions, audited, height, live_records, floating_fields, floating_rows (sums over the rows),
+    records=[dict(interaction, is_send, is_global, bus_index, fields, live_rows, constant=[flag per field], floating=[rows per field])])],
+    entries = [dict(chip, interaction, field, floating, rows=[dict(row, n_support, terms=[(column, coefficient)])])] ascending,
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (dual row evaluations).
+    First order, THIS witness, the other rows' cells held fixed; a floating field on a send usually means that the chip delegates."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 8 or w[0] != 0x31414656 or w[1] != len(w) or w[2] != 8:
+            raise ValueError("not a field report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.truncated = bool(w[3])
+        self.total_entries, self.reported = w[4] | (w[5] << 32), w[6]
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 8
+        self.chips = []
+        for c in range(w[7]):
+            chip = dict(chip=c, width=w[pos], constraints=w[pos + 1], interactions=w[pos + 2], audited=bool(w[pos + 3]), height=u64(pos + 4), live_records=u64(pos + 6),
+                        floating_fields=u64(pos + 8), floating_rows=u64(pos + 10), records=[])
+            pos += 12
+            for m in range(chip["interactions"]):
+                nf = w[pos + 3]
+                chip["records"].append(dict(interaction=m, is_send=bool(w[pos]), is_global=bool(w[pos + 1]), bus_index=w[pos + 2], fields=nf, live_rows=u64(pos + 4),
+                                            constant=[bool(w[pos + 6 + 3 * j]) for j in range(nf)], floating=[u64(pos + 7 + 3 * j) for j in range(nf)]))
+                pos += 6 + 3 * nf
+            self.chips.append(chip)
+        self.entries = []
+        for _ in range(self.reported):
+            rows = []
+            for k in range(w[pos + 3]):
+                at = pos + 6 + 18 * k
+                rows.append(dict(row=w[at], n_support=w[at + 1], terms=[(w[at + 2 + 2 * i], w[at + 3 + 2 * i]) for i in range(min(8, w[at + 1]))]))
+            self.entries.append(dict(chip=w[pos], interaction=w[pos + 1], field=w[pos + 2], floating=u64(pos + 4), rows=rows))
+            pos += 6 + 18 * w[pos + 3]
+        assert pos == len(w)
+
+    def floating(self, chip):
+        """{(interaction, field): rows where the field floats} of `chip`, the fields that float on some row (exact, from the per-field counts)."""
+        return {(r["interaction"], j): n for r in self.chips[chip]["records"] for j, n in enumerate(r["floating"]) if n}
+
+    def to_dict(self):
+        return dict(truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
+                    evaluations=self.evaluations, chips=self.chips, entries=self.entries)
+
+    def to_json(self):
+        import json
+
+        return json.dumps(self.to_dict())
+
+
+def _field_opts(max_entries, max_rows_per_entry, chips):
+    # the rank audit's options (vgpu_rank_audit_opts_t) and refusals, under this audit's name
+    if int(max_entries) < 1 or int(max_rows_per_entry) < 1:
+        raise VgpuError(-1, "field_audit: max_entries and max_rows_per_entry must be at least 1")
+    if chips is not None and (not list(chips) or any(int(c) < 0 or int(c) > 31 for c in chips)):
+        raise VgpuError(-1, "field_audit: chips is a non-empty list of chip indices below 32")
+    return _rank_opts(max_entries, max_rows_per_entry, chips)
+
+
+def _field_report(h):
+    L = lib()
+    L.vgpu_field_report_len.restype = ctypes.c_uint64
+    L.vgpu_field_report_words.restype = c_u32p
+    L.vgpu_field_report_len.argtypes = L.vgpu_field_report_words.argtypes = L.vgpu_field_report_free.argtypes = [ctypes.c_void_p]
+    L.vgpu_field_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    try:
+        n = int(L.vgpu_field_report_len(h))
+        words = np.ctypeslib.as_array(L.vgpu_field_report_words(h), shape=(n,)).copy()
+        tm = (ctypes.c_double * 3)()
+        L.vgpu_field_report_timing(h, tm)
+    finally:
+        L.vgpu_field_report_free(h)
+    return FieldReport(words, tm[0], tm[1], tm[2])
+
+
+def field_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
+    """The field audit on the HOST (vgpu_field_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
+    [(chip index, matrix)], chips = the chip indices to audit (default: all); a FieldReport back."""
+    opts = _field_opts(max_entries, max_rows_per_entry, chips)
+    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
+    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
+    for m in mains + [m for _, m in preps]:
+        if m.ndim != 2:
+            raise VgpuError(-1, "field_audit: traces are two-dimensional matrices")
+
+    def arrays(ms):
+        n = max(1, len(ms))
+        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
+
+    mp, mh, mw = arrays(mains)
+    pp, ph, pw = arrays([m for _, m in preps])
+    chip_ids = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
+    h = ctypes.c_void_p()
+    _check(lib().vgpu_field_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chip_ids, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
+    return _field_report(h)
+
+
 class CoverageAuditOpts(ctypes.Structure):  # vgpu_coverage_audit_opts_t
     _fields_ = [("max_cells", ctypes.c_uint64), ("n_deltas", ctypes.c_uint32), ("deltas", ctypes.c_uint32 * 4), ("max_workgroups", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32 * 2)]
@@ -1846,6 +1950,18 @@ class Prover:
         h = ctypes.c_void_p()
         _check(lib().vgpu_rank_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
         return _rank_report(h)
+
+    def field_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
+        """Which fields of the chips' bus records this witness's constraints leave undetermined (vgpu_field_audit): per row and live record,
+        is each field fixed to first order by the constraints, the counts and the record's other fields; the arguments of prove, chips = the
+        chip indices to audit (default: all); a FieldReport back."""
+        opts = _field_opts(max_entries, max_rows_per_entry, chips)
+        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
+        chip_ids = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
+        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_field_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
+        return _field_report(h)
 
     def coverage_audit(self, main, preprocessed, deltas=None, max_cells=8192, max_workgroups=0):
         """Which constraint or interaction detects each mutation of the mutation audit (vgpu_coverage_audit): the arguments of prove, deltas as

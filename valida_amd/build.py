@@ -29,6 +29,7 @@ SOURCES = [
     "kernels/coverage_audit.hip",
     "kernels/pair_audit.hip",
     "kernels/rank_audit.hip",
+    "kernels/field_audit.hip",
     "host/prover.cpp",
     "host/sharded_prover.cpp",
     "capi.cpp",

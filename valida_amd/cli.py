@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -51,6 +51,15 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         --host), restricted by the same --chips.  The JSON report gets one more key, "rank" (RankReport.to_json's object); stdout gets one line
         per chip that has a coupled column (bound alone, slack together), `add: 12 coupled columns: 0 1 2 ..; max nullity 8; 23 coupled rows`.
         First order, one row, THIS witness, not a soundness proof: the exit status does not depend on this flag.
+        --fields adds the field audit of the same witness (vgpu_field_audit: per trace row and live bus record, which of the record's fields the
+        chip's constraints, the counts and the record's other fields leave undetermined to first order — the rank audit's Jacobian asked per
+        record FIELD instead of per cell: a chip that receives (opcode, a, b, c) and never ties c to a and b), on the same path (device or --host),
+        restricted by the same --chips.  The JSON report gets one more key, "fields" (FieldReport.to_json's object); stdout gets one line per
+        (chip, interaction) with a floating field, `div: interaction 0 (receives on the general bus): fields 0-12 float on 2 of 2 live rows`
+        (the largest row count of a floating field).  First order, on THIS witness, the other rows' cells held fixed: b (b - 1) = 0 pins b, x^2 = 0
+        at x = 0 makes x look free, a field determined only for y != 0 floats on the rows where y = 0.  A floating field on a SEND usually means
+        that the chip delegates (cpu's read values, shift's output): the finding is a field that also floats on the receiving chip; inputs are
+        not functions of outputs, so lt's operands are expected to float.  The exit status does not depend on this flag.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -234,6 +243,25 @@ def rank_lines(report, limit=16):
     return lines
 
 
+def field_lines(report):
+    """One line per (chip, interaction) of a field report with a floating field: the bus, the fields, the most rows one of them floats on."""
+    import valida_amd as va
+
+    lines = []
+    for c in report.chips:
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        for r in c["records"]:
+            fl = [j for j, n in enumerate(r["floating"]) if n]
+            if not fl:
+                continue
+            key = (1 if r["is_global"] else 0, r["bus_index"])
+            bus = "the %s bus" % va.BUS_NAMES[key] if key in va.BUS_NAMES else "bus (%s, %d)" % ("global" if key[0] else "local", key[1])
+            lines.append("%s: interaction %d (%s on %s): field%s %s float%s on %d of %d live row%s" % (
+                name, r["interaction"], "sends" if r["is_send"] else "receives", bus, "" if len(fl) == 1 else "s", index_ranges(fl), "s" if len(fl) == 1 else "",
+                max(r["floating"]), r["live_rows"], "" if r["live_rows"] == 1 else "s"))
+    return lines
+
+
 def coverage_lines(report):
     """One line per chip of a coverage report that has a dead or shadowed detector: the dead constraints / interactions by index, those that
     are never the only detector of a mutation, and how many detectors are essential."""
@@ -283,7 +311,9 @@ def main(argv=None):
                     "alone is noticed; never changes the exit status)")
     ap.add_argument("--rank", action="store_true", help="check: also the rank audit (per row the null space of the Jacobian of all constraints and bus records: "
                     "every first-order degree of freedom; never changes the exit status)")
-    ap.add_argument("--chips", default="", help="check --pairs / --rank: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
+    ap.add_argument("--fields", action="store_true", help="check: also the field audit (per live bus record the fields the chip's constraints leave undetermined to "
+                    "first order on this witness; a floating field on a send usually means the chip delegates; never changes the exit status)")
+    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -315,6 +345,7 @@ def main(argv=None):
                 kreport = va.coverage_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_cells=1 << 20) if args.coverage else None
                 preport = va.pair_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.pairs else None
                 rreport = va.rank_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.rank else None
+                freport = va.field_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.fields else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -326,6 +357,7 @@ def main(argv=None):
                 kreport = prover.coverage_audit(main, prep, deltas=parse_deltas(args.deltas), max_cells=1 << 20) if args.coverage else None
                 preport = prover.pair_audit(main, prep, deltas=parse_deltas(args.deltas), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.pairs else None
                 rreport = prover.rank_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips)) if args.rank else None
+                freport = prover.field_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips)) if args.fields else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -337,11 +369,13 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), pairs=preport.to_dict()))
             if rreport is not None:
                 text = json.dumps(dict(json.loads(text), rank=rreport.to_dict()))
+            if freport is not None:
+                text = json.dumps(dict(json.loads(text), fields=freport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
                     coverage_lines(kreport) if kreport is not None else []) + (pair_lines(preport) if preport is not None else []) + (
-                    rank_lines(rreport) if rreport is not None else []):
+                    rank_lines(rreport) if rreport is not None else []) + (field_lines(freport) if freport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

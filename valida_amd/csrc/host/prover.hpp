@@ -13,6 +13,7 @@
 #include "coverage_audit.hpp"
 #include "pair_audit.hpp"
 #include "rank_audit.hpp"
+#include "field_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -138,6 +139,12 @@ class Prover {
     // row; the same trace handles, queued on the context like a proof.  Scratch from the pool: per chip 32 + 16 bytes per column, 8 per (column,
     // workgroup of rows), the interaction weight rows, 72 x max_rows_per_entry per listed column slot of the chip with the most.
     RankReport rank_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const RankAuditOpts& opts);
+
+    // Field audit of a witness (host/field_audit.hpp, kernels/field_audit.hip): per row and live bus record the fields the chip leaves
+    // undetermined; the same trace handles and options as the rank audit, queued on the context like a proof.  Scratch from the pool: per chip
+    // 24 bytes + 8 per interaction and field, 8 per (field, workgroup of rows), the interaction weight rows, 72 x max_rows_per_entry per listed
+    // field slot of the chip with the most.
+    FieldReport field_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const RankAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

@@ -264,6 +264,36 @@ void launch_ra_count(hipStream_t st, const RaArgs& a, unsigned long long* totals
 // columns below c_cut with a coupled row are listed
 void launch_ra_scan(hipStream_t st, const RaArgs& a, const uint32_t* table, uint32_t* prefix, uint32_t c_cut);
 void launch_ra_list(hipStream_t st, const RaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t c_cut, uint32_t R, uint32_t* rows);
+// field_audit.hip — the passes of the field audit (host/field_audit.hpp: contract; Prover::field_audit drives them), per chip.  One wave per
+// trace row, one wave per workgroup, T rows per workgroup one after the other, NB workgroups.  A SLOT of a chip is (interaction, field) in
+// order, NS of them.  totals: u64 [0] live records, [1] floating fields, [2] rows with a floating field, [3 + m] live rows of interaction m,
+// [3 + M + s] floating rows of slot s (all zeroed); table / prefix: [NS][NB] u32 floating rows of the slot per workgroup and their exclusive
+// prefix (table zeroed); rows: [NS][R][18] u32 (zeroed).
+constexpr uint32_t FA_MAX_FIELDS = 32;  // fields per interaction: a record's float mask is one word
+struct FaArgs {
+    const uint32_t* main;  // column-major working layout (Montgomery), natural row order
+    uint64_t mstride;
+    const uint32_t* prep;  // null for a chip without preprocessed columns
+    uint64_t pstride;
+    uint64_t n;            // height, a power of two
+    uint32_t width, prep_width;
+    const vair::Instr* prog;
+    uint32_t n_instrs, n_regs, K;  // K = constraints of the chip
+    const uint32_t* iw;            // the chip's interactions (interactions.hpp: encode_interactions): the counts, for liveness
+    const uint32_t* wr;            // the interaction rows of the Jacobian (host/rank_audit.hpp: ra_weight_rows)
+    uint32_t M, NS, F;             // interactions, slots, the most fields of one interaction
+    int native_chip;               // a vchips::ChipId with constraints, CA_INTERPRET, or MA_BUS_ONLY
+    uint32_t T, NB;                // fa_shape
+    double evaluations;            // dual row evaluations of the counting pass at most: the profile's `ops`
+};
+inline uint64_t fa_totals_words(const FaArgs& a) { return 2 * (3ull + a.M + a.NS); }  // u32 words of the u64 totals
+// Rows per workgroup and workgroups of a chip's launch; throws std::invalid_argument when the chip does not fit the LDS with one wave
+void fa_shape(FaArgs& a);
+size_t fa_lds_bytes(const FaArgs& a, uint32_t T);
+void launch_fa_count(hipStream_t st, const FaArgs& a, unsigned long long* totals, uint32_t* table);
+// slots below s_cut with a floating row are listed
+void launch_fa_scan(hipStream_t st, const FaArgs& a, const uint32_t* table, uint32_t* prefix, uint32_t s_cut);
+void launch_fa_list(hipStream_t st, const FaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t s_cut, uint32_t R, uint32_t* rows);
 // coverage_audit.hip — the passes of the coverage audit (host/coverage_audit.hpp: contract; Prover::coverage_audit drives them), per chip.  The
 // evaluations are the mutation audit's (MaArgs; mutation_eval.hpp).  A CELL of a chip is ((detector * width + column) * D + delta index),
 // cells = (K + M) * width * D of them.  audit: wg_tables [GX][cells][4] u32 {kills, sole, ~first_row, ~first_sole_row} (zeroed), one table per
