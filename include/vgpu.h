@@ -659,6 +659,63 @@ const uint32_t* vgpu_field_report_words(const vgpu_field_report_t* r);
 void vgpu_field_report_timing(const vgpu_field_report_t* r, double out[3]);
 void vgpu_field_report_free(vgpu_field_report_t* r);
 
+/* ---- Link audit: the bus tuple fields that NO chip on the bus pins — the join the field audit leaves to the reader.  A floating field on a send
+ * usually means that the chip delegates; the finding is a field that floats at every record carrying the tuple.  Inputs: exactly what vgpu_prove
+ * and the other audits take.
+ *   definitions    records, buses, "same tuple" (after zero-padding to the bus's widest interaction) and record order are the bus audit's, word
+ *                  for word; float masks are the field audit's, word for word (the same Jacobian rows, the same n = 1 rule, the same constant
+ *                  rule).  All chips are audited: there is no chip mask, because a join needs every end.
+ *   record mask    of a live record of interaction m with nf fields on a bus of width W <= 32: bit j < nf is set iff field j floats at that row.
+ *                  Bits nf .. W - 1 are clear: a padded position is the constant 0 and so is pinned.  Constant and determined fields are clear.
+ *   tuple mask     the AND of the record masks of all the tuple's records, sends and receives alike.  Position j is OPEN in the tuple iff its
+ *                  bit is set, otherwise it is ANCHORED; a tuple with a non-zero mask is an open tuple.  The audit ignores `net`: it runs on
+ *                  balanced and unbalanced witnesses alike.
+ *   per record     a field that floats at a record is OPEN there if its position is open in the record's tuple, otherwise it is ANSWERED: it
+ *                  floats locally, and another record of the tuple pins it.
+ *   order          open tuples ascend by their first record; each lists its first max_records_per_tuple records in record order.  Only the first
+ *                  max_tuples open tuples are listed; the totals stay exact and `truncated` says the list was cut.  The same words run after run,
+ *                  from device and host, for Machine.basic and for captured AIRs.
+ * What it is not: it is FIRST ORDER, on THIS witness.  Each record is judged alone: the field audit deliberately does not hold sister records of
+ * the same row fixed, so "open" means that no single record's own chip pins the position; a joint move may still be blocked by a sister
+ * record.  "Anchored" is per tuple as it stands: a lookup bus whose receiver can move multiplicities between tuples is not modelled.  `check`'s
+ * exit status never depends on this audit.
+ * Options: max_tuples, max_records_per_tuple and hash_bits are the bus audit's (zeros select its defaults 64, 4 and 64; hash_bits is its test
+ * hook with the same meaning and refusals: the report must not change under it); reserved must be zero.
+ * VGPU_ERR_INVALID_ARG, host and device alike, for bad shapes and for a bus wider than 32 fields (the tuple mask is one word; the message
+ * carries the arithmetic).  vgpu_link_audit runs on the device (kernels/link_audit.hip: the field audit's wave-per-row elimination writes one
+ * mask word per record slot, the bus audit's records / sort / groups / reduce group the records, two streaming passes over the sorted records
+ * AND the masks per tuple and tally them), queued on the prover context like a proof or the other audits; it accepts device-generated and
+ * uploaded traces.  There the field audit's limits apply as well (192 columns, 32 fields per interaction, 160 KB of LDS with one wave per
+ * workgroup: 4 x (w (w | 1) + K w + F ((w + F) | 1) + 128 registers + 4 w + 3 F + 12 + 4 interactions + 3 (w + preprocessed w)) bytes) and
+ * the bus audit's of 2^32 - 2 (row, interaction) pairs.  Scratch comes from the prover's pool: 68 bytes per (row, interaction) pair (the bus
+ * audit's 60, 4 for the record mask, 4 for the tuple mask), 16 per field and 528 per bus of tallies, the interaction weight rows, 24 bytes per
+ * open tuple and the working-layout copy of every uploaded trace; VGPU_ERR_OOM with the arithmetic in the message when the pool cannot give them.
+ * vgpu_link_audit_host is the same contract on the host over canonical row-major matrices (the host field audit's masks, the host bus audit's
+ * records sorted by full padded tuple; one thread, no device, no limit beyond the 32-field bus).
+ * Report image "VLA1" (vgpu_link_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x31414C56 "VLA1" [1] word count [2] truncated [3,4] total open tuples (exact even when the list is cut) [5] reported [6] n_buses
+ *   [7] n_chips
+ *   per bus, ascending (is_global, bus_index): is_global, bus_index, width, live records (u64), tuples (u64), open tuples (u64), then per
+ *   position j < width: tuples in which j is open (u64), records of those tuples (u64)
+ *   per chip, in machine order: interactions, then per interaction: is_send, bus kind (0 local, 1 global), bus index, n_fields, live rows
+ *   (u64), then per field: constant (0 / 1), floating rows (u64; the field audit's count for the same witness), open rows (u64)
+ *   per reported open tuple: is_global, bus_index, width, tuple mask, send records (u64), receive records (u64), n_listed, the width padded
+ *   fields, then n_listed x (chip, row, interaction, is_send, record mask). */
+typedef struct vgpu_link_audit_opts { uint64_t max_tuples; uint32_t max_records_per_tuple; uint32_t hash_bits; uint32_t reserved; } vgpu_link_audit_opts_t;
+typedef struct vgpu_link_report vgpu_link_report_t;
+int32_t vgpu_link_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                        uint32_t n_prep, const vgpu_link_audit_opts_t* opts, vgpu_link_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_link_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                             const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                             const vgpu_link_audit_opts_t* opts, vgpu_link_report_t** out);
+uint64_t vgpu_link_report_len(const vgpu_link_report_t* r);
+const uint32_t* vgpu_link_report_words(const vgpu_link_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: the dual row evaluations of the
+ * masks, counted as the field audit counts them */
+void vgpu_link_report_timing(const vgpu_link_report_t* r, double out[3]);
+void vgpu_link_report_free(vgpu_link_report_t* r);
+
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
  *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct

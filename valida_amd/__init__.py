@@ -1539,6 +1539,126 @@ def field_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max
     return _field_report(h)
 
 
+class LinkAuditOpts(ctypes.Structure):  # vgpu_link_audit_opts_t
+    _fields_ = [("max_tuples", ctypes.c_uint64), ("max_records_per_tuple", ctypes.c_uint32), ("hash_bits", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+class LinkReport:
+    """The link audit of a witness (vgpu_link_audit / vgpu_link_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
+    truncated, open_tuples (tuples with an open position: exact even when the list is cut), reported,
+    buses = [dict(bus=(is_global, bus_index), width, live, tuples, open_tuples, open_in=[tuples in which position j is open], open_records=[the
+    records of those])],
+    chips = [dict(chip, records=[dict(interaction, is_send, is_global, bus_index, fields, live_rows, constant=[flag per field], floating=[rows
+    per field], open=[rows per field])])],
+    tuples = [dict(bus, mask, open=[the open positions], n_send, n_recv, fields, records=[(chip, row, interaction, is_send, record mask)])] in
+    the order of their first records,
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (dual row evaluations of the masks).
+    First order, THIS witness, every record judged alone: open means that no single record's own chip pins the position."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 8 or w[0] != 0x31414C56 or w[1] != len(w):
+            raise ValueError("not a link report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.truncated = bool(w[2])
+        self.open_tuples, self.reported = w[3] | (w[4] << 32), w[5]
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 8
+        self.buses = []
+        for _ in range(w[6]):
+            width = w[pos + 2]
+            self.buses.append(dict(bus=(w[pos], w[pos + 1]), width=width, live=u64(pos + 3), tuples=u64(pos + 5), open_tuples=u64(pos + 7),
+                                   open_in=[u64(pos + 9 + 4 * j) for j in range(width)], open_records=[u64(pos + 11 + 4 * j) for j in range(width)]))
+            pos += 9 + 4 * width
+        self.chips = []
+        for c in range(w[7]):
+            chip = dict(chip=c, records=[])
+            n_inter = w[pos]
+            pos += 1
+            for m in range(n_inter):
+                nf = w[pos + 3]
+                chip["records"].append(dict(interaction=m, is_send=bool(w[pos]), is_global=bool(w[pos + 1]), bus_index=w[pos + 2], fields=nf, live_rows=u64(pos + 4),
+                                            constant=[bool(w[pos + 6 + 5 * j]) for j in range(nf)], floating=[u64(pos + 7 + 5 * j) for j in range(nf)],
+                                            open=[u64(pos + 9 + 5 * j) for j in range(nf)]))
+                pos += 6 + 5 * nf
+            self.chips.append(chip)
+        self.tuples = []
+        for _ in range(self.reported):
+            width, mask, n_listed = w[pos + 2], w[pos + 3], w[pos + 8]
+            t = dict(bus=(w[pos], w[pos + 1]), mask=mask, open=[j for j in range(width) if (mask >> j) & 1], n_send=u64(pos + 4), n_recv=u64(pos + 6), fields=w[pos + 9:pos + 9 + width])
+            pos += 9 + width
+            t["records"] = [tuple(w[pos + 5 * k:pos + 5 * k + 5]) for k in range(n_listed)]
+            pos += 5 * n_listed
+            self.tuples.append(t)
+        assert pos == len(w)
+
+    def open(self, chip):
+        """{(interaction, field): (floating rows, open rows)} of `chip`, the fields that float on some row: a floating row that is not open is
+        answered (another record of its tuple pins the field)."""
+        return {(r["interaction"], j): (n, r["open"][j]) for r in self.chips[chip]["records"] for j, n in enumerate(r["floating"]) if n}
+
+    def to_dict(self):
+        return dict(truncated=self.truncated, open_tuples=self.open_tuples, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms, evaluations=self.evaluations,
+                    buses=[dict(b, bus=list(b["bus"])) for b in self.buses], chips=self.chips,
+                    tuples=[dict(t, bus=list(t["bus"]), records=[list(r) for r in t["records"]]) for t in self.tuples])
+
+    def to_json(self):
+        import json
+
+        return json.dumps(self.to_dict())
+
+
+def _link_opts(max_tuples, max_records_per_tuple, hash_bits):
+    # in the C struct a zero field selects its default, so the refusals of explicit zeros are made here, with the library's status code
+    if not 1 <= int(hash_bits) <= 64:
+        raise VgpuError(-1, "link_audit: hash_bits must be 1..64")
+    if int(max_tuples) < 1 or int(max_records_per_tuple) < 1:
+        raise VgpuError(-1, "link_audit: max_tuples and max_records_per_tuple must be at least 1")
+    return LinkAuditOpts(int(max_tuples), int(max_records_per_tuple), int(hash_bits), 0)
+
+
+def _link_report(h):
+    L = lib()
+    L.vgpu_link_report_len.restype = ctypes.c_uint64
+    L.vgpu_link_report_words.restype = c_u32p
+    L.vgpu_link_report_len.argtypes = L.vgpu_link_report_words.argtypes = L.vgpu_link_report_free.argtypes = [ctypes.c_void_p]
+    L.vgpu_link_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    try:
+        n = int(L.vgpu_link_report_len(h))
+        words = np.ctypeslib.as_array(L.vgpu_link_report_words(h), shape=(n,)).copy()
+        tm = (ctypes.c_double * 3)()
+        L.vgpu_link_report_timing(h, tm)
+    finally:
+        L.vgpu_link_report_free(h)
+    return LinkReport(words, tm[0], tm[1], tm[2])
+
+
+def link_audit_host(machine, main_matrices, preprocessed, max_tuples=64, max_records_per_tuple=4, hash_bits=64):
+    """The link audit on the HOST (vgpu_link_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
+    [(chip index, matrix)]; a LinkReport back.  hash_bits is accepted for symmetry with Prover.link_audit (the host groups by full tuples)."""
+    opts = _link_opts(max_tuples, max_records_per_tuple, hash_bits)
+    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
+    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
+    for m in mains + [m for _, m in preps]:
+        if m.ndim != 2:
+            raise VgpuError(-1, "link_audit: traces are two-dimensional matrices")
+
+    def arrays(ms):
+        n = max(1, len(ms))
+        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
+
+    mp, mh, mw = arrays(mains)
+    pp, ph, pw = arrays([m for _, m in preps])
+    chip_ids = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
+    h = ctypes.c_void_p()
+    _check(lib().vgpu_link_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chip_ids, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
+    return _link_report(h)
+
+
 class CoverageAuditOpts(ctypes.Structure):  # vgpu_coverage_audit_opts_t
     _fields_ = [("max_cells", ctypes.c_uint64), ("n_deltas", ctypes.c_uint32), ("deltas", ctypes.c_uint32 * 4), ("max_workgroups", ctypes.c_uint32),
                 ("reserved", ctypes.c_uint32 * 2)]
@@ -1962,6 +2082,18 @@ class Prover:
         h = ctypes.c_void_p()
         _check(lib().vgpu_field_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
         return _field_report(h)
+
+    def link_audit(self, main, preprocessed, max_tuples=64, max_records_per_tuple=4, hash_bits=64):
+        """Which positions of this witness's bus tuples no chip on the bus pins (vgpu_link_audit): the field audit's float mask of every live
+        record, ANDed over the records of each tuple of the bus audit; the arguments of prove, a LinkReport back.  hash_bits < 64 is the bus
+        audit's test hook (the grouping key is cut; the report must not change)."""
+        opts = _link_opts(max_tuples, max_records_per_tuple, hash_bits)
+        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
+        chip_ids = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
+        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_link_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
+        return _link_report(h)
 
     def coverage_audit(self, main, preprocessed, deltas=None, max_cells=8192, max_workgroups=0):
         """Which constraint or interaction detects each mutation of the mutation audit (vgpu_coverage_audit): the arguments of prove, deltas as

@@ -30,6 +30,7 @@ SOURCES = [
     "kernels/pair_audit.hip",
     "kernels/rank_audit.hip",
     "kernels/field_audit.hip",
+    "kernels/link_audit.hip",
     "host/prover.cpp",
     "host/sharded_prover.cpp",
     "capi.cpp",

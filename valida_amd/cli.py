@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -60,6 +60,16 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         at x = 0 makes x look free, a field determined only for y != 0 floats on the rows where y = 0.  A floating field on a SEND usually means
         that the chip delegates (cpu's read values, shift's output): the finding is a field that also floats on the receiving chip; inputs are
         not functions of outputs, so lt's operands are expected to float.  The exit status does not depend on this flag.
+        --links adds the link audit of the same witness (vgpu_link_audit: the field audit's float mask of every live record ANDed over the
+        records of each bus tuple, sends and receives alike — a position that floats at EVERY record of a tuple is open: no chip on the bus pins
+        it; a field that floats at a record whose tuple has it pinned elsewhere is answered), on the same path (device or --host), always over all
+        chips; --max-tuples and --max-records cut the listed open tuples.  The JSON report gets one more key, "links" (LinkReport.to_json's
+        object); stdout gets one line per bus with an open tuple, `memory bus: 349 of 349 tuples open; open positions 2, 4-7`, and one line per
+        (chip, interaction) whose floating fields are not all answered, `mem: interaction 0 (receives on the memory bus): fields 2, 4-7 open on
+        401 of 401 floating rows` (per field the largest counts).  First order, on THIS witness; each record is judged alone (sister records of
+        the same row are not held fixed), so "open" means that no single record's own chip pins the position — a joint move may still be blocked
+        by a sister record; "anchored" is per tuple as it stands: a lookup bus whose receiver can move multiplicities between tuples is not
+        modelled.  The exit status does not depend on this flag.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -262,6 +272,34 @@ def field_lines(report):
     return lines
 
 
+def link_lines(report):
+    """One line per bus of a link report with an open tuple (open and total tuples, the open positions), then one per (chip, interaction)
+    whose floating fields are not all answered (the open fields, the most open rows of one of them, the most floating rows)."""
+    import valida_amd as va
+
+    def bus_name(key):
+        return "%s bus" % va.BUS_NAMES[key] if key in va.BUS_NAMES else "bus (%s, %d)" % ("global" if key[0] else "local", key[1])
+
+    lines = []
+    for b in report.buses:
+        if not b["open_tuples"]:
+            continue
+        pos = [j for j, n in enumerate(b["open_in"]) if n]
+        lines.append("%s: %d of %d tuple%s open; open position%s %s" % (bus_name(tuple(b["bus"])), b["open_tuples"], b["tuples"], "" if b["tuples"] == 1 else "s",
+                                                                    "" if len(pos) == 1 else "s", index_ranges(pos)))
+    for c in report.chips:
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        for r in c["records"]:
+            op = [j for j, n in enumerate(r["open"]) if n]
+            if not op:
+                continue
+            key = (1 if r["is_global"] else 0, r["bus_index"])
+            lines.append("%s: interaction %d (%s on the %s): field%s %s open on %d of %d floating row%s" % (
+                name, r["interaction"], "sends" if r["is_send"] else "receives", bus_name(key), "" if len(op) == 1 else "s", index_ranges(op), max(r["open"]), max(r["floating"]),
+                "" if max(r["floating"]) == 1 else "s"))
+    return lines
+
+
 def coverage_lines(report):
     """One line per chip of a coverage report that has a dead or shadowed detector: the dead constraints / interactions by index, those that
     are never the only detector of a mutation, and how many detectors are essential."""
@@ -313,6 +351,8 @@ def main(argv=None):
                     "every first-order degree of freedom; never changes the exit status)")
     ap.add_argument("--fields", action="store_true", help="check: also the field audit (per live bus record the fields the chip's constraints leave undetermined to "
                     "first order on this witness; a floating field on a send usually means the chip delegates; never changes the exit status)")
+    ap.add_argument("--links", action="store_true", help="check: also the link audit (the bus tuple positions that float at every record of the tuple, send or receive: "
+                    "no chip on the bus pins them; first order, on this witness, each record judged alone; never changes the exit status)")
     ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
     _config_flags(ap)
     args = ap.parse_args(argv)
@@ -346,6 +386,7 @@ def main(argv=None):
                 preport = va.pair_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), deltas=parse_deltas(args.deltas), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.pairs else None
                 rreport = va.rank_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.rank else None
                 freport = va.field_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.fields else None
+                lreport = va.link_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_tuples=args.max_tuples, max_records_per_tuple=args.max_records) if args.links else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -358,6 +399,7 @@ def main(argv=None):
                 preport = prover.pair_audit(main, prep, deltas=parse_deltas(args.deltas), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.pairs else None
                 rreport = prover.rank_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips)) if args.rank else None
                 freport = prover.field_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips)) if args.fields else None
+                lreport = prover.link_audit(main, prep, max_tuples=args.max_tuples, max_records_per_tuple=args.max_records) if args.links else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -371,11 +413,14 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), rank=rreport.to_dict()))
             if freport is not None:
                 text = json.dumps(dict(json.loads(text), fields=freport.to_dict()))
+            if lreport is not None:
+                text = json.dumps(dict(json.loads(text), links=lreport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
                     coverage_lines(kreport) if kreport is not None else []) + (pair_lines(preport) if preport is not None else []) + (
-                    rank_lines(rreport) if rreport is not None else []) + (field_lines(freport) if freport is not None else []):
+                    rank_lines(rreport) if rreport is not None else []) + (field_lines(freport) if freport is not None else []) + (
+                    link_lines(lreport) if lreport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

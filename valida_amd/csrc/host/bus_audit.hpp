@@ -196,20 +196,22 @@ inline void bus_audit_finish(BusReport& r, const BusAuditOpts& o) {
 
 struct BusHostMatrix { const uint32_t* data; uint64_t height, width; };  // canonical row-major (the reference's RowMajorMatrix<Val>)
 
-// The contract on the host: evaluate, sort, reduce.  One thread; exact by construction (records are grouped by their full tuples).
-inline BusReport bus_audit_host(const MachineDesc& machine, const std::vector<BusHostMatrix>& main, const std::vector<int>& prep_chips,
-                                const std::vector<BusHostMatrix>& prep, const BusAuditOpts& opts_in) {
-    const BusAuditOpts o = bus_audit_checked_opts(opts_in);
-    std::vector<BusShape> ms, ps;
-    for (auto& m : main) { if (!m.data) throw std::invalid_argument("bus_audit: null trace"); ms.push_back({m.height, m.width}); }
-    for (auto& m : prep) { if (!m.data) throw std::invalid_argument("bus_audit: null trace"); ps.push_back({m.height, m.width}); }
-    std::vector<int> prep_slot;
-    const BusPlan plan = bus_audit_plan(machine, ms, prep_chips, ps, prep_slot);
-    const size_t NB = plan.buses.size();
+// Every live record of the witness per bus slot, in record order, with its tuple padded to the bus's width, and per bus the order that makes
+// equal tuples adjacent (ties in record order): what bus_audit_host reduces and the link audit joins (host/link_audit.hpp).  Adds the records to
+// live / sends / receives of `stats` (one entry per bus slot).
+struct BusHostRecords {
     struct PerBus { std::vector<uint32_t> fields; std::vector<uint64_t> id; std::vector<uint32_t> cnt; std::vector<uint8_t> send; };
-    std::vector<PerBus> per(NB);
-    BusReport rep;
-    rep.buses = plan.buses;
+    std::vector<PerBus> per;
+    std::vector<std::vector<uint32_t>> order;
+};
+inline BusHostRecords bus_audit_host_records(const MachineDesc& machine, const BusPlan& plan, const std::vector<BusHostMatrix>& main, const std::vector<BusHostMatrix>& prep,
+                                             const std::vector<int>& prep_slot, std::vector<BusStat>& stats) {
+    const size_t NB = plan.buses.size();
+    using PerBus = BusHostRecords::PerBus;
+    BusHostRecords out;
+    out.per.resize(NB);
+    out.order.resize(NB);
+    std::vector<PerBus>& per = out.per;
     auto eval = [](const vair::VirtualCol& v, const uint32_t* mrow, const uint32_t* prow) {
         uint64_t acc = v.constant % vg::P;
         for (auto& t : v.terms) acc = (acc + (uint64_t)((t.preprocessed ? prow : mrow)[t.col] % vg::P) * (t.weight % vg::P)) % vg::P;
@@ -237,14 +239,12 @@ inline BusReport bus_audit_host(const MachineDesc& machine, const std::vector<Bu
                 pb.id.push_back(plan.chips[c].first_id + r * M + m);
                 pb.cnt.push_back(cnt);
                 pb.send.push_back(it.is_send() ? 1 : 0);
-                rep.buses[b].live++;
-                (it.is_send() ? rep.buses[b].sends : rep.buses[b].receives)++;
+                stats[b].live++;
+                (it.is_send() ? stats[b].sends : stats[b].receives)++;
             }
         }
     }
-    struct Unb { uint64_t first_id; uint32_t bus; size_t lo, hi; uint32_t send, recv; uint64_t ns, nr; };
-    std::vector<Unb> unb;
-    std::vector<std::vector<uint32_t>> order(NB);
+    std::vector<std::vector<uint32_t>>& order = out.order;
     for (size_t b = 0; b < NB; b++) {
         PerBus& pb = per[b];
         const uint32_t W = plan.buses[b].width;
@@ -257,6 +257,33 @@ inline BusReport bus_audit_host(const MachineDesc& machine, const std::vector<Bu
             const int c = W ? memcmp(f + (size_t)x * W, f + (size_t)y * W, (size_t)W * 4) : 0;  // any total order on tuples groups them
             return c != 0 ? c < 0 : x < y;
         });
+    }
+    return out;
+}
+
+// The contract on the host: evaluate, sort, reduce.  One thread; exact by construction (records are grouped by their full tuples).
+inline BusReport bus_audit_host(const MachineDesc& machine, const std::vector<BusHostMatrix>& main, const std::vector<int>& prep_chips,
+                                const std::vector<BusHostMatrix>& prep, const BusAuditOpts& opts_in) {
+    const BusAuditOpts o = bus_audit_checked_opts(opts_in);
+    std::vector<BusShape> ms, ps;
+    for (auto& m : main) { if (!m.data) throw std::invalid_argument("bus_audit: null trace"); ms.push_back({m.height, m.width}); }
+    for (auto& m : prep) { if (!m.data) throw std::invalid_argument("bus_audit: null trace"); ps.push_back({m.height, m.width}); }
+    std::vector<int> prep_slot;
+    const BusPlan plan = bus_audit_plan(machine, ms, prep_chips, ps, prep_slot);
+    const size_t NB = plan.buses.size();
+    BusReport rep;
+    rep.buses = plan.buses;
+    const BusHostRecords recs = bus_audit_host_records(machine, plan, main, prep, prep_slot, rep.buses);
+    using PerBus = BusHostRecords::PerBus;
+    const std::vector<PerBus>& per = recs.per;
+    const std::vector<std::vector<uint32_t>>& order = recs.order;
+    struct Unb { uint64_t first_id; uint32_t bus; size_t lo, hi; uint32_t send, recv; uint64_t ns, nr; };
+    std::vector<Unb> unb;
+    for (size_t b = 0; b < NB; b++) {
+        const PerBus& pb = per[b];
+        const std::vector<uint32_t>& idx = order[b];
+        const uint32_t W = plan.buses[b].width;
+        const uint32_t* f = pb.fields.data();
         for (size_t lo = 0; lo < idx.size();) {
             size_t hi = lo + 1;
             while (hi < idx.size() && (W == 0 || memcmp(f + (size_t)idx[lo] * W, f + (size_t)idx[hi] * W, (size_t)W * 4) == 0)) hi++;

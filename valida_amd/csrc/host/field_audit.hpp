@@ -22,6 +22,7 @@
 // This header holds what host and device share — the report and its word image — and the host implementation (plain C++, one thread, no
 // limits).  Options are the rank audit's.  The device pass is Prover::field_audit (prover.cpp, kernels/field_audit.hip).
 #pragma once
+#include <functional>
 #include "rank_audit.hpp"
 
 namespace vhost {
@@ -152,9 +153,11 @@ inline void field_audit_reduce(const RankBasis& B, std::vector<vg::Fp>& x) {
 
 // The contract on the host, literally: per row the base basis of C and the counts; per live record and field a copy of it with the other
 // fields inserted, and the field reduced against it.  A chip without constraints depends on the row only through its live set: the row before's
-// answer is kept while the live set repeats.
+// answer is kept while the live set repeats.  on_record, when given, is called once per audited live record in record order with the
+// record's float mask (bit j: field j floats; fields from 32 on are not in it): what the link audit joins (host/link_audit.hpp).
+using FieldRecordFn = std::function<void(uint32_t chip, uint64_t row, uint32_t interaction, uint32_t float_mask)>;
 inline FieldReport field_audit_host(const MachineDesc& machine, const std::vector<ConstraintHostMatrix>& main, const std::vector<int>& prep_chips,
-                                    const std::vector<ConstraintHostMatrix>& prep, const RankAuditOpts& opts_in) {
+                                    const std::vector<ConstraintHostMatrix>& prep, const RankAuditOpts& opts_in, const FieldRecordFn* on_record = nullptr) {
     const RankAuditOpts o = field_audit_checked_opts(opts_in, machine.airs.size());
     std::vector<ConstraintShape> ms, ps;
     for (auto& m : main) { if (!m.data) throw std::invalid_argument("field_audit: null trace"); ms.push_back({m.height, m.width}); }
@@ -277,6 +280,11 @@ inline FieldReport field_audit_host(const MachineDesc& machine, const std::vecto
                 if (!live[m]) continue;
                 FieldInteractionStat& s = cs.interactions[m];
                 s.live_rows++; cs.live_records++;
+                if (on_record) {
+                    uint32_t mask = 0;
+                    for (uint32_t j = 0; j < s.n_fields && j < 32u; j++) mask |= fl[m][j] ? 1u << j : 0u;
+                    (*on_record)((uint32_t)c, r, (uint32_t)m, mask);
+                }
                 for (uint32_t j = 0; j < s.n_fields; j++) {
                     if (!fl[m][j]) continue;
                     any = true;

@@ -2076,6 +2076,216 @@ FieldReport Prover::field_audit(const std::vector<const DeviceTrace*>& main, con
     return rep;
 }
 
+// ---- link audit (host/link_audit.hpp; kernels/link_audit.hip) ------------------------------------------------------------------------------
+LinkReport Prover::link_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const LinkAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const LinkAuditOpts o = link_audit_checked_opts(opts_in);
+    std::vector<BusShape> ms, ps;
+    std::vector<int> prep_chips, prep_slot;
+    for (auto t : main) { if (!t) throw std::invalid_argument("link_audit: null trace"); ms.push_back({t->height, t->width}); }
+    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("link_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
+    const BusPlan plan = link_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
+    const uint64_t n = plan.n_slots;
+    if (n >= 0xffffffffull) throw std::invalid_argument("link_audit: more than 2^32 - 2 (row, interaction) pairs; record ids are 32-bit");
+    const size_t NC = machine_.airs.size(), NB = plan.buses.size();
+    LinkReport rep;
+    link_audit_blocks(rep, machine_, plan);
+    // per chip the mask pass's launch shape (a chip that does not fit the LDS is refused before anything is queued) and its fields' slots
+    std::vector<vk::FaArgs> args(NC);
+    std::vector<std::vector<uint32_t>> wrs(NC);
+    std::vector<uint32_t> lt(4 + NC, 0);  // launch.hpp: the tally's table of field slots
+    uint32_t n_fields = 0;
+    for (size_t i = 0; i < NC; i++) {
+        const AirDesc& air = machine_.airs[i];
+        vk::FaArgs& a = args[i];
+        a = vk::FaArgs{};
+        lt[4 + i] = (uint32_t)lt.size();
+        for (auto& it : rep.chips[i]) { lt.push_back(n_fields); n_fields += it.n_fields; }
+        if (!air.width || air.interactions.empty()) continue;  // no record, or only constant fields: the zeroed masks are the answer
+        wrs[i] = ra_weight_rows(air);
+        a.K = air.program.num_asserts;
+        a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
+        a.n_instrs = (uint32_t)air.program.instrs.size();
+        a.n_regs = air.program.num_regs;
+        a.M = (uint32_t)air.interactions.size();
+        for (auto& it : rep.chips[i]) { a.NS += it.n_fields; a.F = std::max(a.F, it.n_fields); }
+        a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
+        try {
+            vk::la_shape(a);
+        } catch (const std::invalid_argument& e) {
+            throw std::invalid_argument(std::string(e.what()) + " [chip " + air.name + "; the host audit has no limit]");
+        }
+        a.evaluations = a.K ? (double)a.n * a.width * (a.n == 1 ? 1 : 2) : 0;
+        rep.evaluations += a.evaluations;
+    }
+    lt[0] = n_fields;
+    const uint64_t tally_words = vk::la_tally_words(n_fields, (uint32_t)NB);
+
+    DeviceCtx& c = *ctx_;
+    c.activate();
+    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
+    c.activate();
+    struct Running {
+        std::atomic<int>& n;
+        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
+        ~Running() { n.fetch_sub(1); }
+    } running(c.proofs_running);
+    hipStream_t st = c.stream;
+
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
+    VG_HIP_CHECK(hipEventCreate(&ev0));
+    VG_HIP_CHECK(hipEventCreate(&ev1));
+    uint64_t wr_words = 0, n_open = 0;
+    try {
+        // working-layout copies, as prove makes them (traces generated on the device are already column-major Montgomery)
+        std::vector<DMat> own;
+        std::vector<const uint32_t*> mptr(NC, nullptr), pptr(NC, nullptr);
+        std::vector<uint64_t> mstride(NC, 0), pstride(NC, 0);
+        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
+            if (!t->nat.empty()) return t->nat.view();
+            own.emplace_back(&c, t->height, t->width);
+            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
+            return own.back().view();
+        };
+        own.reserve(NC + preprocessed.size());
+        std::vector<uint64_t> wr_at(NC, 0);
+        std::vector<uint32_t> wr_all;
+        for (size_t i = 0; i < NC; i++) {
+            if (!plan.chips[i].M) continue;  // a chip without interactions is not read
+            const vk::DMatView v = working(main[i]);
+            mptr[i] = v.data; mstride[i] = v.stride;
+            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); pptr[i] = pv.data; pstride[i] = pv.stride; }
+            vk::FaArgs& a = args[i];
+            if (!a.width) continue;
+            a.main = mptr[i]; a.mstride = mstride[i]; a.prep = pptr[i]; a.pstride = pstride[i];
+            a.prog = (const vair::Instr*)prog_dev_[i].data;
+            a.iw = iw_dev_[i].data;
+            wr_at[i] = wr_all.size();
+            wr_all.insert(wr_all.end(), wrs[i].begin(), wrs[i].end());
+        }
+        if (wr_all.empty()) wr_all.push_back(0);
+        wr_words = wr_all.size();
+        c.check_launch("link_audit ingest");
+        DBuf desc(&c, bus_audit_descriptor(machine_, plan, mptr, mstride, pptr, pstride)), wr_dev(&c, wr_all), lt_dev(&c, lt);
+        for (size_t i = 0; i < NC; i++) args[i].wr = wr_dev.data + wr_at[i];
+
+        uint32_t total_inter = 0;
+        std::vector<uint32_t> inter_base(NC, 0);
+        for (size_t i = 0; i < NC; i++) { inter_base[i] = total_inter; total_inter += plan.chips[i].M; }
+        const size_t n_counters = 8 + NB + total_inter;
+        const uint64_t na = n ? n : 1;
+        DBuf keys2(&c, (size_t)(4 * na)), ids2(&c, (size_t)(2 * na)), cnt(&c, (size_t)na), gid(&c, (size_t)na), head_pos(&c, (size_t)na), sums(&c, (size_t)(4 * na)),
+            nrec(&c, (size_t)(2 * na)), mask(&c, (size_t)na), tmask(&c, (size_t)na), sort_tmp(&c, vk::bus_audit_sort_scratch_words(na)), scan_tmp(&c, vk::bus_audit_scan_scratch_words(na)),
+            counters(&c, n_counters), tally(&c, (size_t)(2 * tally_words ? 2 * tally_words : 2));
+        unsigned long long* keys = (unsigned long long*)keys2.data;
+        unsigned long long* sums_p = (unsigned long long*)sums.data;
+        // the device pass: everything from here to the last download is between the two events
+        VG_HIP_CHECK(hipEventRecord(ev0, st));
+        VG_HIP_CHECK(hipMemsetAsync(counters.data, 0, n_counters * 4, st));
+        VG_HIP_CHECK(hipMemsetAsync(sums.data, 0, (size_t)(4 * na) * 4, st));
+        VG_HIP_CHECK(hipMemsetAsync(nrec.data, 0, (size_t)(2 * na) * 4, st));
+        VG_HIP_CHECK(hipMemsetAsync(mask.data, 0, (size_t)na * 4, st));
+        VG_HIP_CHECK(hipMemsetAsync(tally.data, 0, (size_t)(2 * tally_words ? 2 * tally_words : 2) * 4, st));
+
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].width) vk::launch_la_masks(st, args[i], (uint32_t)plan.chips[i].first_id, mask.data);
+        for (size_t i = 0; i < NC; i++)
+            vk::launch_ba_records(st, desc.data, (uint32_t)i, plan.chips[i].height, machine_.airs[i].width, plan.chips[i].M, o.hash_bits, keys, ids2.data, cnt.data,
+                                  counters.data + 8 + NB + inter_base[i]);
+        int shifts[8], n_shifts = 0;
+        for (uint32_t b = 0; b < (o.hash_bits + 7) / 8; b++) shifts[n_shifts++] = 8 * (int)b;
+        if (o.hash_bits <= 56) shifts[n_shifts++] = 56;  // the pass that sinks the dead slots (key ~0) behind the live ones
+        int half = vk::launch_ba_sort(st, keys, ids2.data, n, sort_tmp.data, shifts, n_shifts, 0);
+        vk::launch_ba_groups(st, desc.data, keys + (uint64_t)half * n, ids2.data + (uint64_t)half * n, n, false, gid.data, head_pos.data, scan_tmp.data, counters.data);
+        vk::launch_ba_reduce(st, desc.data, ids2.data + (uint64_t)half * n, cnt.data, gid.data, head_pos.data, n, true, sums_p, nrec.data, counters.data);
+        c.check_launch("link_audit");
+        std::vector<uint32_t> cw(n_counters);
+        c.download_small(cw.data(), counters.data, n_counters * 4);
+        if (cw[2]) {
+            // a key collision (the hash_bits test hook forces it): group by the full padded tuples instead, exactly as Prover::bus_audit does
+            VG_HIP_CHECK(hipMemsetAsync(counters.data + 1, 0, (7 + NB) * 4, st));
+            VG_HIP_CHECK(hipMemsetAsync(sums.data, 0, (size_t)(4 * na) * 4, st));
+            VG_HIP_CHECK(hipMemsetAsync(nrec.data, 0, (size_t)(2 * na) * 4, st));
+            const int all[8] = {0, 8, 16, 24, 32, 40, 48, 56};
+            half = 0;
+            vk::launch_ba_iota(st, ids2.data, n);
+            for (int chunk = (int)(plan.wmax + 1 + 1) / 2 - 1; chunk >= 0; chunk--) {
+                vk::launch_ba_rekey(st, desc.data, (uint32_t)chunk, ids2.data + (uint64_t)half * n, cnt.data, keys + (uint64_t)half * n, n);
+                half = vk::launch_ba_sort(st, keys, ids2.data, n, sort_tmp.data, all, 8, half);
+            }
+            vk::launch_ba_groups(st, desc.data, keys + (uint64_t)half * n, ids2.data + (uint64_t)half * n, n, true, gid.data, head_pos.data, scan_tmp.data, counters.data);
+            vk::launch_ba_reduce(st, desc.data, ids2.data + (uint64_t)half * n, cnt.data, gid.data, head_pos.data, n, false, sums_p, nrec.data, counters.data);
+            c.check_launch("link_audit exact");
+            c.download_small(cw.data(), counters.data, n_counters * 4);
+        }
+        const uint32_t n_live = cw[0], n_groups = cw[1];
+        const uint32_t* ids = ids2.data + (uint64_t)half * n;
+        if (n_groups) VG_HIP_CHECK(hipMemsetAsync(tmask.data, 0xff, (size_t)n_groups * 4, st));
+        vk::launch_la_join(st, ids, mask.data, gid.data, n_live, tmask.data);
+        vk::launch_la_tally(st, desc.data, lt_dev.data, ids, mask.data, gid.data, head_pos.data, tmask.data, n_live, n_fields, (uint32_t)NB, (unsigned long long*)tally.data);
+        c.check_launch("link_audit join");
+        std::vector<uint32_t> tw((size_t)(2 * tally_words ? 2 * tally_words : 2));
+        c.download_small(tw.data(), tally.data, tw.size() * 4);
+        auto u64 = [&](uint64_t k) { return ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k]; };
+        for (size_t i = 0; i < NC; i++)
+            for (size_t m = 0; m < rep.chips[i].size(); m++) {
+                LinkInteractionStat& s = rep.chips[i][m];
+                s.live_rows = cw[8 + NB + inter_base[i] + m];
+                rep.buses[plan.chips[i].bus_slot[m]].live += s.live_rows;
+                const uint32_t slot = lt[lt[4 + i] + m];
+                for (uint32_t j = 0; j < s.n_fields; j++) { s.floating[j] = u64(slot + j); s.open[j] = u64((uint64_t)n_fields + slot + j); }
+            }
+        for (size_t b = 0; b < NB; b++) {
+            LinkBusStat& bs = rep.buses[b];
+            const uint64_t bb = 2ull * n_fields + 66ull * b;
+            bs.tuples = u64(bb); bs.open_tuples = u64(bb + 1);
+            for (uint32_t j = 0; j < bs.width; j++) { bs.open_in[j] = u64(bb + 2 + j); bs.open_records[j] = u64(bb + 34 + j); }
+            n_open += bs.open_tuples;
+        }
+        rep.total_open = n_open;
+        if (n_open) {
+            const uint32_t n_rep = (uint32_t)std::min<uint64_t>(n_open, o.max_tuples), R = o.max_records_per_tuple, stride = 8 + plan.wmax + 2 * R;
+            DBuf ukeys(&c, (size_t)(4 * n_open)), uvals(&c, (size_t)(2 * n_open)), out(&c, (size_t)n_rep * stride);
+            vk::launch_la_select(st, ids, head_pos.data, tmask.data, n_groups, (uint32_t)n_open, (unsigned long long*)ukeys.data, uvals.data, counters.data);
+            const int id_bytes[4] = {0, 8, 16, 24};  // keys are 32-bit record ids
+            const int uh = vk::launch_ba_sort(st, (unsigned long long*)ukeys.data, uvals.data, n_open, sort_tmp.data, id_bytes, 4, 0);
+            vk::launch_la_report(st, desc.data, ids, mask.data, head_pos.data, nrec.data, tmask.data, uvals.data + (uint64_t)uh * n_open, n_rep, R, out.data);
+            c.check_launch("link_audit report");
+            std::vector<uint32_t> w((size_t)n_rep * stride);
+            c.download_small(w.data(), out.data, w.size() * 4);
+            for (uint32_t t = 0; t < n_rep; t++) {
+                const uint32_t* e = w.data() + (size_t)t * stride;
+                const BusStat& bus = plan.buses.at(e[0]);
+                LinkTuple lk;
+                lk.is_global = bus.is_global; lk.bus_index = bus.bus_index; lk.mask = e[2];
+                lk.fields.assign(e + 8, e + 8 + bus.width);
+                lk.n_send = e[3]; lk.n_recv = e[4];
+                for (uint32_t k = 0; k < e[1] && k < R; k++) {
+                    const BusRecord r = plan.decode(e[8 + plan.wmax + 2 * k]);
+                    lk.records.push_back(LinkRecord{r.chip, r.row, r.interaction, machine_.airs[r.chip].interactions[r.interaction].is_send() ? 1u : 0u, e[8 + plan.wmax + 2 * k + 1]});
+                }
+                rep.tuples.push_back(std::move(lk));
+            }
+        }
+        VG_HIP_CHECK(hipEventRecord(ev1, st));
+        c.sync();
+        float ms_dev = 0;
+        if (hipEventElapsedTime(&ms_dev, ev0, ev1) == hipSuccess) rep.device_ms = ms_dev;
+    } catch (const BusAuditNoMemory&) {
+        throw;
+    } catch (const std::bad_alloc&) {
+        (void)hipStreamSynchronize(st);
+        throw BusAuditNoMemory("link_audit: the device pool cannot give the pass its scratch: 68 bytes for each of the " + std::to_string(n) + " (row, interaction) pairs (the bus audit's " +
+                               std::to_string(BUS_AUDIT_BYTES_PER_SLOT) + ", 4 for the record mask, 4 for the tuple mask: " + std::to_string(68 * n) + " bytes), " + std::to_string(8 * tally_words) +
+                               " bytes of tallies (16 per field, 528 per bus), " + std::to_string(wr_words * 4) + " bytes of interaction weight rows, 24 for each of the " + std::to_string(n_open) +
+                               " open tuples, plus the working-layout copies of uploaded traces");
+    }
+    link_audit_finish(rep, o);
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 // ---- coverage audit (host/coverage_audit.hpp; kernels/coverage_audit.hip) ------------------------------------------------------------------
 CoverageReport Prover::coverage_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
                                       const CoverageAuditOpts& opts_in) {

@@ -14,6 +14,7 @@
 #include "pair_audit.hpp"
 #include "rank_audit.hpp"
 #include "field_audit.hpp"
+#include "link_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -145,6 +146,10 @@ class Prover {
     // 24 bytes + 8 per interaction and field, 8 per (field, workgroup of rows), the interaction weight rows, 72 x max_rows_per_entry per listed
     // field slot of the chip with the most.
     FieldReport field_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const RankAuditOpts& opts);
+    // Link audit of a witness (host/link_audit.hpp, kernels/link_audit.hip): the field audit's float mask of every live record joined over the
+    // bus audit's tuples; the same trace handles as prove, queued on the context like a proof.  Throws std::invalid_argument for bad shapes, a
+    // bus wider than 32 fields and the field and bus audits' device limits; std::bad_alloc (VGPU_ERR_OOM) when the pool cannot give the scratch.
+    LinkReport link_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const LinkAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

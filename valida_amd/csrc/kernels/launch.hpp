@@ -294,6 +294,25 @@ void launch_fa_count(hipStream_t st, const FaArgs& a, unsigned long long* totals
 // slots below s_cut with a floating row are listed
 void launch_fa_scan(hipStream_t st, const FaArgs& a, const uint32_t* table, uint32_t* prefix, uint32_t s_cut);
 void launch_fa_list(hipStream_t st, const FaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t s_cut, uint32_t R, uint32_t* rows);
+// link_audit.hip — the passes of the link audit (host/link_audit.hpp: contract; Prover::link_audit drives them).  The mask pass runs per chip
+// with the field audit's arguments (FaArgs; la_shape fills T and NB: its workgroup head is smaller than the field audit's) and writes one word
+// per live record slot of `mask` [n] (zeroed); the records are grouped by the bus audit's launchers above; join, tally, select and report run
+// over its sorted ids / gid / head_pos / nrec.  tmask: [groups] u32, pre-set to all ones.  lt: [0] fields of the whole machine (NS), [4 + c]
+// where in lt chip c's interactions have their first field slots.  tally: la_tally_words u64, zeroed: [s] floating rows and [NS + s] open rows
+// of field slot s, then per bus slot 66 words: tuples, open tuples, [2 + j] tuples in which position j is open, [34 + j] the records of those.
+void la_shape(FaArgs& a);
+size_t la_lds_bytes(const FaArgs& a, uint32_t T);
+inline uint64_t la_tally_words(uint32_t n_fields, uint32_t n_buses) { return 2ull * n_fields + 66ull * n_buses; }
+void launch_la_masks(hipStream_t st, const FaArgs& a, uint32_t first_id, uint32_t* mask);
+void launch_la_join(hipStream_t st, const uint32_t* ids, const uint32_t* mask, const uint32_t* gid, uint32_t n_live, uint32_t* tmask);
+void launch_la_tally(hipStream_t st, const uint32_t* desc, const uint32_t* lt, const uint32_t* ids, const uint32_t* mask, const uint32_t* gid, const uint32_t* head_pos, const uint32_t* tmask,
+                     uint32_t n_live, uint32_t n_fields, uint32_t n_buses, unsigned long long* tally);
+// appends (first record id, group) of the open groups, at most cap; counters[4] is the cursor (zero before)
+void launch_la_select(hipStream_t st, const uint32_t* ids, const uint32_t* head_pos, const uint32_t* tmask, uint32_t n_groups, uint32_t cap, unsigned long long* ukeys, uint32_t* uvals,
+                      uint32_t* counters);
+// out: n_rep rows of 8 + widest bus + 2 R words (k_la_report states the layout)
+void launch_la_report(hipStream_t st, const uint32_t* desc, const uint32_t* ids, const uint32_t* mask, const uint32_t* head_pos, const uint32_t* nrec, const uint32_t* tmask,
+                      const uint32_t* uvals, uint32_t n_rep, uint32_t R, uint32_t* out);
 // coverage_audit.hip — the passes of the coverage audit (host/coverage_audit.hpp: contract; Prover::coverage_audit drives them), per chip.  The
 // evaluations are the mutation audit's (MaArgs; mutation_eval.hpp).  A CELL of a chip is ((detector * width + column) * D + delta index),
 // cells = (K + M) * width * D of them.  audit: wg_tables [GX][cells][4] u32 {kills, sole, ~first_row, ~first_sole_row} (zeroed), one table per
