@@ -716,6 +716,66 @@ const uint32_t* vgpu_link_report_words(const vgpu_link_report_t* r);
 void vgpu_link_report_timing(const vgpu_link_report_t* r, double out[3]);
 void vgpu_link_report_free(vgpu_link_report_t* r);
 
+/* ---- Step audit: finite steps along each row's null directions.  The rank audit ends at first order: a null vector of a row's Jacobian may be a
+ * real trade (a + b - c, limb trades) or the artefact of a quadratic constraint at a degenerate point (x^2 = 0 at x = 0).  The step audit takes
+ * the rank audit's canonical null vector v of every (row, loose column) and judges the finite moves M[r] + t v by the mutation audit's rule.
+ * Inputs: exactly what vgpu_rank_audit takes.  Chip h, main matrix M (height n, width w), row r:
+ *   directions   exactly the rank audit's: J_r, its RREF, loose / pinned / zero / coupled, the canonical null vector of each loose column; the
+ *                vector of a ZERO loose column is e_c.  Several columns may share a vector; results are per column.
+ *   move         loose column c with vector v, step index s, t = steps[s]: M' = M except M'[r][j] = M[r][j] + t v_j mod p for every j.
+ *                Preprocessed columns never move.
+ *   detected     the mutation audit's two rules on M'.  AIR: Air::eval at q = r and q = (r - 1) mod n on the constraint audit's domain; a
+ *                constraint that is non-zero there and was zero on M detects; n = 1 is one evaluation with the row as local and next at once;
+ *                permutation constraints are not evaluated.  Bus: a changed record detects — v annihilates the count row and, on live rows,
+ *                every field row, so it never does; the host audit evaluates it all the same and counts it, the device pass writes 0.
+ *   per cell     (row, loose column): pass mask, bit s = step s goes undetected.  EXACT: every step passes; CURVED: otherwise.
+ *   per chip     max_degree (the machine's max constraint degree) and line_exact = [n_steps >= max_degree]: along the line every constraint is
+ *                a polynomial in t of degree <= max_degree that is zero at t = 0 if it held; n_steps further zeros make it vanish
+ *                identically, so no constraint that holds now fails anywhere on the line of an exact cell.
+ * A listed exact row is a certificate: made on the trace, the move leaves vgpu_constraint_audit's and vgpu_bus_audit's reports as they were.
+ * What it is not: one row, THIS witness, moves along the canonical vectors only (not the whole null space); line_exact is about constraints that
+ * held; cross-row combinations are not looked for; `check`'s exit status never depends on it.
+ * Options: max_entries, max_rows_per_entry, chip_mask as vgpu_rank_audit_opts_t, same defaults and refusals; n_steps and steps: 1 to 4 distinct
+ * canonical values in 1..p-1, n_steps = 0 the default {1, p - 1, 2}; opts may be NULL; reserved != 0 is refused.
+ * vgpu_step_audit runs on the device (kernels/step_audit.hip: one wave per trace row, the rank audit's dual evaluation and LDS elimination, then
+ * ceil(nu S / 64) passes of plain evaluations, lane <-> (non-pivot column, step)), queued on the prover context; scratch from the pool: per chip
+ * 48 + 32 w bytes of totals, 8 w bytes per workgroup of rows, the interaction weight rows, 80 max_rows_per_entry bytes per column up to the last
+ * listed one; VGPU_ERR_OOM with the arithmetic when the pool cannot give them.  VGPU_ERR_INVALID_ARG for bad shapes, more than 192 columns, and a
+ * chip that does not fit 160 KB of LDS with one wave per workgroup: the rank audit's sum plus 4 x (2 w + 24 + ceil(2 K / 32)) bytes (two more
+ * per-column counters, the pass bits, the baseline bits).  vgpu_step_audit_host: the same contract on the host, one thread, no limits.
+ * Report image (vgpu_step_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x31525356 "VSR1" [1] word count [2] terms per listed row, always 8 [3] truncated [4,5] total_entries = (chip, column) with a
+ *   coupled-and-exact or a curved row (exact even when the list is cut) [6] reported [7] n_chips [8] n_steps [9] 0 [10..13] steps, unused 0
+ *   per chip, in machine order, 30 + 8 w words: width, constraints, interactions, audited (0 / 1), height (u64), max_degree, line_exact, then u64
+ *   each: loose cells, zero cells, exact cells, coupled-and-exact cells (sums over rows and columns), confirmed rows (a coupled-and-exact
+ *   column), refuted rows (a curved column), passes of step 0..3 ((row, loose column) cells), bus-detected (0); then per column c, u64 each:
+ *   loose rows, zero rows, exact rows, coupled-and-exact rows
+ *   per reported entry (ascending (chip, column)): chip, column, n_listed, 0, coupled-and-exact rows (u64), curved rows (u64), then n_listed rows
+ *   of 20 words — the first max_rows_per_entry rows, ascending, where the column is loose and (not zero, or curved); zero-and-exact rows (the
+ *   mutation audit's free cells) are counted and never listed: row, pass mask, zero (0 / 1), n_support (exact), then the first 8 (column,
+ *   coefficient) terms of the vector in ascending column order, unused slots 0. */
+typedef struct vgpu_step_audit_opts {
+    uint64_t max_entries;
+    uint32_t max_rows_per_entry;
+    uint32_t chip_mask;
+    uint32_t n_steps;
+    uint32_t steps[4];
+    uint32_t reserved[3];
+} vgpu_step_audit_opts_t;
+typedef struct vgpu_step_report vgpu_step_report_t;
+int32_t vgpu_step_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                        uint32_t n_prep, const vgpu_step_audit_opts_t* opts, vgpu_step_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_step_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                             const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                             const vgpu_step_audit_opts_t* opts, vgpu_step_report_t** out);
+uint64_t vgpu_step_report_len(const vgpu_step_report_t* r);
+const uint32_t* vgpu_step_report_words(const vgpu_step_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: row evaluations (the rank
+ * audit's dual ones plus the plain ones of the moves) */
+void vgpu_step_report_timing(const vgpu_step_report_t* r, double out[3]);
+void vgpu_step_report_free(vgpu_step_report_t* r);
+
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
  *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct

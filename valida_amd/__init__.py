@@ -1435,6 +1435,144 @@ def rank_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max_
     return _rank_report(h)
 
 
+class StepAuditOpts(ctypes.Structure):  # vgpu_step_audit_opts_t
+    _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("n_steps", ctypes.c_uint32),
+                ("steps", ctypes.c_uint32 * 4), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class StepReport:
+    """The step audit of a witness (vgpu_step_audit / vgpu_step_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
+    steps (canonical), truncated, total_entries ((chip, column) with a coupled-and-exact or a curved row), reported,
+    chips = [dict(chip, width, constraints, interactions, audited, height, max_degree, line_exact, loose_cells, zero_cells, exact_cells,
+    coupled_exact_cells, confirmed_rows, refuted_rows, passes=[cells per step], bus, loose / zeros / exact / coupled_exact=[rows per column])],
+    entries = [dict(chip, column, coupled_exact, curved, rows=[dict(row, pass_mask, zero, exact, n_support, terms=[(column, coefficient)])])]
+    ascending by (chip, column), device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations.
+    One row, THIS witness, the canonical null vectors only: not a soundness proof."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 14 or w[0] != 0x31525356 or w[1] != len(w) or w[2] != 8 or not 1 <= w[8] <= 4:
+            raise ValueError("not a step report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.truncated = bool(w[3])
+        self.total_entries, self.reported = w[4] | (w[5] << 32), w[6]
+        self.steps = w[10:10 + w[8]]
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+        S, full = len(self.steps), (1 << len(self.steps)) - 1
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 14
+        self.chips = []
+        for c in range(w[7]):
+            wd = w[pos]
+            self.chips.append(dict(chip=c, width=wd, constraints=w[pos + 1], interactions=w[pos + 2], audited=bool(w[pos + 3]), height=u64(pos + 4), max_degree=w[pos + 6],
+                                   line_exact=bool(w[pos + 7]), loose_cells=u64(pos + 8), zero_cells=u64(pos + 10), exact_cells=u64(pos + 12), coupled_exact_cells=u64(pos + 14),
+                                   confirmed_rows=u64(pos + 16), refuted_rows=u64(pos + 18), passes=[u64(pos + 20 + 2 * s) for s in range(S)], bus=u64(pos + 28),
+                                   loose=[u64(pos + 30 + 8 * k) for k in range(wd)], zeros=[u64(pos + 32 + 8 * k) for k in range(wd)],
+                                   exact=[u64(pos + 34 + 8 * k) for k in range(wd)], coupled_exact=[u64(pos + 36 + 8 * k) for k in range(wd)]))
+            pos += 30 + 8 * wd
+        self.entries = []
+        for _ in range(self.reported):
+            rows = []
+            for k in range(w[pos + 2]):
+                at = pos + 8 + 20 * k
+                rows.append(dict(row=w[at], pass_mask=w[at + 1], zero=bool(w[at + 2]), exact=w[at + 1] == full, n_support=w[at + 3],
+                                 terms=[(w[at + 4 + 2 * i], w[at + 5 + 2 * i]) for i in range(min(8, w[at + 3]))]))
+            self.entries.append(dict(chip=w[pos], column=w[pos + 1], coupled_exact=u64(pos + 4), curved=u64(pos + 6), rows=rows))
+            pos += 8 + 20 * w[pos + 2]
+        assert pos == len(w)
+
+    def confirmed_columns(self, chip):
+        """The columns of `chip` that are coupled and exact on some row: a finite trade every check accepts (exact, from the per-column counts)."""
+        return [k for k, n in enumerate(self.chips[chip]["coupled_exact"]) if n]
+
+    def refuted_columns(self, chip):
+        """The columns of `chip` that are curved on some row: loose to first order, caught at some step."""
+        c = self.chips[chip]
+        return [k for k in range(c["width"]) if c["loose"][k] > c["exact"][k]]
+
+    def apply(self, main_traces, entry, listed_row, step):
+        """A copy of the chip's trace with the move of entry['rows'][listed_row] made at step index `step`: M[r] + steps[step] v.  Only when the
+        vector is listed whole (support <= 8 terms)."""
+        row = entry["rows"][listed_row]
+        if row["n_support"] > len(row["terms"]):
+            raise VgpuError(-1, "step_audit: the vector of chip %d column %d row %d is cut (%d terms, %d listed): it cannot be applied" %
+                            (entry["chip"], entry["column"], row["row"], row["n_support"], len(row["terms"])))
+        t = self.steps[step]
+        out = np.array(main_traces[entry["chip"]], dtype=np.uint32, copy=True)
+        for col, coef in row["terms"]:
+            out[row["row"], col] = (int(out[row["row"], col]) % P + t * coef) % P
+        return out
+
+    def to_dict(self):
+        return dict(steps=self.steps, truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
+                    evaluations=self.evaluations, chips=self.chips, entries=self.entries)
+
+    def to_json(self):
+        import json
+
+        return json.dumps(self.to_dict())
+
+
+def _step_opts(steps, max_entries, max_rows_per_entry, chips):
+    if int(max_entries) < 1 or int(max_rows_per_entry) < 1:
+        raise VgpuError(-1, "step_audit: max_entries and max_rows_per_entry must be at least 1")
+    mask = 0
+    if chips is not None:
+        cs = [int(c) for c in chips]
+        if not cs or any(c < 0 or c > 31 for c in cs):
+            raise VgpuError(-1, "step_audit: chips is a non-empty list of chip indices below 32")
+        for c in cs:
+            mask |= 1 << c
+    st = [] if steps is None else [int(x) for x in steps]
+    if steps is not None and not 1 <= len(st) <= 4:
+        raise VgpuError(-1, "step_audit: 1 to 4 steps (got %d)" % len(st))
+    if any(x < 0 or x >= 1 << 32 for x in st):
+        raise VgpuError(-1, "step_audit: a step must be a canonical value in 1..p-1")
+    return StepAuditOpts(int(max_entries), int(max_rows_per_entry), mask, len(st), (ctypes.c_uint32 * 4)(*st), (ctypes.c_uint32 * 3)(0, 0, 0))
+
+
+def _step_report(h):
+    L = lib()
+    L.vgpu_step_report_len.restype = ctypes.c_uint64
+    L.vgpu_step_report_words.restype = c_u32p
+    L.vgpu_step_report_len.argtypes = L.vgpu_step_report_words.argtypes = L.vgpu_step_report_free.argtypes = [ctypes.c_void_p]
+    L.vgpu_step_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    try:
+        n = int(L.vgpu_step_report_len(h))
+        words = np.ctypeslib.as_array(L.vgpu_step_report_words(h), shape=(n,)).copy()
+        tm = (ctypes.c_double * 3)()
+        L.vgpu_step_report_timing(h, tm)
+    finally:
+        L.vgpu_step_report_free(h)
+    return StepReport(words, tm[0], tm[1], tm[2])
+
+
+def step_audit_host(machine, main_matrices, preprocessed, steps=None, max_entries=1024, max_rows_per_entry=4, chips=None):
+    """The step audit on the HOST (vgpu_step_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
+    [(chip index, matrix)], steps = 1 to 4 distinct canonical values in 1..p-1 (default 1, p - 1, 2), chips = the chip indices to audit
+    (default: all); a StepReport back."""
+    opts = _step_opts(steps, max_entries, max_rows_per_entry, chips)
+    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
+    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
+    for m in mains + [m for _, m in preps]:
+        if m.ndim != 2:
+            raise VgpuError(-1, "step_audit: traces are two-dimensional matrices")
+
+    def arrays(ms):
+        n = max(1, len(ms))
+        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
+
+    mp, mh, mw = arrays(mains)
+    pp, ph, pw = arrays([m for _, m in preps])
+    chip_ids = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
+    h = ctypes.c_void_p()
+    _check(lib().vgpu_step_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chip_ids, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
+    return _step_report(h)
+
+
 class FieldReport:
     """The field audit of a witness (vgpu_field_audit / vgpu_field_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
     truncated, total_entries ((chip, interaction, field) with a floating row), reported,
@@ -2070,6 +2208,18 @@ class Prover:
         h = ctypes.c_void_p()
         _check(lib().vgpu_rank_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
         return _rank_report(h)
+
+    def step_audit(self, main, preprocessed, steps=None, max_entries=1024, max_rows_per_entry=4, chips=None):
+        """Finite steps along each row's null directions (vgpu_step_audit): the rank audit's canonical null vector of every (row, loose column),
+        moved by each step and judged by the mutation audit's rule; the arguments of prove, steps = 1 to 4 distinct canonical values (default 1,
+        p - 1, 2), chips = the chip indices to audit (default: all); a StepReport back."""
+        opts = _step_opts(steps, max_entries, max_rows_per_entry, chips)
+        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
+        chip_ids = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
+        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_step_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
+        return _step_report(h)
 
     def field_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
         """Which fields of the chips' bus records this witness's constraints leave undetermined (vgpu_field_audit): per row and live record,

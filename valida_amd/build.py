@@ -31,6 +31,7 @@ SOURCES = [
     "kernels/rank_audit.hip",
     "kernels/field_audit.hip",
     "kernels/link_audit.hip",
+    "kernels/step_audit.hip",
     "host/prover.cpp",
     "host/sharded_prover.cpp",
     "capi.cpp",

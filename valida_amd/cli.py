@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -70,6 +70,14 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         the same row are not held fixed), so "open" means that no single record's own chip pins the position — a joint move may still be blocked
         by a sister record; "anchored" is per tuple as it stands: a lookup bus whose receiver can move multiplicities between tuples is not
         modelled.  The exit status does not depend on this flag.
+        --steps adds the step audit of the same witness (vgpu_step_audit: the rank audit's canonical null vector of every (row, loose column),
+        moved by finite steps and judged by the mutation audit's rule — which first-order freedoms are real trades every check accepts, and
+        which are artefacts of a quadratic constraint at a degenerate point), on the same path (device or --host), restricted by the same
+        --chips; --step-sizes=1,-1,2 names 1 to 4 distinct step sizes (integers mod p; default 1,-1,2).  The JSON report gets one more key,
+        "steps" (StepReport.to_json's object); stdout gets one line per chip that has a confirmed or refuted column, `add: confirmed columns
+        0-7, 11-14 on 23 rows (whole lines: degree 3 <= 3 steps); refuted columns 5-8 on 72 rows` (a half with nothing to say is omitted; the
+        parenthesis only when the steps are enough for the chip's constraint degree).  One row, THIS witness, the canonical vectors only: the
+        exit status does not depend on this flag.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -253,6 +261,26 @@ def rank_lines(report, limit=16):
     return lines
 
 
+def step_lines(report):
+    """One line per chip of a step report that has a confirmed (coupled and exact) or a refuted (curved) column."""
+    import valida_amd as va
+
+    lines = []
+    for c in report.chips:
+        conf, ref = report.confirmed_columns(c["chip"]), report.refuted_columns(c["chip"])
+        if not conf and not ref:
+            continue
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        parts = []
+        if conf:
+            whole = " (whole lines: degree %d <= %d steps)" % (c["max_degree"], len(report.steps)) if c["line_exact"] else ""
+            parts.append("confirmed columns %s on %d rows%s" % (index_ranges(conf), c["confirmed_rows"], whole))
+        if ref:
+            parts.append("refuted columns %s on %d rows" % (index_ranges(ref), c["refuted_rows"]))
+        lines.append("%s: %s" % (name, "; ".join(parts)))
+    return lines
+
+
 def field_lines(report):
     """One line per (chip, interaction) of a field report with a floating field: the bus, the fields, the most rows one of them floats on."""
     import valida_amd as va
@@ -353,7 +381,10 @@ def main(argv=None):
                     "first order on this witness; a floating field on a send usually means the chip delegates; never changes the exit status)")
     ap.add_argument("--links", action="store_true", help="check: also the link audit (the bus tuple positions that float at every record of the tuple, send or receive: "
                     "no chip on the bus pins them; first order, on this witness, each record judged alone; never changes the exit status)")
-    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
+    ap.add_argument("--steps", action="store_true", help="check: also the step audit (finite steps along each row's null directions: which of the rank audit's "
+                    "freedoms are trades every check accepts, which are first-order artefacts; never changes the exit status)")
+    ap.add_argument("--step-sizes", default="1,-1,2", help="check --steps: 1 to 4 distinct step sizes, comma-separated integers mod p (as --step-sizes=1,-1,2)")
+    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields / --steps: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -387,6 +418,7 @@ def main(argv=None):
                 rreport = va.rank_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.rank else None
                 freport = va.field_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.fields else None
                 lreport = va.link_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_tuples=args.max_tuples, max_records_per_tuple=args.max_records) if args.links else None
+                sreport = va.step_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), steps=parse_deltas(args.step_sizes), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.steps else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -400,6 +432,7 @@ def main(argv=None):
                 rreport = prover.rank_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips)) if args.rank else None
                 freport = prover.field_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips)) if args.fields else None
                 lreport = prover.link_audit(main, prep, max_tuples=args.max_tuples, max_records_per_tuple=args.max_records) if args.links else None
+                sreport = prover.step_audit(main, prep, steps=parse_deltas(args.step_sizes), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.steps else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -415,12 +448,14 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), fields=freport.to_dict()))
             if lreport is not None:
                 text = json.dumps(dict(json.loads(text), links=lreport.to_dict()))
+            if sreport is not None:
+                text = json.dumps(dict(json.loads(text), steps=sreport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
                     coverage_lines(kreport) if kreport is not None else []) + (pair_lines(preport) if preport is not None else []) + (
                     rank_lines(rreport) if rreport is not None else []) + (field_lines(freport) if freport is not None else []) + (
-                    link_lines(lreport) if lreport is not None else []):
+                    link_lines(lreport) if lreport is not None else []) + (step_lines(sreport) if sreport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

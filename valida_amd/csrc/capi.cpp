@@ -55,6 +55,7 @@ struct vgpu_pair_report { std::vector<uint32_t> words; double device_ms = 0, hos
 struct vgpu_rank_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
 struct vgpu_field_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
 struct vgpu_link_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
+struct vgpu_step_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
 struct vgpu_comm { std::shared_ptr<Prover> owner; std::unique_ptr<Comm> comm; };  // owner first: the communicator dies before its context
 static_assert(sizeof(vgpu_cpu_op_t) == sizeof(vk::TgCpuOp) && sizeof(vgpu_mem_op_t) == sizeof(vk::TgMemOp) && sizeof(vgpu_alu_op_t) == sizeof(vk::TgAluOp),
               "C ABI log records and their device images must match");
@@ -1171,6 +1172,55 @@ uint64_t vgpu_link_report_len(const vgpu_link_report_t* r) { return r ? r->words
 const uint32_t* vgpu_link_report_words(const vgpu_link_report_t* r) { return r ? r->words.data() : nullptr; }
 void vgpu_link_report_timing(const vgpu_link_report_t* r, double out[3]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; out[2] = r ? r->evaluations : 0; }
 void vgpu_link_report_free(vgpu_link_report_t* r) { delete r; }
+
+// ---- step audit (host/step_audit.hpp) ----
+static_assert(sizeof(vgpu_step_audit_opts_t) == 48, "vgpu_step_audit_opts_t has no padding");
+static StepAuditOpts step_opts(const vgpu_step_audit_opts_t* o) {
+    StepAuditOpts r;  // a null pointer or a zero field: the default
+    if (o) {
+        r.max_entries = o->max_entries; r.max_rows_per_entry = o->max_rows_per_entry; r.chip_mask = o->chip_mask; r.n_steps = o->n_steps;
+        for (uint32_t i = 0; i < SA_MAX_STEPS; i++) r.steps[i] = o->steps[i];
+        for (uint32_t i = 0; i < 3; i++) r.reserved[i] = o->reserved[i];
+    }
+    return r;
+}
+static vgpu_step_report* step_report_handle(const StepReport& rep) {
+    auto h = std::make_unique<vgpu_step_report>();
+    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms; h->evaluations = rep.evaluations;
+    return h.release();
+}
+int32_t vgpu_step_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                        uint32_t n_prep, const vgpu_step_audit_opts_t* opts, vgpu_step_report_t** out) {
+    VG_TRY({
+        if (!p || !out || (n_main && !main) || (n_prep && (!prep || !prep_chips))) throw std::invalid_argument("null argument");
+        std::vector<const DeviceTrace*> m;
+        std::vector<std::shared_ptr<Prover>> foreign;
+        for (uint32_t i = 0; i < n_main; i++) { check_trace(p, main[i], &foreign); m.push_back(main[i]->t.get()); }
+        std::vector<std::pair<int, const DeviceTrace*>> pr;
+        for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &foreign); pr.push_back({(int)prep_chips[i], prep[i]->t.get()}); }
+        drain(foreign);
+        *out = step_report_handle(p->p->step_audit(m, pr, step_opts(opts)));
+    })
+}
+int32_t vgpu_step_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                             const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                             const vgpu_step_audit_opts_t* opts, vgpu_step_report_t** out) {
+    VG_TRY({
+        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
+        const auto t0 = std::chrono::steady_clock::now();
+        std::vector<ConstraintHostMatrix> m, pm;
+        std::vector<int> chips;
+        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
+        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
+        StepReport rep = step_audit_host(machine->desc, m, chips, pm, step_opts(opts));
+        rep.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        *out = step_report_handle(rep);
+    })
+}
+uint64_t vgpu_step_report_len(const vgpu_step_report_t* r) { return r ? r->words.size() : 0; }
+const uint32_t* vgpu_step_report_words(const vgpu_step_report_t* r) { return r ? r->words.data() : nullptr; }
+void vgpu_step_report_timing(const vgpu_step_report_t* r, double out[3]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; out[2] = r ? r->evaluations : 0; }
+void vgpu_step_report_free(vgpu_step_report_t* r) { delete r; }
 
 // ---- coverage audit (host/coverage_audit.hpp) ----
 static_assert(sizeof(vgpu_coverage_audit_opts_t) == 40, "vgpu_coverage_audit_opts_t has no padding");

@@ -1912,6 +1912,169 @@ RankReport Prover::rank_audit(const std::vector<const DeviceTrace*>& main, const
     return rep;
 }
 
+// ---- step audit (host/step_audit.hpp; kernels/step_audit.hip) ------------------------------------------------------------------------------
+StepReport Prover::step_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const StepAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const StepAuditOpts o = step_audit_checked_opts(opts_in, machine_.airs.size());
+    std::vector<ConstraintShape> ms, ps;
+    std::vector<int> prep_chips, prep_slot;
+    for (auto t : main) { if (!t) throw std::invalid_argument("step_audit: null trace"); ms.push_back({t->height, t->width}); }
+    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("step_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
+    step_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
+    const size_t NC = machine_.airs.size();
+    const uint32_t R = o.max_rows_per_entry;
+    // per chip its launch shape: a chip that does not fit the LDS is refused before anything is queued
+    std::vector<vk::SaArgs> sargs(NC);
+    StepReport rep;
+    rep.chips.resize(NC);
+    for (size_t i = 0; i < NC; i++) {
+        const AirDesc& air = machine_.airs[i];
+        sargs[i] = vk::SaArgs{};
+        vk::RaArgs& a = sargs[i].r;
+        sargs[i].n_steps = o.n_steps;
+        for (uint32_t s = 0; s < SA_MAX_STEPS; s++) sargs[i].steps[s] = vg::Fp::from_canonical(o.steps[s]).v;
+        StepChipStat& cs = rep.chips[i];
+        step_audit_chip_block(cs, air, main[i]->height, step_audit_selected(o, i), o.n_steps);
+        if (!cs.audited || !air.width) continue;
+        a.K = air.program.num_asserts;
+        a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
+        a.n_instrs = (uint32_t)air.program.instrs.size();
+        a.n_regs = air.program.num_regs;
+        a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
+        try {
+            vk::sa_shape(sargs[i]);
+        } catch (const std::invalid_argument& e) {
+            throw std::invalid_argument(std::string(e.what()) + " [chip " + air.name + "; the host audit has no limit]");
+        }
+        // dual evaluations, and at most one plain evaluation per (column, step) and q
+        a.evaluations = a.K ? (double)a.n * a.width * (a.n == 1 ? 1 : 2) * (1 + o.n_steps) : 0;
+        rep.evaluations += a.evaluations;
+    }
+
+    DeviceCtx& c = *ctx_;
+    c.activate();
+    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
+    c.activate();
+    struct Running {
+        std::atomic<int>& n;
+        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
+        ~Running() { n.fetch_sub(1); }
+    } running(c.proofs_running);
+    hipStream_t st = c.stream;
+
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
+    VG_HIP_CHECK(hipEventCreate(&ev0));
+    VG_HIP_CHECK(hipEventCreate(&ev1));
+    uint64_t scratch_words = 0, rows_words = 0, desc_words_n = 0;
+    try {
+        std::vector<DMat> own;
+        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
+            if (!t->nat.empty()) return t->nat.view();
+            own.emplace_back(&c, t->height, t->width);
+            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
+            return own.back().view();
+        };
+        own.reserve(NC + preprocessed.size());
+        // per chip: its weight rows and its slice of the scratch (u32 words): totals, table [w NB], prefix [w NB]
+        std::vector<uint64_t> tot_at(NC, 0), tab_at(NC, 0), pre_at(NC, 0), wr_at(NC, 0);
+        std::vector<uint32_t> desc_words;
+        uint64_t zeroed = 0;
+        for (size_t i = 0; i < NC; i++) {
+            vk::RaArgs& a = sargs[i].r;
+            if (!a.width) continue;
+            const AirDesc& air = machine_.airs[i];
+            const vk::DMatView mv = working(main[i]);
+            a.main = mv.data; a.mstride = mv.stride;
+            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
+            a.prog = (const vair::Instr*)prog_dev_[i].data;
+            a.iw = iw_dev_[i].data;
+            const std::vector<uint32_t> wr = ra_weight_rows(air);
+            wr_at[i] = desc_words.size();
+            desc_words.insert(desc_words.end(), wr.begin(), wr.end());
+            tot_at[i] = zeroed; zeroed += vk::sa_totals_words(sargs[i]);
+            tab_at[i] = zeroed; zeroed += ((uint64_t)a.width * a.NB + 1) & ~1ull;  // the next chip's u64 totals stay 8-byte aligned
+        }
+        scratch_words = zeroed;
+        for (size_t i = 0; i < NC; i++) if (sargs[i].r.width) { pre_at[i] = scratch_words; scratch_words += (uint64_t)sargs[i].r.width * sargs[i].r.NB; }
+        if (desc_words.empty()) desc_words.push_back(0);
+        desc_words_n = desc_words.size();
+        DBuf desc(&c, desc_words);
+        for (size_t i = 0; i < NC; i++) sargs[i].r.wr = desc.data + wr_at[i];
+        c.check_launch("step_audit ingest");
+        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
+        // the device pass: everything from here to the last download is between the two events
+        VG_HIP_CHECK(hipEventRecord(ev0, st));
+        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)zeroed * 4, st));
+        for (size_t i = 0; i < NC; i++)
+            if (sargs[i].r.width) vk::launch_sa_count(st, sargs[i], reinterpret_cast<unsigned long long*>(scratch.data + tot_at[i]), scratch.data + tab_at[i]);
+        c.check_launch("step_audit count");
+        {
+            std::vector<uint32_t> tw;
+            for (size_t i = 0; i < NC; i++) {
+                if (!sargs[i].r.width) continue;
+                StepChipStat& cs = rep.chips[i];
+                tw.resize(vk::sa_totals_words(sargs[i]));
+                c.download_small(tw.data(), scratch.data + tot_at[i], tw.size() * 4);
+                auto u64 = [&](size_t k) { return ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k]; };
+                cs.confirmed_rows = u64(0); cs.refuted_rows = u64(1);
+                for (uint32_t s = 0; s < SA_MAX_STEPS; s++) cs.passes[s] = u64(2 + s);
+                for (uint32_t k = 0; k < cs.width; k++) {
+                    cs.loose[k] = u64(6 + 4 * (size_t)k); cs.zeros[k] = u64(7 + 4 * (size_t)k); cs.exact[k] = u64(8 + 4 * (size_t)k); cs.coupled_exact[k] = u64(9 + 4 * (size_t)k);
+                }
+            }
+        }
+        step_audit_finish(rep, o);
+        for (size_t e0 = 0; e0 < rep.entries.size();) {
+            const uint32_t chip = rep.entries[e0].chip;
+            size_t e1 = e0;
+            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
+            rows_words = std::max<uint64_t>(rows_words, ((uint64_t)rep.entries[e1 - 1].column + 1) * R * SA_ROW_WORDS);
+            e0 = e1;
+        }
+        DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
+        for (size_t e0 = 0; e0 < rep.entries.size();) {
+            // the listed columns of one chip: scan, list, one download
+            const uint32_t chip = rep.entries[e0].chip;
+            size_t e1 = e0;
+            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
+            const vk::SaArgs& sa = sargs[chip];
+            const uint32_t c_cut = rep.entries[e1 - 1].column + 1;  // entries ascend: the listed columns of a chip are below it
+            const size_t words = (size_t)c_cut * R * SA_ROW_WORDS;
+            VG_HIP_CHECK(hipMemsetAsync(out.data, 0, words * 4, st));  // unused term slots are zero
+            vk::launch_ra_scan(st, sa.r, scratch.data + tab_at[chip], scratch.data + pre_at[chip], c_cut);
+            vk::launch_sa_list(st, sa, scratch.data + tab_at[chip], scratch.data + pre_at[chip], c_cut, R, out.data);
+            c.check_launch("step_audit list");
+            std::vector<uint32_t> w(words);
+            c.download_small(w.data(), out.data, w.size() * 4);
+            for (size_t e = e0; e < e1; e++) {
+                StepEntry& en = rep.entries[e];
+                const uint64_t listed = std::min<uint64_t>(en.coupled_exact + en.curved, R);
+                en.rows.resize((size_t)listed);
+                for (size_t k = 0; k < listed; k++) {
+                    const uint32_t* src = w.data() + ((size_t)en.column * R + k) * SA_ROW_WORDS;
+                    en.rows[k].row = src[0]; en.rows[k].pass_mask = src[1]; en.rows[k].zero = src[2]; en.rows[k].n_support = src[3];
+                    for (uint32_t x = 0; x < 2 * RA_TERMS; x++) en.rows[k].terms[x] = src[4 + x];
+                }
+            }
+            e0 = e1;
+        }
+        VG_HIP_CHECK(hipEventRecord(ev1, st));
+        c.sync();
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
+    } catch (const BusAuditNoMemory&) {
+        throw;
+    } catch (const std::bad_alloc&) {
+        (void)hipStreamSynchronize(st);
+        throw BusAuditNoMemory("step_audit: the device pool cannot give the pass its scratch: 48 + 32 bytes per column of totals and 8 per (column, workgroup of rows) of every chip (" +
+                               std::to_string(scratch_words * 4) + " bytes for this witness), " + std::to_string(desc_words_n * 4) + " bytes of interaction weight rows, " + std::to_string(rows_words * 4) +
+                               " bytes of listed rows (80 per (listed column, row slot)), plus the working-layout copies of uploaded traces; chip_mask audits fewer chips at a time");
+    }
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 // ---- field audit (host/field_audit.hpp; kernels/field_audit.hip) ---------------------------------------------------------------------------
 FieldReport Prover::field_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const RankAuditOpts& opts_in) {
     const auto t_host = Clock::now();

@@ -15,6 +15,7 @@
 #include "rank_audit.hpp"
 #include "field_audit.hpp"
 #include "link_audit.hpp"
+#include "step_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -150,6 +151,9 @@ class Prover {
     // bus audit's tuples; the same trace handles as prove, queued on the context like a proof.  Throws std::invalid_argument for bad shapes, a
     // bus wider than 32 fields and the field and bus audits' device limits; std::bad_alloc (VGPU_ERR_OOM) when the pool cannot give the scratch.
     LinkReport link_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const LinkAuditOpts& opts);
+    // Step audit of a witness (host/step_audit.hpp, kernels/step_audit.hip): finite steps along the rank audit's canonical null vectors, judged by the
+    // mutation audit's rule; queued on the context like the other audits, scratch from the pool.
+    StepReport step_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const StepAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

@@ -24,6 +24,7 @@
 // host implementation (plain C++, one thread, no limits).  The device pass is Prover::rank_audit (prover.cpp, kernels/rank_audit.hip).
 #pragma once
 #include <chrono>
+#include <functional>
 #include "mutation_audit.hpp"
 
 namespace vhost {
@@ -218,9 +219,11 @@ inline void rank_audit_finish(RankReport& r, const RankAuditOpts& o) {
 }
 
 // The contract on the host: a dual-number (value, derivative) evaluation of the chip's Program seeded at one (column, role), the interaction
-// rows from the VirtualCol weights, RREF by row insertion; one thread.
+// rows from the VirtualCol weights, RREF by row insertion; one thread.  per_row (optional) sees the reduced basis of every audited row, in
+// (chip, row) order, right after the row's own analysis: the step audit (host/step_audit.hpp) takes its directions there.
+using RankRowFn = std::function<void(size_t chip, uint64_t row, const RankBasis& basis)>;
 inline RankReport rank_audit_host(const MachineDesc& machine, const std::vector<ConstraintHostMatrix>& main, const std::vector<int>& prep_chips,
-                                  const std::vector<ConstraintHostMatrix>& prep, const RankAuditOpts& opts_in) {
+                                  const std::vector<ConstraintHostMatrix>& prep, const RankAuditOpts& opts_in, const RankRowFn& per_row = nullptr) {
     const RankAuditOpts o = rank_audit_checked_opts(opts_in, machine.airs.size());
     std::vector<ConstraintShape> ms, ps;
     for (auto& m : main) { if (!m.data) throw std::invalid_argument("rank_audit: null trace"); ms.push_back({m.height, m.width}); }
@@ -314,6 +317,7 @@ inline RankReport rank_audit_host(const MachineDesc& machine, const std::vector<
                 if (!B.nonzero[col]) { cs.zeros[col]++; continue; }
                 if (first[c][col].size() < R) first[c][col].push_back(B.null_vector(col, (uint32_t)r));
             }
+            if (per_row) per_row(c, r, B);
         }
     }
     rank_audit_finish(rep, o);

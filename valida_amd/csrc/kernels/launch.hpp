@@ -264,6 +264,19 @@ void launch_ra_count(hipStream_t st, const RaArgs& a, unsigned long long* totals
 // columns below c_cut with a coupled row are listed
 void launch_ra_scan(hipStream_t st, const RaArgs& a, const uint32_t* table, uint32_t* prefix, uint32_t c_cut);
 void launch_ra_list(hipStream_t st, const RaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t c_cut, uint32_t R, uint32_t* rows);
+// step_audit.hip — the passes of the step audit (host/step_audit.hpp: contract; Prover::step_audit drives them), per chip: the rank audit's launch
+// shape and inputs plus the steps (Montgomery).  totals: u64 [0] confirmed rows, [1] refuted rows, [2 + s] passes of step s, then per column
+// [6 + 4 c] loose, zero, exact, coupled-and-exact rows (all zeroed); table / prefix: [width][NB] u32 listable rows of the column per workgroup and
+// their exclusive prefix (table zeroed; the scan is launch_ra_scan); rows: [width][R][20] u32 (zeroed).
+struct SaArgs {
+    RaArgs r;  // evaluations: dual plus plain row evaluations at most
+    uint32_t n_steps, steps[4];
+};
+inline uint64_t sa_totals_words(const SaArgs& a) { return 2 * (6ull + 4ull * a.r.width); }  // u32 words of the u64 totals
+void sa_shape(SaArgs& a);  // ra_shape for this audit's LDS; throws std::invalid_argument when the chip does not fit
+size_t sa_lds_bytes(const SaArgs& a, uint32_t NW, uint32_t T);
+void launch_sa_count(hipStream_t st, const SaArgs& a, unsigned long long* totals, uint32_t* table);
+void launch_sa_list(hipStream_t st, const SaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t c_cut, uint32_t R, uint32_t* rows);
 // field_audit.hip — the passes of the field audit (host/field_audit.hpp: contract; Prover::field_audit drives them), per chip.  One wave per
 // trace row, one wave per workgroup, T rows per workgroup one after the other, NB workgroups.  A SLOT of a chip is (interaction, field) in
 // order, NS of them.  totals: u64 [0] live records, [1] floating fields, [2] rows with a floating field, [3 + m] live rows of interaction m,
