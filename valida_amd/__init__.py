@@ -921,6 +921,64 @@ def prove_sharded_local(provers, main_traces, preprocessed, log_min_sharded=12, 
     return Proof(h)
 
 
+# ---- the witness audits.  Each has its options, its report class and its public functions below; what they share is here.
+class _AuditReport:
+    def to_json(self):
+        import json
+
+        return json.dumps(self.to_dict())
+
+
+def _chip_mask(name, chips):
+    """chips (None: every chip) as the chip_mask of the options of `name`_audit; refused here, with the library's status code."""
+    mask = 0
+    if chips is not None:
+        cs = [int(c) for c in chips]
+        if not cs or any(c < 0 or c > 31 for c in cs):
+            raise VgpuError(-1, "%s_audit: chips is a non-empty list of chip indices below 32" % name)
+        for c in cs:
+            mask |= 1 << c
+    return mask
+
+
+def _audit_report(name, cls, h):
+    """The handle h of a vgpu_`name`_report_t as a `cls`, and the handle freed."""
+    L = lib()
+    length, words_of, timing, free = (getattr(L, "vgpu_%s_report_%s" % (name, f)) for f in ("len", "words", "timing", "free"))
+    length.restype = ctypes.c_uint64
+    words_of.restype = c_u32p
+    length.argtypes = words_of.argtypes = free.argtypes = [ctypes.c_void_p]
+    timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    try:
+        words = np.ctypeslib.as_array(words_of(h), shape=(int(length(h)),)).copy()
+        tm = (ctypes.c_double * (2 if name in ("bus", "constraint") else 3))()  # device_ms, host_ms and, but for these two, evaluations
+        timing(h, tm)
+    finally:
+        free(h)
+    return cls(words, *tm)
+
+
+def _audit_host(name, machine, main_matrices, preprocessed, opts):
+    """vgpu_`name`_audit_host: main_matrices = one canonical matrix per chip, preprocessed = [(chip index, matrix)], opts = the audit's options."""
+    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
+    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
+    for m in mains + [m for _, m in preps]:
+        if m.ndim != 2:
+            raise VgpuError(-1, "%s_audit: traces are two-dimensional matrices" % name)
+
+    def arrays(ms):
+        n = max(1, len(ms))
+        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
+
+    mp, mh, mw = arrays(mains)
+    pp, ph, pw = arrays([m for _, m in preps])
+    chips = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
+    h = ctypes.c_void_p()
+    _check(getattr(lib(), "vgpu_%s_audit_host" % name)(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chips, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts),
+                                                        ctypes.byref(h)))
+    return _audit_report(name, _AUDIT_REPORTS[name], h)
+
+
 class BusAuditOpts(ctypes.Structure):  # vgpu_bus_audit_opts_t
     _fields_ = [("max_tuples", ctypes.c_uint64), ("max_records_per_tuple", ctypes.c_uint32), ("hash_bits", ctypes.c_uint32)]
 
@@ -976,48 +1034,18 @@ def _bus_opts(max_tuples, max_records_per_tuple, hash_bits):
     return BusAuditOpts(int(max_tuples), int(max_records_per_tuple), int(hash_bits))
 
 
-def _bus_report(h):
-    L = lib()
-    L.vgpu_bus_report_len.restype = ctypes.c_uint64
-    L.vgpu_bus_report_words.restype = c_u32p
-    L.vgpu_bus_report_len.argtypes = L.vgpu_bus_report_words.argtypes = L.vgpu_bus_report_free.argtypes = [ctypes.c_void_p]
-    try:
-        n = int(L.vgpu_bus_report_len(h))
-        words = np.ctypeslib.as_array(L.vgpu_bus_report_words(h), shape=(n,)).copy()
-        tm = (ctypes.c_double * 2)()
-        L.vgpu_bus_report_timing(h, tm)
-    finally:
-        L.vgpu_bus_report_free(h)
-    return BusReport(words, tm[0], tm[1])
-
-
 def bus_audit_host(machine, main_matrices, preprocessed, max_tuples=64, max_records_per_tuple=4, hash_bits=64):
     """The bus audit on the HOST (vgpu_bus_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
     [(chip index, matrix)].  hash_bits is accepted for symmetry with Prover.bus_audit (the host groups by full tuples)."""
     opts = _bus_opts(max_tuples, max_records_per_tuple, hash_bits)
-    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
-    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
-    for m in mains + [m for _, m in preps]:
-        if m.ndim != 2:
-            raise VgpuError(-1, "bus_audit: traces are two-dimensional matrices")
-
-    def arrays(ms):
-        n = max(1, len(ms))
-        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
-
-    mp, mh, mw = arrays(mains)
-    pp, ph, pw = arrays([m for _, m in preps])
-    chips = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
-    h = ctypes.c_void_p()
-    _check(lib().vgpu_bus_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chips, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
-    return _bus_report(h)
+    return _audit_host("bus", machine, main_matrices, preprocessed, opts)
 
 
 class ConstraintAuditOpts(ctypes.Structure):  # vgpu_constraint_audit_opts_t
     _fields_ = [("max_constraints", ctypes.c_uint64), ("max_rows_per_constraint", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
-class ConstraintReport:
+class ConstraintReport(_AuditReport):
     """The constraint audit of a witness (vgpu_constraint_audit / vgpu_constraint_audit_host; the contract is stated in include/vgpu.h), as plain
     Python values: satisfied, truncated, total_failing (failing (chip, constraint) pairs), reported,
     chips = [dict(chip, constraints, failing_constraints, height, failing_rows)], constraints = [dict(chip, constraint, failing_rows,
@@ -1050,11 +1078,6 @@ class ConstraintReport:
         return dict(satisfied=self.satisfied, truncated=self.truncated, total_failing=self.total_failing, reported=self.reported, device_ms=self.device_ms,
                     host_ms=self.host_ms, chips=self.chips, constraints=[dict(e, rows=[list(r) for r in e["rows"]]) for e in self.constraints])
 
-    def to_json(self):
-        import json
-
-        return json.dumps(self.to_dict())
-
 
 def _constraint_opts(max_constraints, max_rows_per_constraint):
     # in the C struct a zero field selects its default, so the refusals of explicit zeros are made here, with the library's status code
@@ -1063,42 +1086,11 @@ def _constraint_opts(max_constraints, max_rows_per_constraint):
     return ConstraintAuditOpts(int(max_constraints), int(max_rows_per_constraint), 0)
 
 
-def _constraint_report(h):
-    L = lib()
-    L.vgpu_constraint_report_len.restype = ctypes.c_uint64
-    L.vgpu_constraint_report_words.restype = c_u32p
-    L.vgpu_constraint_report_len.argtypes = L.vgpu_constraint_report_words.argtypes = L.vgpu_constraint_report_free.argtypes = [ctypes.c_void_p]
-    L.vgpu_constraint_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    try:
-        n = int(L.vgpu_constraint_report_len(h))
-        words = np.ctypeslib.as_array(L.vgpu_constraint_report_words(h), shape=(n,)).copy()
-        tm = (ctypes.c_double * 2)()
-        L.vgpu_constraint_report_timing(h, tm)
-    finally:
-        L.vgpu_constraint_report_free(h)
-    return ConstraintReport(words, tm[0], tm[1])
-
-
 def constraint_audit_host(machine, main_matrices, preprocessed, max_constraints=64, max_rows_per_constraint=4):
     """The constraint audit on the HOST (vgpu_constraint_audit_host: no device, one thread): main_matrices = one canonical matrix per chip,
     preprocessed = [(chip index, matrix)]; a ConstraintReport back."""
     opts = _constraint_opts(max_constraints, max_rows_per_constraint)
-    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
-    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
-    for m in mains + [m for _, m in preps]:
-        if m.ndim != 2:
-            raise VgpuError(-1, "constraint_audit: traces are two-dimensional matrices")
-
-    def arrays(ms):
-        n = max(1, len(ms))
-        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
-
-    mp, mh, mw = arrays(mains)
-    pp, ph, pw = arrays([m for _, m in preps])
-    chips = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
-    h = ctypes.c_void_p()
-    _check(lib().vgpu_constraint_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chips, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
-    return _constraint_report(h)
+    return _audit_host("constraint", machine, main_matrices, preprocessed, opts)
 
 
 class MutationAuditOpts(ctypes.Structure):  # vgpu_mutation_audit_opts_t
@@ -1106,7 +1098,7 @@ class MutationAuditOpts(ctypes.Structure):  # vgpu_mutation_audit_opts_t
                 ("reserved", ctypes.c_uint32 * 2)]
 
 
-class MutationReport:
+class MutationReport(_AuditReport):
     """The mutation audit of a witness (vgpu_mutation_audit / vgpu_mutation_audit_host; the contract is stated in include/vgpu.h), as plain
     Python values: deltas, truncated, total_entries ((chip, column, delta) with a free row), reported,
     chips = [dict(chip, width, constraints, height, unbound, free=[per delta], air=[..], bus=[..])] (sums over the chip's columns),
@@ -1153,11 +1145,6 @@ class MutationReport:
         return dict(deltas=self.deltas, truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
                     evaluations=self.evaluations, chips=self.chips, entries=self.entries)
 
-    def to_json(self):
-        import json
-
-        return json.dumps(self.to_dict())
-
 
 def _mutation_opts(deltas, max_entries, max_rows_per_entry):
     # in the C struct a zero field selects its default, so the refusals of explicit zeros (and of an empty delta list) are made here, with the
@@ -1172,42 +1159,11 @@ def _mutation_opts(deltas, max_entries, max_rows_per_entry):
     return MutationAuditOpts(int(max_entries), int(max_rows_per_entry), len(ds), (ctypes.c_uint32 * 4)(*ds), (ctypes.c_uint32 * 2)(0, 0))
 
 
-def _mutation_report(h):
-    L = lib()
-    L.vgpu_mutation_report_len.restype = ctypes.c_uint64
-    L.vgpu_mutation_report_words.restype = c_u32p
-    L.vgpu_mutation_report_len.argtypes = L.vgpu_mutation_report_words.argtypes = L.vgpu_mutation_report_free.argtypes = [ctypes.c_void_p]
-    L.vgpu_mutation_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    try:
-        n = int(L.vgpu_mutation_report_len(h))
-        words = np.ctypeslib.as_array(L.vgpu_mutation_report_words(h), shape=(n,)).copy()
-        tm = (ctypes.c_double * 3)()
-        L.vgpu_mutation_report_timing(h, tm)
-    finally:
-        L.vgpu_mutation_report_free(h)
-    return MutationReport(words, tm[0], tm[1], tm[2])
-
-
 def mutation_audit_host(machine, main_matrices, preprocessed, deltas=None, max_entries=1024, max_rows_per_entry=4):
     """The mutation audit on the HOST (vgpu_mutation_audit_host: no device, one thread): main_matrices = one canonical matrix per chip,
     preprocessed = [(chip index, matrix)], deltas = 1 to 4 distinct values in 1..p-1 (default (1, p - 1)); a MutationReport back."""
     opts = _mutation_opts(deltas, max_entries, max_rows_per_entry)
-    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
-    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
-    for m in mains + [m for _, m in preps]:
-        if m.ndim != 2:
-            raise VgpuError(-1, "mutation_audit: traces are two-dimensional matrices")
-
-    def arrays(ms):
-        n = max(1, len(ms))
-        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
-
-    mp, mh, mw = arrays(mains)
-    pp, ph, pw = arrays([m for _, m in preps])
-    chips = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
-    h = ctypes.c_void_p()
-    _check(lib().vgpu_mutation_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chips, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
-    return _mutation_report(h)
+    return _audit_host("mutation", machine, main_matrices, preprocessed, opts)
 
 
 class PairAuditOpts(ctypes.Structure):  # vgpu_pair_audit_opts_t
@@ -1215,7 +1171,7 @@ class PairAuditOpts(ctypes.Structure):  # vgpu_pair_audit_opts_t
                 ("chip_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
-class PairReport:
+class PairReport(_AuditReport):
     """The pair audit of a witness (vgpu_pair_audit / vgpu_pair_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
     deltas, truncated, total_entries ((chip, c1, c2, q) with a compensated row), reported,
     chips = [dict(chip, width, constraints, interactions, audited, height, coupled, slack, free=[per q], compensated=[per q])] (sums over all
@@ -1257,11 +1213,6 @@ class PairReport:
         return dict(deltas=self.deltas, truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
                     evaluations=self.evaluations, chips=self.chips, entries=self.entries)
 
-    def to_json(self):
-        import json
-
-        return json.dumps(self.to_dict())
-
 
 def _pair_opts(deltas, max_entries, max_rows_per_entry, chips):
     # as _mutation_opts: explicit zeros and an empty delta list are refused here, with the library's status code
@@ -1272,30 +1223,7 @@ def _pair_opts(deltas, max_entries, max_rows_per_entry, chips):
         raise VgpuError(-1, "pair_audit: 1 to 4 deltas (got %d)" % len(ds))
     if any(d < 0 or d > 0xFFFFFFFF for d in ds):
         raise VgpuError(-1, "pair_audit: a delta must be a canonical value in 1..p-1")
-    mask = 0
-    if chips is not None:
-        cs = [int(c) for c in chips]
-        if not cs or any(c < 0 or c > 31 for c in cs):
-            raise VgpuError(-1, "pair_audit: chips is a non-empty list of chip indices below 32")
-        for c in cs:
-            mask |= 1 << c
-    return PairAuditOpts(int(max_entries), int(max_rows_per_entry), len(ds), (ctypes.c_uint32 * 4)(*ds), mask, 0)
-
-
-def _pair_report(h):
-    L = lib()
-    L.vgpu_pair_report_len.restype = ctypes.c_uint64
-    L.vgpu_pair_report_words.restype = c_u32p
-    L.vgpu_pair_report_len.argtypes = L.vgpu_pair_report_words.argtypes = L.vgpu_pair_report_free.argtypes = [ctypes.c_void_p]
-    L.vgpu_pair_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    try:
-        n = int(L.vgpu_pair_report_len(h))
-        words = np.ctypeslib.as_array(L.vgpu_pair_report_words(h), shape=(n,)).copy()
-        tm = (ctypes.c_double * 3)()
-        L.vgpu_pair_report_timing(h, tm)
-    finally:
-        L.vgpu_pair_report_free(h)
-    return PairReport(words, tm[0], tm[1], tm[2])
+    return PairAuditOpts(int(max_entries), int(max_rows_per_entry), len(ds), (ctypes.c_uint32 * 4)(*ds), _chip_mask("pair", chips), 0)
 
 
 def pair_audit_host(machine, main_matrices, preprocessed, deltas=None, max_entries=1024, max_rows_per_entry=4, chips=None):
@@ -1303,29 +1231,14 @@ def pair_audit_host(machine, main_matrices, preprocessed, deltas=None, max_entri
     [(chip index, matrix)], deltas = 1 to 4 distinct values in 1..p-1 (default (1, p - 1)), chips = the chip indices to audit (default: all);
     a PairReport back."""
     opts = _pair_opts(deltas, max_entries, max_rows_per_entry, chips)
-    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
-    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
-    for m in mains + [m for _, m in preps]:
-        if m.ndim != 2:
-            raise VgpuError(-1, "pair_audit: traces are two-dimensional matrices")
-
-    def arrays(ms):
-        n = max(1, len(ms))
-        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
-
-    mp, mh, mw = arrays(mains)
-    pp, ph, pw = arrays([m for _, m in preps])
-    chip_ids = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
-    h = ctypes.c_void_p()
-    _check(lib().vgpu_pair_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chip_ids, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
-    return _pair_report(h)
+    return _audit_host("pair", machine, main_matrices, preprocessed, opts)
 
 
 class RankAuditOpts(ctypes.Structure):  # vgpu_rank_audit_opts_t
     _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 2)]
 
 
-class RankReport:
+class RankReport(_AuditReport):
     """The rank audit of a witness (vgpu_rank_audit / vgpu_rank_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
     truncated, total_entries ((chip, column) with a coupled row), reported,
     chips = [dict(chip, width, constraints, interactions, audited, height, nullity, zero, coupled_rows (sums over the rows), max_nullity,
@@ -1377,62 +1290,19 @@ class RankReport:
         return dict(truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
                     evaluations=self.evaluations, chips=self.chips, entries=self.entries)
 
-    def to_json(self):
-        import json
-
-        return json.dumps(self.to_dict())
-
 
 def _rank_opts(max_entries, max_rows_per_entry, chips):
     # as _pair_opts: explicit zeros are refused here, with the library's status code
     if int(max_entries) < 1 or int(max_rows_per_entry) < 1:
         raise VgpuError(-1, "rank_audit: max_entries and max_rows_per_entry must be at least 1")
-    mask = 0
-    if chips is not None:
-        cs = [int(c) for c in chips]
-        if not cs or any(c < 0 or c > 31 for c in cs):
-            raise VgpuError(-1, "rank_audit: chips is a non-empty list of chip indices below 32")
-        for c in cs:
-            mask |= 1 << c
-    return RankAuditOpts(int(max_entries), int(max_rows_per_entry), mask, (ctypes.c_uint32 * 2)(0, 0))
-
-
-def _rank_report(h):
-    L = lib()
-    L.vgpu_rank_report_len.restype = ctypes.c_uint64
-    L.vgpu_rank_report_words.restype = c_u32p
-    L.vgpu_rank_report_len.argtypes = L.vgpu_rank_report_words.argtypes = L.vgpu_rank_report_free.argtypes = [ctypes.c_void_p]
-    L.vgpu_rank_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    try:
-        n = int(L.vgpu_rank_report_len(h))
-        words = np.ctypeslib.as_array(L.vgpu_rank_report_words(h), shape=(n,)).copy()
-        tm = (ctypes.c_double * 3)()
-        L.vgpu_rank_report_timing(h, tm)
-    finally:
-        L.vgpu_rank_report_free(h)
-    return RankReport(words, tm[0], tm[1], tm[2])
+    return RankAuditOpts(int(max_entries), int(max_rows_per_entry), _chip_mask("rank", chips), (ctypes.c_uint32 * 2)(0, 0))
 
 
 def rank_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
     """The rank audit on the HOST (vgpu_rank_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
     [(chip index, matrix)], chips = the chip indices to audit (default: all); a RankReport back."""
     opts = _rank_opts(max_entries, max_rows_per_entry, chips)
-    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
-    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
-    for m in mains + [m for _, m in preps]:
-        if m.ndim != 2:
-            raise VgpuError(-1, "rank_audit: traces are two-dimensional matrices")
-
-    def arrays(ms):
-        n = max(1, len(ms))
-        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
-
-    mp, mh, mw = arrays(mains)
-    pp, ph, pw = arrays([m for _, m in preps])
-    chip_ids = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
-    h = ctypes.c_void_p()
-    _check(lib().vgpu_rank_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chip_ids, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
-    return _rank_report(h)
+    return _audit_host("rank", machine, main_matrices, preprocessed, opts)
 
 
 class StepAuditOpts(ctypes.Structure):  # vgpu_step_audit_opts_t
@@ -1440,7 +1310,7 @@ class StepAuditOpts(ctypes.Structure):  # vgpu_step_audit_opts_t
                 ("steps", ctypes.c_uint32 * 4), ("reserved", ctypes.c_uint32 * 3)]
 
 
-class StepReport:
+class StepReport(_AuditReport):
     """The step audit of a witness (vgpu_step_audit / vgpu_step_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
     steps (canonical), truncated, total_entries ((chip, column) with a coupled-and-exact or a curved row), reported,
     chips = [dict(chip, width, constraints, interactions, audited, height, max_degree, line_exact, loose_cells, zero_cells, exact_cells,
@@ -1510,22 +1380,11 @@ class StepReport:
         return dict(steps=self.steps, truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
                     evaluations=self.evaluations, chips=self.chips, entries=self.entries)
 
-    def to_json(self):
-        import json
-
-        return json.dumps(self.to_dict())
-
 
 def _step_opts(steps, max_entries, max_rows_per_entry, chips):
     if int(max_entries) < 1 or int(max_rows_per_entry) < 1:
         raise VgpuError(-1, "step_audit: max_entries and max_rows_per_entry must be at least 1")
-    mask = 0
-    if chips is not None:
-        cs = [int(c) for c in chips]
-        if not cs or any(c < 0 or c > 31 for c in cs):
-            raise VgpuError(-1, "step_audit: chips is a non-empty list of chip indices below 32")
-        for c in cs:
-            mask |= 1 << c
+    mask = _chip_mask("step", chips)
     st = [] if steps is None else [int(x) for x in steps]
     if steps is not None and not 1 <= len(st) <= 4:
         raise VgpuError(-1, "step_audit: 1 to 4 steps (got %d)" % len(st))
@@ -1534,46 +1393,15 @@ def _step_opts(steps, max_entries, max_rows_per_entry, chips):
     return StepAuditOpts(int(max_entries), int(max_rows_per_entry), mask, len(st), (ctypes.c_uint32 * 4)(*st), (ctypes.c_uint32 * 3)(0, 0, 0))
 
 
-def _step_report(h):
-    L = lib()
-    L.vgpu_step_report_len.restype = ctypes.c_uint64
-    L.vgpu_step_report_words.restype = c_u32p
-    L.vgpu_step_report_len.argtypes = L.vgpu_step_report_words.argtypes = L.vgpu_step_report_free.argtypes = [ctypes.c_void_p]
-    L.vgpu_step_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    try:
-        n = int(L.vgpu_step_report_len(h))
-        words = np.ctypeslib.as_array(L.vgpu_step_report_words(h), shape=(n,)).copy()
-        tm = (ctypes.c_double * 3)()
-        L.vgpu_step_report_timing(h, tm)
-    finally:
-        L.vgpu_step_report_free(h)
-    return StepReport(words, tm[0], tm[1], tm[2])
-
-
 def step_audit_host(machine, main_matrices, preprocessed, steps=None, max_entries=1024, max_rows_per_entry=4, chips=None):
     """The step audit on the HOST (vgpu_step_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
     [(chip index, matrix)], steps = 1 to 4 distinct canonical values in 1..p-1 (default 1, p - 1, 2), chips = the chip indices to audit
     (default: all); a StepReport back."""
     opts = _step_opts(steps, max_entries, max_rows_per_entry, chips)
-    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
-    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
-    for m in mains + [m for _, m in preps]:
-        if m.ndim != 2:
-            raise VgpuError(-1, "step_audit: traces are two-dimensional matrices")
-
-    def arrays(ms):
-        n = max(1, len(ms))
-        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
-
-    mp, mh, mw = arrays(mains)
-    pp, ph, pw = arrays([m for _, m in preps])
-    chip_ids = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
-    h = ctypes.c_void_p()
-    _check(lib().vgpu_step_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chip_ids, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
-    return _step_report(h)
+    return _audit_host("step", machine, main_matrices, preprocessed, opts)
 
 
-class FieldReport:
+class FieldReport(_AuditReport):
     """The field audit of a witness (vgpu_field_audit / vgpu_field_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
     truncated, total_entries ((chip, interaction, field) with a floating row), reported,
     chips = [dict(chip, width, constraints, interactions, audited, height, live_records, floating_fields, floating_rows (sums over the rows),
@@ -1624,11 +1452,6 @@ class FieldReport:
         return dict(truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
                     evaluations=self.evaluations, chips=self.chips, entries=self.entries)
 
-    def to_json(self):
-        import json
-
-        return json.dumps(self.to_dict())
-
 
 def _field_opts(max_entries, max_rows_per_entry, chips):
     # the rank audit's options (vgpu_rank_audit_opts_t) and refusals, under this audit's name
@@ -1639,49 +1462,18 @@ def _field_opts(max_entries, max_rows_per_entry, chips):
     return _rank_opts(max_entries, max_rows_per_entry, chips)
 
 
-def _field_report(h):
-    L = lib()
-    L.vgpu_field_report_len.restype = ctypes.c_uint64
-    L.vgpu_field_report_words.restype = c_u32p
-    L.vgpu_field_report_len.argtypes = L.vgpu_field_report_words.argtypes = L.vgpu_field_report_free.argtypes = [ctypes.c_void_p]
-    L.vgpu_field_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    try:
-        n = int(L.vgpu_field_report_len(h))
-        words = np.ctypeslib.as_array(L.vgpu_field_report_words(h), shape=(n,)).copy()
-        tm = (ctypes.c_double * 3)()
-        L.vgpu_field_report_timing(h, tm)
-    finally:
-        L.vgpu_field_report_free(h)
-    return FieldReport(words, tm[0], tm[1], tm[2])
-
-
 def field_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
     """The field audit on the HOST (vgpu_field_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
     [(chip index, matrix)], chips = the chip indices to audit (default: all); a FieldReport back."""
     opts = _field_opts(max_entries, max_rows_per_entry, chips)
-    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
-    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
-    for m in mains + [m for _, m in preps]:
-        if m.ndim != 2:
-            raise VgpuError(-1, "field_audit: traces are two-dimensional matrices")
-
-    def arrays(ms):
-        n = max(1, len(ms))
-        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
-
-    mp, mh, mw = arrays(mains)
-    pp, ph, pw = arrays([m for _, m in preps])
-    chip_ids = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
-    h = ctypes.c_void_p()
-    _check(lib().vgpu_field_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chip_ids, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
-    return _field_report(h)
+    return _audit_host("field", machine, main_matrices, preprocessed, opts)
 
 
 class LinkAuditOpts(ctypes.Structure):  # vgpu_link_audit_opts_t
     _fields_ = [("max_tuples", ctypes.c_uint64), ("max_records_per_tuple", ctypes.c_uint32), ("hash_bits", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
 
 
-class LinkReport:
+class LinkReport(_AuditReport):
     """The link audit of a witness (vgpu_link_audit / vgpu_link_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
     truncated, open_tuples (tuples with an open position: exact even when the list is cut), reported,
     buses = [dict(bus=(is_global, bus_index), width, live, tuples, open_tuples, open_in=[tuples in which position j is open], open_records=[the
@@ -1744,11 +1536,6 @@ class LinkReport:
                     buses=[dict(b, bus=list(b["bus"])) for b in self.buses], chips=self.chips,
                     tuples=[dict(t, bus=list(t["bus"]), records=[list(r) for r in t["records"]]) for t in self.tuples])
 
-    def to_json(self):
-        import json
-
-        return json.dumps(self.to_dict())
-
 
 def _link_opts(max_tuples, max_records_per_tuple, hash_bits):
     # in the C struct a zero field selects its default, so the refusals of explicit zeros are made here, with the library's status code
@@ -1759,42 +1546,11 @@ def _link_opts(max_tuples, max_records_per_tuple, hash_bits):
     return LinkAuditOpts(int(max_tuples), int(max_records_per_tuple), int(hash_bits), 0)
 
 
-def _link_report(h):
-    L = lib()
-    L.vgpu_link_report_len.restype = ctypes.c_uint64
-    L.vgpu_link_report_words.restype = c_u32p
-    L.vgpu_link_report_len.argtypes = L.vgpu_link_report_words.argtypes = L.vgpu_link_report_free.argtypes = [ctypes.c_void_p]
-    L.vgpu_link_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    try:
-        n = int(L.vgpu_link_report_len(h))
-        words = np.ctypeslib.as_array(L.vgpu_link_report_words(h), shape=(n,)).copy()
-        tm = (ctypes.c_double * 3)()
-        L.vgpu_link_report_timing(h, tm)
-    finally:
-        L.vgpu_link_report_free(h)
-    return LinkReport(words, tm[0], tm[1], tm[2])
-
-
 def link_audit_host(machine, main_matrices, preprocessed, max_tuples=64, max_records_per_tuple=4, hash_bits=64):
     """The link audit on the HOST (vgpu_link_audit_host: no device, one thread): main_matrices = one canonical matrix per chip, preprocessed =
     [(chip index, matrix)]; a LinkReport back.  hash_bits is accepted for symmetry with Prover.link_audit (the host groups by full tuples)."""
     opts = _link_opts(max_tuples, max_records_per_tuple, hash_bits)
-    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
-    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
-    for m in mains + [m for _, m in preps]:
-        if m.ndim != 2:
-            raise VgpuError(-1, "link_audit: traces are two-dimensional matrices")
-
-    def arrays(ms):
-        n = max(1, len(ms))
-        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
-
-    mp, mh, mw = arrays(mains)
-    pp, ph, pw = arrays([m for _, m in preps])
-    chip_ids = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
-    h = ctypes.c_void_p()
-    _check(lib().vgpu_link_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chip_ids, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
-    return _link_report(h)
+    return _audit_host("link", machine, main_matrices, preprocessed, opts)
 
 
 class CoverageAuditOpts(ctypes.Structure):  # vgpu_coverage_audit_opts_t
@@ -1805,7 +1561,7 @@ class CoverageAuditOpts(ctypes.Structure):  # vgpu_coverage_audit_opts_t
 NO_ROW = 0xFFFFFFFF
 
 
-class CoverageReport:
+class CoverageReport(_AuditReport):
     """The coverage audit of a witness (vgpu_coverage_audit / vgpu_coverage_audit_host; the contract is stated in include/vgpu.h), as plain
     Python values: deltas, truncated, total_cells ((chip, detector, column, delta) with kills > 0), reported,
     chips = [dict(chip, width, constraints, interactions, height, dead_constraints, shadowed_constraints, dead_interactions,
@@ -1864,11 +1620,6 @@ class CoverageReport:
     def to_dict(self):
         return dict(deltas=self.deltas, truncated=self.truncated, total_cells=self.total_cells, reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms,
                     evaluations=self.evaluations, chips=self.chips, cells=self.cells)
-
-    def to_json(self):
-        import json
-
-        return json.dumps(self.to_dict())
 
     @staticmethod
     def _image(deltas, truncated, total_cells, chips, cells):
@@ -1951,43 +1702,23 @@ def _coverage_opts(deltas, max_cells, max_workgroups):
     return CoverageAuditOpts(int(max_cells), len(ds), (ctypes.c_uint32 * 4)(*ds), int(max_workgroups), (ctypes.c_uint32 * 2)(0, 0))
 
 
-def _coverage_report(h):
-    L = lib()
-    L.vgpu_coverage_report_len.restype = ctypes.c_uint64
-    L.vgpu_coverage_report_words.restype = c_u32p
-    L.vgpu_coverage_report_len.argtypes = L.vgpu_coverage_report_words.argtypes = L.vgpu_coverage_report_free.argtypes = [ctypes.c_void_p]
-    L.vgpu_coverage_report_timing.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-    try:
-        n = int(L.vgpu_coverage_report_len(h))
-        words = np.ctypeslib.as_array(L.vgpu_coverage_report_words(h), shape=(n,)).copy()
-        tm = (ctypes.c_double * 3)()
-        L.vgpu_coverage_report_timing(h, tm)
-    finally:
-        L.vgpu_coverage_report_free(h)
-    return CoverageReport(words, tm[0], tm[1], tm[2])
-
-
 def coverage_audit_host(machine, main_matrices, preprocessed, deltas=None, max_cells=8192):
     """The coverage audit on the HOST (vgpu_coverage_audit_host: no device, one thread, no limits): main_matrices = one canonical matrix per
     chip, preprocessed = [(chip index, matrix)], deltas = 1 to 4 distinct values in 1..p-1 (default (1, p - 1)); a CoverageReport back."""
     opts = _coverage_opts(deltas, max_cells, 0)
-    mains = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_matrices]
-    preps = [(int(c), np.ascontiguousarray(m, dtype=np.uint32)) for c, m in preprocessed]
-    for m in mains + [m for _, m in preps]:
-        if m.ndim != 2:
-            raise VgpuError(-1, "coverage_audit: traces are two-dimensional matrices")
+    return _audit_host("coverage", machine, main_matrices, preprocessed, opts)
 
-    def arrays(ms):
-        n = max(1, len(ms))
-        return ((ctypes.c_void_p * n)(*[m.ctypes.data for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[0] for m in ms]), (ctypes.c_uint64 * n)(*[m.shape[1] for m in ms]))
 
-    mp, mh, mw = arrays(mains)
-    pp, ph, pw = arrays([m for _, m in preps])
-    chips = (ctypes.c_uint32 * max(1, len(preps)))(*[c for c, _ in preps])
-    h = ctypes.c_void_p()
-    _check(lib().vgpu_coverage_audit_host(machine._h, mp, mh, mw, ctypes.c_uint32(len(mains)), chips, pp, ph, pw, ctypes.c_uint32(len(preps)), ctypes.byref(opts), ctypes.byref(h)))
-    return _coverage_report(h)
+_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, field=FieldReport,
+                      link=LinkReport, coverage=CoverageReport)
 
+
+def _report_of(name):
+    return lambda h: _audit_report(name, _AUDIT_REPORTS[name], h)
+
+
+# a raw vgpu_X_audit(_host) call's handle as the audit's report (the tests of the options structs call the C entry points themselves)
+_rank_report, _step_report, _field_report, _link_report = _report_of("rank"), _report_of("step"), _report_of("field"), _report_of("link")
 
 class Ticket:
     """An outstanding asynchronous proof (vgpu_prove_async); keeps its inputs alive until waited for."""
@@ -2152,110 +1883,74 @@ class Prover:
                                 ctypes.c_uint32((1 if debug else 0) | (2 if check else 0)), ctypes.byref(h)))
         return Proof(h)
 
-    def bus_audit(self, main, preprocessed, max_tuples=64, max_records_per_tuple=4, hash_bits=64):
-        """Which bus tuples of this witness are unbalanced (vgpu_bus_audit; the exact form of check_cumulative_sums): the arguments of prove,
-        a BusReport back.  hash_bits < 64 is a test hook (the grouping key is cut; the report must not change)."""
-        opts = _bus_opts(max_tuples, max_records_per_tuple, hash_bits)
+    def _audit(self, name, main, preprocessed, opts):
+        """vgpu_`name`_audit: the arguments of prove and the audit's options; the audit's report back."""
         arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
         chips = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
         parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
         h = ctypes.c_void_p()
-        _check(lib().vgpu_bus_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
-        return _bus_report(h)
+        _check(getattr(lib(), "vgpu_%s_audit" % name)(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
+        return _audit_report(name, _AUDIT_REPORTS[name], h)
+
+    def bus_audit(self, main, preprocessed, max_tuples=64, max_records_per_tuple=4, hash_bits=64):
+        """Which bus tuples of this witness are unbalanced (vgpu_bus_audit; the exact form of check_cumulative_sums): the arguments of prove,
+        a BusReport back.  hash_bits < 64 is a test hook (the grouping key is cut; the report must not change)."""
+        opts = _bus_opts(max_tuples, max_records_per_tuple, hash_bits)
+        return self._audit("bus", main, preprocessed, opts)
 
     def constraint_audit(self, main, preprocessed, max_constraints=64, max_rows_per_constraint=4):
         """Which AIR constraints of this witness fail, on which rows, with which value (vgpu_constraint_audit; check_constraints made exact and
         complete): the arguments of prove, a ConstraintReport back."""
         opts = _constraint_opts(max_constraints, max_rows_per_constraint)
-        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
-        chips = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
-        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
-        h = ctypes.c_void_p()
-        _check(lib().vgpu_constraint_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
-        return _constraint_report(h)
+        return self._audit("constraint", main, preprocessed, opts)
 
     def mutation_audit(self, main, preprocessed, deltas=None, max_entries=1024, max_rows_per_entry=4):
         """Which cells of this witness could be changed by a delta without any AIR constraint or bus noticing (vgpu_mutation_audit; mutation
         testing of the AIRs): the arguments of prove, deltas = 1 to 4 distinct values in 1..p-1 (default (1, p - 1)); a MutationReport back."""
         opts = _mutation_opts(deltas, max_entries, max_rows_per_entry)
-        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
-        chips = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
-        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
-        h = ctypes.c_void_p()
-        _check(lib().vgpu_mutation_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
-        return _mutation_report(h)
+        return self._audit("mutation", main, preprocessed, opts)
 
     def pair_audit(self, main, preprocessed, deltas=None, max_entries=1024, max_rows_per_entry=4, chips=None):
         """Which two cells of one row of this witness could be changed together without any AIR constraint or bus noticing although one of the
         changes alone is noticed (vgpu_pair_audit): the arguments of prove, deltas as in mutation_audit, chips = the chip indices to audit
         (default: all); a PairReport back."""
         opts = _pair_opts(deltas, max_entries, max_rows_per_entry, chips)
-        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
-        chip_ids = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
-        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
-        h = ctypes.c_void_p()
-        _check(lib().vgpu_pair_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
-        return _pair_report(h)
+        return self._audit("pair", main, preprocessed, opts)
 
     def rank_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
         """Every first-order degree of freedom of each trace row of this witness (vgpu_rank_audit): per row the null space of the Jacobian of
         all constraints and bus records that read the row; the arguments of prove, chips = the chip indices to audit (default: all); a
         RankReport back."""
         opts = _rank_opts(max_entries, max_rows_per_entry, chips)
-        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
-        chip_ids = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
-        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
-        h = ctypes.c_void_p()
-        _check(lib().vgpu_rank_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
-        return _rank_report(h)
+        return self._audit("rank", main, preprocessed, opts)
 
     def step_audit(self, main, preprocessed, steps=None, max_entries=1024, max_rows_per_entry=4, chips=None):
         """Finite steps along each row's null directions (vgpu_step_audit): the rank audit's canonical null vector of every (row, loose column),
         moved by each step and judged by the mutation audit's rule; the arguments of prove, steps = 1 to 4 distinct canonical values (default 1,
         p - 1, 2), chips = the chip indices to audit (default: all); a StepReport back."""
         opts = _step_opts(steps, max_entries, max_rows_per_entry, chips)
-        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
-        chip_ids = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
-        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
-        h = ctypes.c_void_p()
-        _check(lib().vgpu_step_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
-        return _step_report(h)
+        return self._audit("step", main, preprocessed, opts)
 
     def field_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
         """Which fields of the chips' bus records this witness's constraints leave undetermined (vgpu_field_audit): per row and live record,
         is each field fixed to first order by the constraints, the counts and the record's other fields; the arguments of prove, chips = the
         chip indices to audit (default: all); a FieldReport back."""
         opts = _field_opts(max_entries, max_rows_per_entry, chips)
-        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
-        chip_ids = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
-        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
-        h = ctypes.c_void_p()
-        _check(lib().vgpu_field_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
-        return _field_report(h)
+        return self._audit("field", main, preprocessed, opts)
 
     def link_audit(self, main, preprocessed, max_tuples=64, max_records_per_tuple=4, hash_bits=64):
         """Which positions of this witness's bus tuples no chip on the bus pins (vgpu_link_audit): the field audit's float mask of every live
         record, ANDed over the records of each tuple of the bus audit; the arguments of prove, a LinkReport back.  hash_bits < 64 is the bus
         audit's test hook (the grouping key is cut; the report must not change)."""
         opts = _link_opts(max_tuples, max_records_per_tuple, hash_bits)
-        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
-        chip_ids = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
-        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
-        h = ctypes.c_void_p()
-        _check(lib().vgpu_link_audit(self._h, arr, ctypes.c_uint32(len(main)), chip_ids, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
-        return _link_report(h)
+        return self._audit("link", main, preprocessed, opts)
 
     def coverage_audit(self, main, preprocessed, deltas=None, max_cells=8192, max_workgroups=0):
         """Which constraint or interaction detects each mutation of the mutation audit (vgpu_coverage_audit): the arguments of prove, deltas as
         in mutation_audit; max_workgroups is a tuning knob (workgroups along a chip's rows, 0: the default) on which the report never depends.
         A CoverageReport back."""
         opts = _coverage_opts(deltas, max_cells, max_workgroups)
-        arr = (ctypes.c_void_p * max(1, len(main)))(*[t._h for t in main])
-        chips = (ctypes.c_uint32 * max(1, len(preprocessed)))(*[c for c, _ in preprocessed])
-        parr = (ctypes.c_void_p * max(1, len(preprocessed)))(*[t._h for _, t in preprocessed])
-        h = ctypes.c_void_p()
-        _check(lib().vgpu_coverage_audit(self._h, arr, ctypes.c_uint32(len(main)), chips, parr, ctypes.c_uint32(len(preprocessed)), ctypes.byref(opts), ctypes.byref(h)))
-        return _coverage_report(h)
+        return self._audit("coverage", main, preprocessed, opts)
 
     def prove_async(self, main, preprocessed, keep=None):
         """Start Machine::prove on a host thread of the library; returns a Ticket (wait() -> Proof).  `keep`: further objects

@@ -47,15 +47,17 @@ struct vgpu_ticket { std::future<std::pair<vgpu_proof_t*, std::pair<int32_t, std
 struct vgpu_proof { std::vector<uint32_t> words; PhaseTimes tm; ProveDebugOut dbg; };
 struct vgpu_oplog { std::shared_ptr<Prover> owner; std::unique_ptr<DeviceOplog> log; };
 struct vgpu_opening { std::vector<uint32_t> values, proof; };
-struct vgpu_bus_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0; };
-struct vgpu_constraint_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0; };
-struct vgpu_mutation_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
-struct vgpu_coverage_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
-struct vgpu_pair_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
-struct vgpu_rank_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
-struct vgpu_field_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
-struct vgpu_link_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
-struct vgpu_step_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
+// Every audit's report handle: the word image and the times (evaluations stays 0 for the bus and constraint audits, whose reports have none).
+struct audit_report { std::vector<uint32_t> words; double device_ms = 0, host_ms = 0, evaluations = 0; };
+struct vgpu_bus_report : audit_report {};
+struct vgpu_constraint_report : audit_report {};
+struct vgpu_mutation_report : audit_report {};
+struct vgpu_coverage_report : audit_report {};
+struct vgpu_pair_report : audit_report {};
+struct vgpu_rank_report : audit_report {};
+struct vgpu_field_report : audit_report {};
+struct vgpu_link_report : audit_report {};
+struct vgpu_step_report : audit_report {};
 struct vgpu_comm { std::shared_ptr<Prover> owner; std::unique_ptr<Comm> comm; };  // owner first: the communicator dies before its context
 static_assert(sizeof(vgpu_cpu_op_t) == sizeof(vk::TgCpuOp) && sizeof(vgpu_mem_op_t) == sizeof(vk::TgMemOp) && sizeof(vgpu_alu_op_t) == sizeof(vk::TgAluOp),
               "C ABI log records and their device images must match");
@@ -858,19 +860,22 @@ int32_t vgpu_prove(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n
         *out = proof.release();
     })
 }
-// ---- bus audit (host/bus_audit.hpp) ----
-static BusAuditOpts bus_opts(const vgpu_bus_audit_opts_t* o) {
-    BusAuditOpts r;  // a null pointer or a zero field: the default
-    if (o) { r.max_tuples = o->max_tuples; r.max_records_per_tuple = o->max_records_per_tuple; r.hash_bits = o->hash_bits; }
-    return r;
-}
-static vgpu_bus_report* bus_report_handle(const BusReport& rep) {
-    auto h = std::make_unique<vgpu_bus_report>();
-    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms;
+
+// ---- the witness audits (host/*_audit.hpp; the device passes are host/prover_audits.cpp).  Every audit has the same five entry points: what
+// differs is the report type, the options and which function runs, so the bodies are written once and the C shells below name those three.
+extern "C++" {
+template <class Report> static auto report_evaluations(const Report& rep, int) -> decltype(rep.evaluations) { return rep.evaluations; }
+template <class Report> static double report_evaluations(const Report&, long) { return 0; }
+template <class Handle, class Report>
+static Handle* audit_report_handle(const Report& rep) {
+    auto h = std::make_unique<Handle>();
+    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms; h->evaluations = report_evaluations(rep, 0);
     return h.release();
 }
-int32_t vgpu_bus_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
-                       uint32_t n_prep, const vgpu_bus_audit_opts_t* opts, vgpu_bus_report_t** out) {
+// the device pass: audit(main traces, preprocessed traces) is one of Prover::*_audit with its options bound
+template <class Handle, class Audit>
+static int32_t audit_on_device(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep, uint32_t n_prep, Handle** out,
+                        Audit&& audit) {
     VG_TRY({
         if (!p || !out || (n_main && !main) || (n_prep && (!prep || !prep_chips))) throw std::invalid_argument("null argument");
         std::vector<const DeviceTrace*> m;
@@ -879,27 +884,52 @@ int32_t vgpu_bus_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32
         std::vector<std::pair<int, const DeviceTrace*>> pr;
         for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &foreign); pr.push_back({(int)prep_chips[i], prep[i]->t.get()}); }
         drain(foreign);
-        *out = bus_report_handle(p->p->bus_audit(m, pr, bus_opts(opts)));
+        *out = audit_report_handle<Handle>(audit(m, pr));
     })
+}
+// the host reference: audit(machine, main matrices, preprocessed chips, preprocessed matrices) is one of the *_audit_host with its options bound
+template <class Matrix, class Handle, class Audit>
+static int32_t audit_on_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main, const uint32_t* prep_chips,
+                      const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep, Handle** out, Audit&& audit) {
+    VG_TRY({
+        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
+        const auto t0 = Clock::now();
+        std::vector<Matrix> m, pm;
+        std::vector<int> chips;
+        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
+        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
+        auto rep = audit(machine->desc, m, chips, pm);
+        rep.host_ms = ms_since(t0);
+        *out = audit_report_handle<Handle>(rep);
+    })
+}
+}  // extern "C++"
+static uint64_t report_len(const audit_report* r) { return r ? r->words.size() : 0; }
+static const uint32_t* report_words(const audit_report* r) { return r ? r->words.data() : nullptr; }
+static void report_timing(const audit_report* r, double* out, int n) {  // n: 2, or 3 for the reports that count evaluations
+    out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0;
+    if (n == 3) out[2] = r ? r->evaluations : 0;
+}
+
+// ---- bus audit (host/bus_audit.hpp) ----
+static BusAuditOpts bus_opts(const vgpu_bus_audit_opts_t* o) {
+    BusAuditOpts r;  // a null pointer or a zero field: the default
+    if (o) { r.max_tuples = o->max_tuples; r.max_records_per_tuple = o->max_records_per_tuple; r.hash_bits = o->hash_bits; }
+    return r;
+}
+int32_t vgpu_bus_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                       uint32_t n_prep, const vgpu_bus_audit_opts_t* opts, vgpu_bus_report_t** out) {
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->bus_audit(m, pr, bus_opts(opts)); });
 }
 int32_t vgpu_bus_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
                             const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
                             const vgpu_bus_audit_opts_t* opts, vgpu_bus_report_t** out) {
-    VG_TRY({
-        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<BusHostMatrix> m, pm;
-        std::vector<int> chips;
-        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
-        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
-        BusReport rep = bus_audit_host(machine->desc, m, chips, pm, bus_opts(opts));
-        rep.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *out = bus_report_handle(rep);
-    })
+    return audit_on_host<BusHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                        [&](auto&... a) { return bus_audit_host(a..., bus_opts(opts)); });
 }
-uint64_t vgpu_bus_report_len(const vgpu_bus_report_t* r) { return r ? r->words.size() : 0; }
-const uint32_t* vgpu_bus_report_words(const vgpu_bus_report_t* r) { return r ? r->words.data() : nullptr; }
-void vgpu_bus_report_timing(const vgpu_bus_report_t* r, double out[2]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; }
+uint64_t vgpu_bus_report_len(const vgpu_bus_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_bus_report_words(const vgpu_bus_report_t* r) { return report_words(r); }
+void vgpu_bus_report_timing(const vgpu_bus_report_t* r, double out[2]) { report_timing(r, out, 2); }
 void vgpu_bus_report_free(vgpu_bus_report_t* r) { delete r; }
 
 // ---- constraint audit (host/constraint_audit.hpp) ----
@@ -908,42 +938,19 @@ static ConstraintAuditOpts constraint_opts(const vgpu_constraint_audit_opts_t* o
     if (o) { r.max_constraints = o->max_constraints; r.max_rows_per_constraint = o->max_rows_per_constraint; r.reserved = o->reserved; }
     return r;
 }
-static vgpu_constraint_report* constraint_report_handle(const ConstraintReport& rep) {
-    auto h = std::make_unique<vgpu_constraint_report>();
-    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms;
-    return h.release();
-}
 int32_t vgpu_constraint_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
                               uint32_t n_prep, const vgpu_constraint_audit_opts_t* opts, vgpu_constraint_report_t** out) {
-    VG_TRY({
-        if (!p || !out || (n_main && !main) || (n_prep && (!prep || !prep_chips))) throw std::invalid_argument("null argument");
-        std::vector<const DeviceTrace*> m;
-        std::vector<std::shared_ptr<Prover>> foreign;
-        for (uint32_t i = 0; i < n_main; i++) { check_trace(p, main[i], &foreign); m.push_back(main[i]->t.get()); }
-        std::vector<std::pair<int, const DeviceTrace*>> pr;
-        for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &foreign); pr.push_back({(int)prep_chips[i], prep[i]->t.get()}); }
-        drain(foreign);
-        *out = constraint_report_handle(p->p->constraint_audit(m, pr, constraint_opts(opts)));
-    })
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->constraint_audit(m, pr, constraint_opts(opts)); });
 }
 int32_t vgpu_constraint_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
                                    const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
                                    const vgpu_constraint_audit_opts_t* opts, vgpu_constraint_report_t** out) {
-    VG_TRY({
-        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<ConstraintHostMatrix> m, pm;
-        std::vector<int> chips;
-        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
-        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
-        ConstraintReport rep = constraint_audit_host(machine->desc, m, chips, pm, constraint_opts(opts));
-        rep.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *out = constraint_report_handle(rep);
-    })
+    return audit_on_host<ConstraintHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                               [&](auto&... a) { return constraint_audit_host(a..., constraint_opts(opts)); });
 }
-uint64_t vgpu_constraint_report_len(const vgpu_constraint_report_t* r) { return r ? r->words.size() : 0; }
-const uint32_t* vgpu_constraint_report_words(const vgpu_constraint_report_t* r) { return r ? r->words.data() : nullptr; }
-void vgpu_constraint_report_timing(const vgpu_constraint_report_t* r, double out[2]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; }
+uint64_t vgpu_constraint_report_len(const vgpu_constraint_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_constraint_report_words(const vgpu_constraint_report_t* r) { return report_words(r); }
+void vgpu_constraint_report_timing(const vgpu_constraint_report_t* r, double out[2]) { report_timing(r, out, 2); }
 void vgpu_constraint_report_free(vgpu_constraint_report_t* r) { delete r; }
 
 // ---- mutation audit (host/mutation_audit.hpp) ----
@@ -957,42 +964,19 @@ static MutationAuditOpts mutation_opts(const vgpu_mutation_audit_opts_t* o) {
     }
     return r;
 }
-static vgpu_mutation_report* mutation_report_handle(const MutationReport& rep) {
-    auto h = std::make_unique<vgpu_mutation_report>();
-    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms; h->evaluations = rep.evaluations;
-    return h.release();
-}
 int32_t vgpu_mutation_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
                             uint32_t n_prep, const vgpu_mutation_audit_opts_t* opts, vgpu_mutation_report_t** out) {
-    VG_TRY({
-        if (!p || !out || (n_main && !main) || (n_prep && (!prep || !prep_chips))) throw std::invalid_argument("null argument");
-        std::vector<const DeviceTrace*> m;
-        std::vector<std::shared_ptr<Prover>> foreign;
-        for (uint32_t i = 0; i < n_main; i++) { check_trace(p, main[i], &foreign); m.push_back(main[i]->t.get()); }
-        std::vector<std::pair<int, const DeviceTrace*>> pr;
-        for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &foreign); pr.push_back({(int)prep_chips[i], prep[i]->t.get()}); }
-        drain(foreign);
-        *out = mutation_report_handle(p->p->mutation_audit(m, pr, mutation_opts(opts)));
-    })
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->mutation_audit(m, pr, mutation_opts(opts)); });
 }
 int32_t vgpu_mutation_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
                                  const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
                                  const vgpu_mutation_audit_opts_t* opts, vgpu_mutation_report_t** out) {
-    VG_TRY({
-        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<ConstraintHostMatrix> m, pm;
-        std::vector<int> chips;
-        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
-        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
-        MutationReport rep = mutation_audit_host(machine->desc, m, chips, pm, mutation_opts(opts));
-        rep.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *out = mutation_report_handle(rep);
-    })
+    return audit_on_host<ConstraintHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                               [&](auto&... a) { return mutation_audit_host(a..., mutation_opts(opts)); });
 }
-uint64_t vgpu_mutation_report_len(const vgpu_mutation_report_t* r) { return r ? r->words.size() : 0; }
-const uint32_t* vgpu_mutation_report_words(const vgpu_mutation_report_t* r) { return r ? r->words.data() : nullptr; }
-void vgpu_mutation_report_timing(const vgpu_mutation_report_t* r, double out[3]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; out[2] = r ? r->evaluations : 0; }
+uint64_t vgpu_mutation_report_len(const vgpu_mutation_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_mutation_report_words(const vgpu_mutation_report_t* r) { return report_words(r); }
+void vgpu_mutation_report_timing(const vgpu_mutation_report_t* r, double out[3]) { report_timing(r, out, 3); }
 void vgpu_mutation_report_free(vgpu_mutation_report_t* r) { delete r; }
 
 // ---- pair audit (host/pair_audit.hpp) ----
@@ -1006,42 +990,19 @@ static PairAuditOpts pair_opts(const vgpu_pair_audit_opts_t* o) {
     }
     return r;
 }
-static vgpu_pair_report* pair_report_handle(const PairReport& rep) {
-    auto h = std::make_unique<vgpu_pair_report>();
-    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms; h->evaluations = rep.evaluations;
-    return h.release();
-}
 int32_t vgpu_pair_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
                         uint32_t n_prep, const vgpu_pair_audit_opts_t* opts, vgpu_pair_report_t** out) {
-    VG_TRY({
-        if (!p || !out || (n_main && !main) || (n_prep && (!prep || !prep_chips))) throw std::invalid_argument("null argument");
-        std::vector<const DeviceTrace*> m;
-        std::vector<std::shared_ptr<Prover>> foreign;
-        for (uint32_t i = 0; i < n_main; i++) { check_trace(p, main[i], &foreign); m.push_back(main[i]->t.get()); }
-        std::vector<std::pair<int, const DeviceTrace*>> pr;
-        for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &foreign); pr.push_back({(int)prep_chips[i], prep[i]->t.get()}); }
-        drain(foreign);
-        *out = pair_report_handle(p->p->pair_audit(m, pr, pair_opts(opts)));
-    })
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->pair_audit(m, pr, pair_opts(opts)); });
 }
 int32_t vgpu_pair_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
                              const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
                              const vgpu_pair_audit_opts_t* opts, vgpu_pair_report_t** out) {
-    VG_TRY({
-        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<ConstraintHostMatrix> m, pm;
-        std::vector<int> chips;
-        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
-        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
-        PairReport rep = pair_audit_host(machine->desc, m, chips, pm, pair_opts(opts));
-        rep.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *out = pair_report_handle(rep);
-    })
+    return audit_on_host<ConstraintHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                               [&](auto&... a) { return pair_audit_host(a..., pair_opts(opts)); });
 }
-uint64_t vgpu_pair_report_len(const vgpu_pair_report_t* r) { return r ? r->words.size() : 0; }
-const uint32_t* vgpu_pair_report_words(const vgpu_pair_report_t* r) { return r ? r->words.data() : nullptr; }
-void vgpu_pair_report_timing(const vgpu_pair_report_t* r, double out[3]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; out[2] = r ? r->evaluations : 0; }
+uint64_t vgpu_pair_report_len(const vgpu_pair_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_pair_report_words(const vgpu_pair_report_t* r) { return report_words(r); }
+void vgpu_pair_report_timing(const vgpu_pair_report_t* r, double out[3]) { report_timing(r, out, 3); }
 void vgpu_pair_report_free(vgpu_pair_report_t* r) { delete r; }
 
 // ---- rank audit (host/rank_audit.hpp) ----
@@ -1051,81 +1012,35 @@ static RankAuditOpts rank_opts(const vgpu_rank_audit_opts_t* o) {
     if (o) { r.max_entries = o->max_entries; r.max_rows_per_entry = o->max_rows_per_entry; r.chip_mask = o->chip_mask; r.reserved[0] = o->reserved[0]; r.reserved[1] = o->reserved[1]; }
     return r;
 }
-static vgpu_rank_report* rank_report_handle(const RankReport& rep) {
-    auto h = std::make_unique<vgpu_rank_report>();
-    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms; h->evaluations = rep.evaluations;
-    return h.release();
-}
 int32_t vgpu_rank_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
                         uint32_t n_prep, const vgpu_rank_audit_opts_t* opts, vgpu_rank_report_t** out) {
-    VG_TRY({
-        if (!p || !out || (n_main && !main) || (n_prep && (!prep || !prep_chips))) throw std::invalid_argument("null argument");
-        std::vector<const DeviceTrace*> m;
-        std::vector<std::shared_ptr<Prover>> foreign;
-        for (uint32_t i = 0; i < n_main; i++) { check_trace(p, main[i], &foreign); m.push_back(main[i]->t.get()); }
-        std::vector<std::pair<int, const DeviceTrace*>> pr;
-        for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &foreign); pr.push_back({(int)prep_chips[i], prep[i]->t.get()}); }
-        drain(foreign);
-        *out = rank_report_handle(p->p->rank_audit(m, pr, rank_opts(opts)));
-    })
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->rank_audit(m, pr, rank_opts(opts)); });
 }
 int32_t vgpu_rank_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
                              const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
                              const vgpu_rank_audit_opts_t* opts, vgpu_rank_report_t** out) {
-    VG_TRY({
-        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<ConstraintHostMatrix> m, pm;
-        std::vector<int> chips;
-        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
-        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
-        RankReport rep = rank_audit_host(machine->desc, m, chips, pm, rank_opts(opts));
-        rep.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *out = rank_report_handle(rep);
-    })
+    return audit_on_host<ConstraintHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                               [&](auto&... a) { return rank_audit_host(a..., rank_opts(opts)); });
 }
-uint64_t vgpu_rank_report_len(const vgpu_rank_report_t* r) { return r ? r->words.size() : 0; }
-const uint32_t* vgpu_rank_report_words(const vgpu_rank_report_t* r) { return r ? r->words.data() : nullptr; }
-void vgpu_rank_report_timing(const vgpu_rank_report_t* r, double out[3]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; out[2] = r ? r->evaluations : 0; }
+uint64_t vgpu_rank_report_len(const vgpu_rank_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_rank_report_words(const vgpu_rank_report_t* r) { return report_words(r); }
+void vgpu_rank_report_timing(const vgpu_rank_report_t* r, double out[3]) { report_timing(r, out, 3); }
 void vgpu_rank_report_free(vgpu_rank_report_t* r) { delete r; }
 
 // ---- field audit (host/field_audit.hpp); the options are the rank audit's ----
-static vgpu_field_report* field_report_handle(const FieldReport& rep) {
-    auto h = std::make_unique<vgpu_field_report>();
-    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms; h->evaluations = rep.evaluations;
-    return h.release();
-}
 int32_t vgpu_field_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
                         uint32_t n_prep, const vgpu_rank_audit_opts_t* opts, vgpu_field_report_t** out) {
-    VG_TRY({
-        if (!p || !out || (n_main && !main) || (n_prep && (!prep || !prep_chips))) throw std::invalid_argument("null argument");
-        std::vector<const DeviceTrace*> m;
-        std::vector<std::shared_ptr<Prover>> foreign;
-        for (uint32_t i = 0; i < n_main; i++) { check_trace(p, main[i], &foreign); m.push_back(main[i]->t.get()); }
-        std::vector<std::pair<int, const DeviceTrace*>> pr;
-        for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &foreign); pr.push_back({(int)prep_chips[i], prep[i]->t.get()}); }
-        drain(foreign);
-        *out = field_report_handle(p->p->field_audit(m, pr, rank_opts(opts)));
-    })
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->field_audit(m, pr, rank_opts(opts)); });
 }
 int32_t vgpu_field_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
                              const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
                              const vgpu_rank_audit_opts_t* opts, vgpu_field_report_t** out) {
-    VG_TRY({
-        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<ConstraintHostMatrix> m, pm;
-        std::vector<int> chips;
-        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
-        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
-        FieldReport rep = field_audit_host(machine->desc, m, chips, pm, rank_opts(opts));
-        rep.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *out = field_report_handle(rep);
-    })
+    return audit_on_host<ConstraintHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                               [&](auto&... a) { return field_audit_host(a..., rank_opts(opts)); });
 }
-uint64_t vgpu_field_report_len(const vgpu_field_report_t* r) { return r ? r->words.size() : 0; }
-const uint32_t* vgpu_field_report_words(const vgpu_field_report_t* r) { return r ? r->words.data() : nullptr; }
-void vgpu_field_report_timing(const vgpu_field_report_t* r, double out[3]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; out[2] = r ? r->evaluations : 0; }
+uint64_t vgpu_field_report_len(const vgpu_field_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_field_report_words(const vgpu_field_report_t* r) { return report_words(r); }
+void vgpu_field_report_timing(const vgpu_field_report_t* r, double out[3]) { report_timing(r, out, 3); }
 void vgpu_field_report_free(vgpu_field_report_t* r) { delete r; }
 
 // ---- link audit (host/link_audit.hpp) ----
@@ -1135,42 +1050,19 @@ static LinkAuditOpts link_opts(const vgpu_link_audit_opts_t* o) {
     if (o) { r.max_tuples = o->max_tuples; r.max_records_per_tuple = o->max_records_per_tuple; r.hash_bits = o->hash_bits; r.reserved = o->reserved; }
     return r;
 }
-static vgpu_link_report* link_report_handle(const LinkReport& rep) {
-    auto h = std::make_unique<vgpu_link_report>();
-    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms; h->evaluations = rep.evaluations;
-    return h.release();
-}
 int32_t vgpu_link_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
                         uint32_t n_prep, const vgpu_link_audit_opts_t* opts, vgpu_link_report_t** out) {
-    VG_TRY({
-        if (!p || !out || (n_main && !main) || (n_prep && (!prep || !prep_chips))) throw std::invalid_argument("null argument");
-        std::vector<const DeviceTrace*> m;
-        std::vector<std::shared_ptr<Prover>> foreign;
-        for (uint32_t i = 0; i < n_main; i++) { check_trace(p, main[i], &foreign); m.push_back(main[i]->t.get()); }
-        std::vector<std::pair<int, const DeviceTrace*>> pr;
-        for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &foreign); pr.push_back({(int)prep_chips[i], prep[i]->t.get()}); }
-        drain(foreign);
-        *out = link_report_handle(p->p->link_audit(m, pr, link_opts(opts)));
-    })
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->link_audit(m, pr, link_opts(opts)); });
 }
 int32_t vgpu_link_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
                              const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
                              const vgpu_link_audit_opts_t* opts, vgpu_link_report_t** out) {
-    VG_TRY({
-        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<ConstraintHostMatrix> m, pm;
-        std::vector<int> chips;
-        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
-        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
-        LinkReport rep = link_audit_host(machine->desc, m, chips, pm, link_opts(opts));
-        rep.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *out = link_report_handle(rep);
-    })
+    return audit_on_host<ConstraintHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                               [&](auto&... a) { return link_audit_host(a..., link_opts(opts)); });
 }
-uint64_t vgpu_link_report_len(const vgpu_link_report_t* r) { return r ? r->words.size() : 0; }
-const uint32_t* vgpu_link_report_words(const vgpu_link_report_t* r) { return r ? r->words.data() : nullptr; }
-void vgpu_link_report_timing(const vgpu_link_report_t* r, double out[3]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; out[2] = r ? r->evaluations : 0; }
+uint64_t vgpu_link_report_len(const vgpu_link_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_link_report_words(const vgpu_link_report_t* r) { return report_words(r); }
+void vgpu_link_report_timing(const vgpu_link_report_t* r, double out[3]) { report_timing(r, out, 3); }
 void vgpu_link_report_free(vgpu_link_report_t* r) { delete r; }
 
 // ---- step audit (host/step_audit.hpp) ----
@@ -1184,42 +1076,19 @@ static StepAuditOpts step_opts(const vgpu_step_audit_opts_t* o) {
     }
     return r;
 }
-static vgpu_step_report* step_report_handle(const StepReport& rep) {
-    auto h = std::make_unique<vgpu_step_report>();
-    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms; h->evaluations = rep.evaluations;
-    return h.release();
-}
 int32_t vgpu_step_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
                         uint32_t n_prep, const vgpu_step_audit_opts_t* opts, vgpu_step_report_t** out) {
-    VG_TRY({
-        if (!p || !out || (n_main && !main) || (n_prep && (!prep || !prep_chips))) throw std::invalid_argument("null argument");
-        std::vector<const DeviceTrace*> m;
-        std::vector<std::shared_ptr<Prover>> foreign;
-        for (uint32_t i = 0; i < n_main; i++) { check_trace(p, main[i], &foreign); m.push_back(main[i]->t.get()); }
-        std::vector<std::pair<int, const DeviceTrace*>> pr;
-        for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &foreign); pr.push_back({(int)prep_chips[i], prep[i]->t.get()}); }
-        drain(foreign);
-        *out = step_report_handle(p->p->step_audit(m, pr, step_opts(opts)));
-    })
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->step_audit(m, pr, step_opts(opts)); });
 }
 int32_t vgpu_step_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
                              const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
                              const vgpu_step_audit_opts_t* opts, vgpu_step_report_t** out) {
-    VG_TRY({
-        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<ConstraintHostMatrix> m, pm;
-        std::vector<int> chips;
-        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
-        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
-        StepReport rep = step_audit_host(machine->desc, m, chips, pm, step_opts(opts));
-        rep.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *out = step_report_handle(rep);
-    })
+    return audit_on_host<ConstraintHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                               [&](auto&... a) { return step_audit_host(a..., step_opts(opts)); });
 }
-uint64_t vgpu_step_report_len(const vgpu_step_report_t* r) { return r ? r->words.size() : 0; }
-const uint32_t* vgpu_step_report_words(const vgpu_step_report_t* r) { return r ? r->words.data() : nullptr; }
-void vgpu_step_report_timing(const vgpu_step_report_t* r, double out[3]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; out[2] = r ? r->evaluations : 0; }
+uint64_t vgpu_step_report_len(const vgpu_step_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_step_report_words(const vgpu_step_report_t* r) { return report_words(r); }
+void vgpu_step_report_timing(const vgpu_step_report_t* r, double out[3]) { report_timing(r, out, 3); }
 void vgpu_step_report_free(vgpu_step_report_t* r) { delete r; }
 
 // ---- coverage audit (host/coverage_audit.hpp) ----
@@ -1233,42 +1102,19 @@ static CoverageAuditOpts coverage_opts(const vgpu_coverage_audit_opts_t* o) {
     }
     return r;
 }
-static vgpu_coverage_report* coverage_report_handle(const CoverageReport& rep) {
-    auto h = std::make_unique<vgpu_coverage_report>();
-    h->words = rep.words(); h->device_ms = rep.device_ms; h->host_ms = rep.host_ms; h->evaluations = rep.evaluations;
-    return h.release();
-}
 int32_t vgpu_coverage_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
                             uint32_t n_prep, const vgpu_coverage_audit_opts_t* opts, vgpu_coverage_report_t** out) {
-    VG_TRY({
-        if (!p || !out || (n_main && !main) || (n_prep && (!prep || !prep_chips))) throw std::invalid_argument("null argument");
-        std::vector<const DeviceTrace*> m;
-        std::vector<std::shared_ptr<Prover>> foreign;
-        for (uint32_t i = 0; i < n_main; i++) { check_trace(p, main[i], &foreign); m.push_back(main[i]->t.get()); }
-        std::vector<std::pair<int, const DeviceTrace*>> pr;
-        for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &foreign); pr.push_back({(int)prep_chips[i], prep[i]->t.get()}); }
-        drain(foreign);
-        *out = coverage_report_handle(p->p->coverage_audit(m, pr, coverage_opts(opts)));
-    })
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->coverage_audit(m, pr, coverage_opts(opts)); });
 }
 int32_t vgpu_coverage_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
                                  const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
                                  const vgpu_coverage_audit_opts_t* opts, vgpu_coverage_report_t** out) {
-    VG_TRY({
-        if (!machine || !out || (n_main && (!main || !heights || !widths)) || (n_prep && (!prep || !prep_chips || !prep_heights || !prep_widths))) throw std::invalid_argument("null argument");
-        const auto t0 = std::chrono::steady_clock::now();
-        std::vector<ConstraintHostMatrix> m, pm;
-        std::vector<int> chips;
-        for (uint32_t i = 0; i < n_main; i++) m.push_back({main[i], heights[i], widths[i]});
-        for (uint32_t i = 0; i < n_prep; i++) { pm.push_back({prep[i], prep_heights[i], prep_widths[i]}); chips.push_back((int)prep_chips[i]); }
-        CoverageReport rep = coverage_audit_host(machine->desc, m, chips, pm, coverage_opts(opts));
-        rep.host_ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        *out = coverage_report_handle(rep);
-    })
+    return audit_on_host<ConstraintHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                               [&](auto&... a) { return coverage_audit_host(a..., coverage_opts(opts)); });
 }
-uint64_t vgpu_coverage_report_len(const vgpu_coverage_report_t* r) { return r ? r->words.size() : 0; }
-const uint32_t* vgpu_coverage_report_words(const vgpu_coverage_report_t* r) { return r ? r->words.data() : nullptr; }
-void vgpu_coverage_report_timing(const vgpu_coverage_report_t* r, double out[3]) { out[0] = r ? r->device_ms : 0; out[1] = r ? r->host_ms : 0; out[2] = r ? r->evaluations : 0; }
+uint64_t vgpu_coverage_report_len(const vgpu_coverage_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_coverage_report_words(const vgpu_coverage_report_t* r) { return report_words(r); }
+void vgpu_coverage_report_timing(const vgpu_coverage_report_t* r, double out[3]) { report_timing(r, out, 3); }
 void vgpu_coverage_report_free(vgpu_coverage_report_t* r) { delete r; }
 
 // Asynchronous prove: the call returns at once; the proof is produced by a host thread of its own driving this prover's

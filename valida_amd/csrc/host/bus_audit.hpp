@@ -4,7 +4,7 @@
 // argument reduces a tuple as sum_j f_j beta^j, machine/src/chip.rs:121-208, so a trailing zero field is invisible to it); a tuple is
 // unbalanced when its sends minus its receives are non-zero in F_p.  This header holds what the host and the device implementation
 // share — the plan (record ids, bus table, the device descriptor), the report and its flat word image — and the host implementation of
-// the contract over host matrices (plain C++, no device).  The device pass is Prover::bus_audit (prover.cpp, kernels/bus_audit.hip).
+// the contract over host matrices (plain C++, no device).  The device pass is Prover::bus_audit (prover_audits.cpp, kernels/bus_audit.hip).
 #pragma once
 #include <algorithm>
 #include <cstring>

@@ -6,7 +6,7 @@
 // non-zero.  Only Air::eval is audited (the permutation constraints depend on sampled challenges; their exact statement is the bus audit).
 // This header holds what the host and the device implementation share — options, shape validation, the report and its flat word image — and the
 // host implementation over canonical row-major matrices (plain C++, one thread, no device).  The device pass is Prover::constraint_audit
-// (prover.cpp, kernels/constraint_audit.hip).
+// (prover_audits.cpp, kernels/constraint_audit.hip).
 #pragma once
 #include <stdexcept>
 #include <string>

@@ -14,7 +14,7 @@
 // witness or of the AIR.  "Shadowed" does not mean removable: a constraint that is never alone against one-cell changes may be the only guard
 // against a two-cell change.
 // This header holds what the host and the device implementation share — options, the report and its flat word image — and the host
-// implementation (plain C++, one thread, no device, no limits).  The device pass is Prover::coverage_audit (prover.cpp,
+// implementation (plain C++, one thread, no device, no limits).  The device pass is Prover::coverage_audit (prover_audits.cpp,
 // kernels/coverage_audit.hip).
 #pragma once
 #include "mutation_audit.hpp"

@@ -20,7 +20,7 @@
 // usually means "this chip delegates" (cpu's read values, shift's output): the finding is a field that also floats on the receiving chip.
 // Inputs are not functions of outputs: lt's operands are expected to float.
 // This header holds what host and device share — the report and its word image — and the host implementation (plain C++, one thread, no
-// limits).  Options are the rank audit's.  The device pass is Prover::field_audit (prover.cpp, kernels/field_audit.hip).
+// limits).  Options are the rank audit's.  The device pass is Prover::field_audit (prover_audits.cpp, kernels/field_audit.hip).
 #pragma once
 #include <functional>
 #include "rank_audit.hpp"

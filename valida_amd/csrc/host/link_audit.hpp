@@ -14,7 +14,7 @@
 // "open" means that no single record's own chip pins the position: a joint move may still be blocked by a sister record.  "Anchored" is per
 // tuple as it stands: a lookup bus whose receiver can move multiplicities between tuples is not modelled.
 // This header holds what host and device share — the options, the report and its word image, the finishing step — and the host
-// implementation (plain C++, one thread, no limit beyond the 32-field bus).  The device pass is Prover::link_audit (prover.cpp,
+// implementation (plain C++, one thread, no limit beyond the 32-field bus).  The device pass is Prover::link_audit (prover_audits.cpp,
 // kernels/link_audit.hip).
 #pragma once
 #include "bus_audit.hpp"

@@ -15,7 +15,7 @@
 // definition.  It is a statement about single-cell slack on THIS witness, not a soundness proof.
 // This header holds what the host and the device implementation share — options, the column flags, the report and its flat word image — and
 // the host implementation over canonical row-major matrices (plain C++, one thread, no device, any number of constraints).  The device pass is
-// Prover::mutation_audit (prover.cpp, kernels/mutation_audit.hip).
+// Prover::mutation_audit (prover_audits.cpp, kernels/mutation_audit.hip).
 #pragma once
 #include <algorithm>
 #include <stdexcept>

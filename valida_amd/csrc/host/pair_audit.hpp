@@ -15,7 +15,7 @@
 //                  the singles' detectors: compensated = 0 and free = rows where both singles are free.  Uncoupled pairs are not evaluated.
 // It covers same-row pairs only; cross-row pairs and triples are not looked for.  It is a statement about THIS witness, not a soundness proof.
 // This header holds what the host and the device implementation share — options, coupling sets, bus masks, the report and its word image —
-// and the host implementation (plain C++, one thread, no limits).  The device pass is Prover::pair_audit (prover.cpp, kernels/pair_audit.hip).
+// and the host implementation (plain C++, one thread, no limits).  The device pass is Prover::pair_audit (prover_audits.cpp, kernels/pair_audit.hip).
 #pragma once
 #include "mutation_audit.hpp"
 

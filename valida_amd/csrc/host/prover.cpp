@@ -5,9 +5,6 @@
 
 namespace vhost {
 
-using Clock = std::chrono::steady_clock;
-static double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
-
 static Ext5 ext_from_canonical(const uint32_t* w) { Ext5 e; for (int k = 0; k < 5; k++) e.c[k] = Fp::from_canonical(w[k]); return e; }
 static void ext_to_canonical(const Ext5& e, uint32_t* w) { for (int k = 0; k < 5; k++) w[k] = e.c[k].canonical(); }
 
@@ -1125,1494 +1122,6 @@ PcsOpening Prover::open_multi_batches(const std::vector<OpenRound>& rounds, Chal
     for (auto& f : fix) res.proof_words[f.first] = f.second;
     res.ms_queries = ms_since(t0);
     return res;
-}
-
-
-// ---- bus audit (host/bus_audit.hpp; kernels/bus_audit.hip) ------------------------------------------------------------------------------
-namespace {
-struct BusAuditNoMemory : std::bad_alloc {  // the pool cannot give the pass its scratch: VGPU_ERR_OOM with a message that says how much it needs
-    std::string msg;
-    explicit BusAuditNoMemory(std::string m) : msg(std::move(m)) {}
-    const char* what() const noexcept override { return msg.c_str(); }
-};
-}  // namespace
-
-BusReport Prover::bus_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const BusAuditOpts& opts_in) {
-    const auto t_host = Clock::now();
-    const BusAuditOpts o = bus_audit_checked_opts(opts_in);
-    std::vector<BusShape> ms, ps;
-    std::vector<int> prep_chips, prep_slot;
-    for (auto t : main) { if (!t) throw std::invalid_argument("bus_audit: null trace"); ms.push_back({t->height, t->width}); }
-    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("bus_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
-    BusPlan plan = bus_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
-    const uint64_t n = plan.n_slots;
-    if (n >= 0xffffffffull) throw std::invalid_argument("bus_audit: more than 2^32 - 2 (row, interaction) pairs; record ids are 32-bit");
-
-    DeviceCtx& c = *ctx_;
-    c.activate();
-    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
-    c.activate();
-    struct Running {
-        std::atomic<int>& n;
-        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
-        ~Running() { n.fetch_sub(1); }
-    } running(c.proofs_running);
-    const size_t NC = machine_.airs.size(), NB = plan.buses.size();
-    hipStream_t st = c.stream;
-
-    BusReport rep;
-    rep.buses = plan.buses;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
-    VG_HIP_CHECK(hipEventCreate(&ev0));
-    VG_HIP_CHECK(hipEventCreate(&ev1));
-    try {
-        // working-layout copies, as prove makes them (traces generated on the device are already column-major Montgomery)
-        std::vector<DMat> own;
-        std::vector<const uint32_t*> mptr(NC, nullptr), pptr(NC, nullptr);
-        std::vector<uint64_t> mstride(NC, 0), pstride(NC, 0);
-        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
-            if (!t->nat.empty()) return t->nat.view();
-            own.emplace_back(&c, t->height, t->width);
-            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
-            return own.back().view();
-        };
-        own.reserve(NC + preprocessed.size());
-        VG_HIP_CHECK(hipEventRecord(ev0, st));
-        for (size_t i = 0; i < NC; i++) {
-            if (!plan.chips[i].M) continue;  // a chip without interactions is not read
-            const vk::DMatView v = working(main[i]);
-            mptr[i] = v.data; mstride[i] = v.stride;
-            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); pptr[i] = pv.data; pstride[i] = pv.stride; }
-        }
-        c.check_launch("bus_audit ingest");
-        DBuf desc(&c, bus_audit_descriptor(machine_, plan, mptr, mstride, pptr, pstride));
-
-        uint32_t total_inter = 0;
-        std::vector<uint32_t> inter_base(NC, 0);
-        for (size_t i = 0; i < NC; i++) { inter_base[i] = total_inter; total_inter += plan.chips[i].M; }
-        const size_t n_counters = 8 + NB + total_inter;
-        const uint64_t na = n ? n : 1;
-        DBuf keys2(&c, (size_t)(4 * na)), ids2(&c, (size_t)(2 * na)), cnt(&c, (size_t)na), gid(&c, (size_t)na), head_pos(&c, (size_t)na), sums(&c, (size_t)(4 * na)),
-            nrec(&c, (size_t)(2 * na)), sort_tmp(&c, vk::bus_audit_sort_scratch_words(na)), scan_tmp(&c, vk::bus_audit_scan_scratch_words(na)), counters(&c, n_counters);
-        unsigned long long* keys = (unsigned long long*)keys2.data;
-        unsigned long long* sums_p = (unsigned long long*)sums.data;
-        VG_HIP_CHECK(hipMemsetAsync(counters.data, 0, n_counters * 4, st));
-        VG_HIP_CHECK(hipMemsetAsync(sums.data, 0, (size_t)(4 * na) * 4, st));
-        VG_HIP_CHECK(hipMemsetAsync(nrec.data, 0, (size_t)(2 * na) * 4, st));
-
-        for (size_t i = 0; i < NC; i++)
-            vk::launch_ba_records(st, desc.data, (uint32_t)i, plan.chips[i].height, machine_.airs[i].width, plan.chips[i].M, o.hash_bits, keys, ids2.data, cnt.data,
-                                  counters.data + 8 + NB + inter_base[i]);
-        int shifts[8], n_shifts = 0;
-        for (uint32_t b = 0; b < (o.hash_bits + 7) / 8; b++) shifts[n_shifts++] = 8 * (int)b;
-        if (o.hash_bits <= 56) shifts[n_shifts++] = 56;  // the pass that sinks the dead slots (key ~0) behind the live ones
-        int half = vk::launch_ba_sort(st, keys, ids2.data, n, sort_tmp.data, shifts, n_shifts, 0);
-        vk::launch_ba_groups(st, desc.data, keys + (uint64_t)half * n, ids2.data + (uint64_t)half * n, n, false, gid.data, head_pos.data, scan_tmp.data, counters.data);
-        vk::launch_ba_reduce(st, desc.data, ids2.data + (uint64_t)half * n, cnt.data, gid.data, head_pos.data, n, true, sums_p, nrec.data, counters.data);
-        vk::launch_ba_select(st, desc.data, ids2.data + (uint64_t)half * n, head_pos.data, sums_p, n, false, 0, nullptr, nullptr, counters.data);
-        c.check_launch("bus_audit");
-        std::vector<uint32_t> cw(n_counters);
-        c.download_small(cw.data(), counters.data, n_counters * 4);
-
-        if (cw[2]) {
-            // a key collision (with 64 key bits: practically never; the hash_bits test hook forces it): group by the full padded tuples instead.
-            // Words [bus slot, field 0, ..]: two per radix sort, least significant pair first; the sorts are stable, ids start ascending.
-            VG_HIP_CHECK(hipMemsetAsync(counters.data + 1, 0, (7 + NB) * 4, st));
-            VG_HIP_CHECK(hipMemsetAsync(sums.data, 0, (size_t)(4 * na) * 4, st));
-            VG_HIP_CHECK(hipMemsetAsync(nrec.data, 0, (size_t)(2 * na) * 4, st));
-            const int all[8] = {0, 8, 16, 24, 32, 40, 48, 56};
-            half = 0;
-            vk::launch_ba_iota(st, ids2.data, n);
-            for (int chunk = (int)(plan.wmax + 1 + 1) / 2 - 1; chunk >= 0; chunk--) {
-                vk::launch_ba_rekey(st, desc.data, (uint32_t)chunk, ids2.data + (uint64_t)half * n, cnt.data, keys + (uint64_t)half * n, n);
-                half = vk::launch_ba_sort(st, keys, ids2.data, n, sort_tmp.data, all, 8, half);
-            }
-            vk::launch_ba_groups(st, desc.data, keys + (uint64_t)half * n, ids2.data + (uint64_t)half * n, n, true, gid.data, head_pos.data, scan_tmp.data, counters.data);
-            vk::launch_ba_reduce(st, desc.data, ids2.data + (uint64_t)half * n, cnt.data, gid.data, head_pos.data, n, false, sums_p, nrec.data, counters.data);
-            vk::launch_ba_select(st, desc.data, ids2.data + (uint64_t)half * n, head_pos.data, sums_p, n, false, 0, nullptr, nullptr, counters.data);
-            c.check_launch("bus_audit exact");
-            c.download_small(cw.data(), counters.data, n_counters * 4);
-        }
-        const uint32_t n_unb = cw[3];
-        rep.total_unbalanced = n_unb;
-        for (size_t b = 0; b < NB; b++) rep.buses[b].unbalanced = cw[8 + b];
-        for (size_t i = 0; i < NC; i++)
-            for (uint32_t m = 0; m < plan.chips[i].M; m++) {
-                BusStat& b = rep.buses[plan.chips[i].bus_slot[m]];
-                const uint64_t live = cw[8 + NB + inter_base[i] + m];
-                b.live += live;
-                (machine_.airs[i].interactions[m].is_send() ? b.sends : b.receives) += live;
-            }
-        if (n_unb) {
-            const uint32_t n_rep = (uint32_t)std::min<uint64_t>(n_unb, o.max_tuples), R = o.max_records_per_tuple, stride = 8 + plan.wmax + 2 * R;
-            DBuf ukeys(&c, (size_t)4 * n_unb), uvals(&c, (size_t)2 * n_unb), out(&c, (size_t)n_rep * stride);
-            vk::launch_ba_select(st, desc.data, ids2.data + (uint64_t)half * n, head_pos.data, sums_p, cw[1], true, n_unb, (unsigned long long*)ukeys.data, uvals.data, counters.data);
-            const int id_bytes[4] = {0, 8, 16, 24};  // keys are 32-bit record ids
-            const int uh = vk::launch_ba_sort(st, (unsigned long long*)ukeys.data, uvals.data, n_unb, sort_tmp.data, id_bytes, 4, 0);
-            vk::launch_ba_report(st, desc.data, ids2.data + (uint64_t)half * n, cnt.data, head_pos.data, sums_p, nrec.data, uvals.data + (uint64_t)uh * n_unb, n_rep, R, out.data);
-            c.check_launch("bus_audit report");
-            std::vector<uint32_t> w((size_t)n_rep * stride);
-            c.download_small(w.data(), out.data, w.size() * 4);
-            for (uint32_t t = 0; t < n_rep; t++) {
-                const uint32_t* e = w.data() + (size_t)t * stride;
-                const BusStat& bus = plan.buses.at(e[0]);
-                BusTuple bt;
-                bt.is_global = bus.is_global; bt.bus_index = bus.bus_index;
-                bt.fields.assign(e + 8, e + 8 + bus.width);
-                bt.send_sum = (uint32_t)((((uint64_t)e[3] << 32) | e[2]) % vg::P);
-                bt.recv_sum = (uint32_t)((((uint64_t)e[5] << 32) | e[4]) % vg::P);
-                bt.net = (bt.send_sum + vg::P - bt.recv_sum) % vg::P;
-                bt.n_send = e[6]; bt.n_recv = e[7];
-                for (uint32_t k = 0; k < e[1] && k < R; k++) {
-                    BusRecord r = plan.decode(e[8 + plan.wmax + 2 * k]);
-                    r.is_send = machine_.airs[r.chip].interactions[r.interaction].is_send() ? 1u : 0u;
-                    r.count = e[8 + plan.wmax + 2 * k + 1];
-                    bt.records.push_back(r);
-                }
-                rep.tuples.push_back(std::move(bt));
-            }
-        }
-        VG_HIP_CHECK(hipEventRecord(ev1, st));
-        c.sync();
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
-    } catch (const BusAuditNoMemory&) {
-        throw;
-    } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(st);
-        throw BusAuditNoMemory("bus_audit: the device pool cannot give the pass its scratch: " + std::to_string(BUS_AUDIT_BYTES_PER_SLOT) + " bytes for each of the " +
-                               std::to_string(n) + " (row, interaction) pairs, 24 more per unbalanced tuple, plus the working-layout copies of uploaded traces");
-    }
-    bus_audit_finish(rep, o);
-    rep.host_ms = ms_since(t_host);
-    return rep;
-}
-
-// ---- constraint audit (host/constraint_audit.hpp; kernels/constraint_audit.hip) ------------------------------------------------------------
-ConstraintReport Prover::constraint_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
-                                          const ConstraintAuditOpts& opts_in) {
-    const auto t_host = Clock::now();
-    const ConstraintAuditOpts o = constraint_audit_checked_opts(opts_in);
-    std::vector<ConstraintShape> ms, ps;
-    std::vector<int> prep_chips, prep_slot;
-    for (auto t : main) { if (!t) throw std::invalid_argument("constraint_audit: null trace"); ms.push_back({t->height, t->width}); }
-    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("constraint_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
-    constraint_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
-    const size_t NC = machine_.airs.size();
-    for (size_t i = 0; i < NC; i++)
-        if (machine_.airs[i].program.num_asserts > vk::CA_MAX_CONSTRAINTS)
-            throw std::invalid_argument("constraint_audit: chip " + machine_.airs[i].name + " has " + std::to_string(machine_.airs[i].program.num_asserts) + " constraints; the device audit handles up to " +
-                                        std::to_string(vk::CA_MAX_CONSTRAINTS) + " per chip (the host audit has no limit)");
-
-    DeviceCtx& c = *ctx_;
-    c.activate();
-    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
-    c.activate();
-    struct Running {
-        std::atomic<int>& n;
-        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
-        ~Running() { n.fetch_sub(1); }
-    } running(c.proofs_running);
-    hipStream_t st = c.stream;
-
-    ConstraintReport rep;
-    rep.chips.resize(NC);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
-    VG_HIP_CHECK(hipEventCreate(&ev0));
-    VG_HIP_CHECK(hipEventCreate(&ev1));
-    uint64_t scratch_words = 0;
-    try {
-        // working-layout copies, as prove makes them (traces generated on the device are already column-major Montgomery)
-        std::vector<DMat> own;
-        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
-            if (!t->nat.empty()) return t->nat.view();
-            own.emplace_back(&c, t->height, t->width);
-            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
-            return own.back().view();
-        };
-        own.reserve(NC + preprocessed.size());
-        // per chip: the launch shape and its slice of the scratch (u32 words): totals [2 (K + 1)], table [K NB], prefix [K NB]
-        std::vector<vk::CaArgs> args(NC);
-        std::vector<uint64_t> tot_at(NC, 0), tab_at(NC, 0), pre_at(NC, 0);
-        uint64_t zeroed = 0;
-        for (size_t i = 0; i < NC; i++) {
-            const AirDesc& air = machine_.airs[i];
-            vk::CaArgs& a = args[i];
-            a = vk::CaArgs{};
-            a.K = air.program.num_asserts;
-            rep.chips[i].n_constraints = a.K; rep.chips[i].height = main[i]->height;
-            if (!a.K) continue;  // a chip without constraints (program, mem, div, range) is not read
-            const vk::DMatView v = working(main[i]);
-            a.main = v.data; a.mstride = v.stride; a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
-            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
-            a.prog = (const vair::Instr*)prog_dev_[i].data;
-            a.n_instrs = (uint32_t)air.program.instrs.size();
-            a.n_regs = air.program.num_regs;
-            a.native_chip = fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip;
-            a.T = vk::ca_block_threads(a);
-            a.NB = (uint32_t)((a.n + a.T - 1) / a.T);
-            tot_at[i] = zeroed; zeroed += 2 * (uint64_t)(a.K + 1);
-            tab_at[i] = zeroed; zeroed += ((uint64_t)a.K * a.NB + 1) & ~1ull;  // the next chip's u64 totals stay 8-byte aligned
-        }
-        scratch_words = zeroed;
-        for (size_t i = 0; i < NC; i++) if (args[i].K) { pre_at[i] = scratch_words; scratch_words += (uint64_t)args[i].K * args[i].NB; }
-        c.check_launch("constraint_audit ingest");
-        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
-        // the device pass: everything from here to the last download is between the two events (the working-layout copies of uploaded traces,
-        // which a proof makes as well, are before them)
-        VG_HIP_CHECK(hipEventRecord(ev0, st));
-        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)zeroed * 4, st));
-        for (size_t i = 0; i < NC; i++)
-            if (args[i].K) vk::launch_ca_count(st, args[i], reinterpret_cast<unsigned long long*>(scratch.data + tot_at[i]), scratch.data + tab_at[i]);
-        c.check_launch("constraint_audit count");
-        // the totals of all chips lie in front of their tables: gather them with one small copy per chip
-        std::vector<std::vector<uint64_t>> counts(NC);
-        {
-            std::vector<uint32_t> tw;
-            for (size_t i = 0; i < NC; i++) {
-                const uint32_t K = args[i].K;
-                counts[i].assign(K, 0);
-                if (!K) continue;
-                tw.resize(2 * (size_t)(K + 1));
-                c.download_small(tw.data(), scratch.data + tot_at[i], tw.size() * 4);
-                for (uint32_t k = 0; k < K; k++) counts[i][k] = ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k];
-                rep.chips[i].failing_rows = ((uint64_t)tw[2 * K + 1] << 32) | tw[2 * K];
-            }
-        }
-        constraint_audit_finish(rep, counts, o);
-        const uint32_t R = o.max_rows_per_constraint;
-        for (size_t e0 = 0; e0 < rep.constraints.size();) {
-            // the listed constraints of one chip: scan, list, values, one download
-            const uint32_t chip = rep.constraints[e0].chip;
-            size_t e1 = e0;
-            vk::CaListed listed{};
-            while (e1 < rep.constraints.size() && rep.constraints[e1].chip == chip) { const uint32_t k = rep.constraints[e1].constraint; listed.w[k >> 5] |= 1u << (k & 31u); e1++; }
-            const vk::CaArgs& a = args[chip];
-            DBuf out(&c, (size_t)2 * a.K * R);
-            uint32_t* rows = out.data;
-            uint32_t* values = out.data + (size_t)a.K * R;
-            vk::launch_ca_scan(st, a, scratch.data + tab_at[chip], scratch.data + pre_at[chip], listed);
-            vk::launch_ca_list(st, a, scratch.data + tab_at[chip], scratch.data + pre_at[chip], listed, R, rows);
-            vk::launch_ca_values(st, a, reinterpret_cast<const unsigned long long*>(scratch.data + tot_at[chip]), listed, R, rows, values);
-            c.check_launch("constraint_audit list");
-            std::vector<uint32_t> w((size_t)2 * a.K * R);
-            c.download_small(w.data(), out.data, w.size() * 4);
-            for (size_t e = e0; e < e1; e++) {
-                ConstraintEntry& en = rep.constraints[e];
-                const uint64_t listed_rows = std::min<uint64_t>(en.failing_rows, R);
-                for (uint64_t j = 0; j < listed_rows; j++) en.rows.push_back({w[(size_t)en.constraint * R + j], w[(size_t)a.K * R + (size_t)en.constraint * R + j]});
-            }
-            e0 = e1;
-        }
-        VG_HIP_CHECK(hipEventRecord(ev1, st));
-        c.sync();
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
-    } catch (const BusAuditNoMemory&) {
-        throw;
-    } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(st);
-        throw BusAuditNoMemory("constraint_audit: the device pool cannot give the pass its scratch: 8 bytes per (constraint, workgroup of 256 rows) of every chip (" +
-                               std::to_string(scratch_words * 4) + " bytes for this witness), 8 more per listed row, plus the working-layout copies of uploaded traces");
-    }
-    rep.host_ms = ms_since(t_host);
-    return rep;
-}
-
-// ---- mutation audit (host/mutation_audit.hpp; kernels/mutation_audit.hip) ------------------------------------------------------------------
-MutationReport Prover::mutation_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
-                                      const MutationAuditOpts& opts_in) {
-    const auto t_host = Clock::now();
-    const MutationAuditOpts o = mutation_audit_checked_opts(opts_in);
-    std::vector<ConstraintShape> ms, ps;
-    std::vector<int> prep_chips, prep_slot;
-    for (auto t : main) { if (!t) throw std::invalid_argument("mutation_audit: null trace"); ms.push_back({t->height, t->width}); }
-    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("mutation_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
-    mutation_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
-    const size_t NC = machine_.airs.size();
-    for (size_t i = 0; i < NC; i++)
-        if (machine_.airs[i].program.num_asserts > vk::CA_MAX_CONSTRAINTS)
-            throw std::invalid_argument("mutation_audit: chip " + machine_.airs[i].name + " has " + std::to_string(machine_.airs[i].program.num_asserts) + " constraints; the device audit handles up to " +
-                                        std::to_string(vk::CA_MAX_CONSTRAINTS) + " per chip (the host audit has no limit)");
-    const uint32_t D = o.n_deltas, R = o.max_rows_per_entry;
-
-    DeviceCtx& c = *ctx_;
-    c.activate();
-    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
-    c.activate();
-    struct Running {
-        std::atomic<int>& n;
-        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
-        ~Running() { n.fetch_sub(1); }
-    } running(c.proofs_running);
-    hipStream_t st = c.stream;
-
-    MutationReport rep;
-    rep.chips.resize(NC);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
-    VG_HIP_CHECK(hipEventCreate(&ev0));
-    VG_HIP_CHECK(hipEventCreate(&ev1));
-    uint64_t scratch_words = 0, rows_words = 0;
-    try {
-        // working-layout copies, as prove makes them (traces generated on the device are already column-major Montgomery)
-        std::vector<DMat> own;
-        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
-            if (!t->nat.empty()) return t->nat.view();
-            own.emplace_back(&c, t->height, t->width);
-            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
-            return own.back().view();
-        };
-        own.reserve(NC + preprocessed.size());
-        // per chip: the launch shape, its column flags and its slice of the scratch (u32 words): totals [6 E], table [E NB], prefix [E NB]
-        std::vector<vk::MaArgs> args(NC);
-        std::vector<uint64_t> tot_at(NC, 0), tab_at(NC, 0), pre_at(NC, 0), flag_at(NC, 0);
-        std::vector<uint32_t> flag_words;
-        uint64_t zeroed = 0;
-        for (size_t i = 0; i < NC; i++) {
-            const AirDesc& air = machine_.airs[i];
-            vk::MaArgs& a = args[i];
-            a = vk::MaArgs{};
-            a.K = air.program.num_asserts;
-            rep.chips[i].width = air.width; rep.chips[i].n_constraints = a.K; rep.chips[i].height = main[i]->height;
-            const double evaluations = ma_evaluations(air, main[i]->height, D);
-            rep.evaluations += evaluations;
-            if (!air.width) continue;
-            const vk::DMatView v = working(main[i]);
-            a.main = v.data; a.mstride = v.stride; a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
-            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
-            a.prog = (const vair::Instr*)prog_dev_[i].data;
-            a.n_instrs = (uint32_t)air.program.instrs.size();
-            a.n_regs = air.program.num_regs;
-            a.iw = iw_dev_[i].data;
-            a.evaluations = evaluations;
-            a.D = D;
-            for (uint32_t k = 0; k < D; k++) a.delta[k] = Fp::from_canonical(o.deltas[k]).v;
-            a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
-            a.T = vk::ma_block_threads(a);
-            a.NB = (uint32_t)((a.n + a.T - 1) / a.T);
-            a.CY = vk::ma_column_slices(a, a.NB);
-            const double baselines = a.K ? (a.n == 1 ? 1.0 : 2.0) * (double)a.n * (a.CY - 1) : 0;  // every column slice evaluates the baselines of its rows
-            a.evaluations += baselines; rep.evaluations += baselines;
-            const std::vector<uint32_t> fl = ma_column_flags(air);
-            bool masks_ok = false;
-            const std::vector<uint32_t> bm = ma_bus_masks(air, masks_ok);
-            a.bus_walk = masks_ok ? 0u : 1u;
-            flag_at[i] = flag_words.size();
-            flag_words.insert(flag_words.end(), fl.begin(), fl.end());
-            flag_words.insert(flag_words.end(), bm.begin(), bm.end());
-            const uint64_t E = (uint64_t)a.width * D;
-            tot_at[i] = zeroed; zeroed += 6 * E;
-            tab_at[i] = zeroed; zeroed += (E * a.NB + 1) & ~1ull;  // the next chip's u64 totals stay 8-byte aligned
-            rows_words = std::max<uint64_t>(rows_words, E * R);
-        }
-        scratch_words = zeroed;
-        for (size_t i = 0; i < NC; i++) if (args[i].width) { pre_at[i] = scratch_words; scratch_words += (uint64_t)args[i].width * D * args[i].NB; }
-        if (flag_words.empty()) flag_words.push_back(0);
-        DBuf flags(&c, flag_words);
-        for (size_t i = 0; i < NC; i++) args[i].flags = flags.data + flag_at[i];
-        c.check_launch("mutation_audit ingest");
-        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
-        DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
-        // the device pass: everything from here to the last download is between the two events (the working-layout copies of uploaded traces,
-        // which a proof makes as well, are before them)
-        VG_HIP_CHECK(hipEventRecord(ev0, st));
-        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)zeroed * 4, st));
-        for (size_t i = 0; i < NC; i++)
-            if (args[i].width) vk::launch_ma_count(st, args[i], reinterpret_cast<unsigned long long*>(scratch.data + tot_at[i]), scratch.data + tab_at[i]);
-        c.check_launch("mutation_audit count");
-        std::vector<std::vector<uint64_t>> counts(NC);
-        {
-            std::vector<uint32_t> tw;
-            for (size_t i = 0; i < NC; i++) {
-                const size_t E = (size_t)args[i].width * D;
-                counts[i].assign(3 * E, 0);
-                if (!E) continue;
-                tw.resize(6 * E);
-                c.download_small(tw.data(), scratch.data + tot_at[i], tw.size() * 4);
-                for (size_t k = 0; k < 3 * E; k++) counts[i][k] = ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k];
-            }
-        }
-        mutation_audit_finish(rep, counts, o);
-        for (size_t e0 = 0; e0 < rep.entries.size();) {
-            // the listed entries of one chip: scan, list, one download
-            const uint32_t chip = rep.entries[e0].chip;
-            size_t e1 = e0;
-            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
-            const vk::MaArgs& a = args[chip];
-            const uint32_t e_cut = rep.entries[e1 - 1].column * D + rep.entries[e1 - 1].delta + 1;  // entries ascend: the listed ones of a chip are a prefix
-            vk::launch_ma_scan(st, a, reinterpret_cast<const unsigned long long*>(scratch.data + tot_at[chip]), scratch.data + tab_at[chip], scratch.data + pre_at[chip], e_cut);
-            vk::launch_ma_list(st, a, scratch.data + tab_at[chip], scratch.data + pre_at[chip], e_cut, R, out.data);
-            c.check_launch("mutation_audit list");
-            std::vector<uint32_t> w((size_t)e_cut * R);
-            c.download_small(w.data(), out.data, w.size() * 4);
-            for (size_t e = e0; e < e1; e++) {
-                MutationEntry& en = rep.entries[e];
-                const uint64_t listed = std::min<uint64_t>(en.free_, R);
-                const size_t at = ((size_t)en.column * D + en.delta) * R;
-                en.rows.assign(w.begin() + at, w.begin() + at + listed);
-            }
-            e0 = e1;
-        }
-        VG_HIP_CHECK(hipEventRecord(ev1, st));
-        c.sync();
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
-    } catch (const BusAuditNoMemory&) {
-        throw;
-    } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(st);
-        throw BusAuditNoMemory("mutation_audit: the device pool cannot give the pass its scratch: 8 bytes per (column, delta, workgroup of rows) and 24 per (column, delta) of every chip (" +
-                               std::to_string(scratch_words * 4) + " bytes for this witness), " + std::to_string(rows_words * 4) + " bytes of listed rows (4 x columns x deltas x max_rows_per_entry of the widest chip), plus the working-layout copies of uploaded traces");
-    }
-    rep.host_ms = ms_since(t_host);
-    return rep;
-}
-
-// ---- pair audit (host/pair_audit.hpp; kernels/pair_audit.hip) ------------------------------------------------------------------------------
-PairReport Prover::pair_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const PairAuditOpts& opts_in) {
-    const auto t_host = Clock::now();
-    const PairAuditOpts o = pair_audit_checked_opts(opts_in, machine_.airs.size());
-    std::vector<ConstraintShape> ms, ps;
-    std::vector<int> prep_chips, prep_slot;
-    for (auto t : main) { if (!t) throw std::invalid_argument("pair_audit: null trace"); ms.push_back({t->height, t->width}); }
-    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("pair_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
-    pair_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
-    const size_t NC = machine_.airs.size();
-    for (size_t i = 0; i < NC; i++) {
-        if (!pair_audit_selected(o, i)) continue;
-        if (machine_.airs[i].program.num_asserts > vk::CA_MAX_CONSTRAINTS)
-            throw std::invalid_argument("pair_audit: chip " + machine_.airs[i].name + " has " + std::to_string(machine_.airs[i].program.num_asserts) + " constraints; the device audit handles up to " +
-                                        std::to_string(vk::CA_MAX_CONSTRAINTS) + " per chip (the host audit has no limit)");
-        if (machine_.airs[i].width > 4096)
-            throw std::invalid_argument("pair_audit: chip " + machine_.airs[i].name + " has more than 4096 columns; the device audit handles up to 4096 (the host audit up to 65535)");
-    }
-    const uint32_t D = o.n_deltas, DD = D * D, R = o.max_rows_per_entry;
-
-    DeviceCtx& c = *ctx_;
-    c.activate();
-    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
-    c.activate();
-    struct Running {
-        std::atomic<int>& n;
-        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
-        ~Running() { n.fetch_sub(1); }
-    } running(c.proofs_running);
-    hipStream_t st = c.stream;
-
-    PairReport rep;
-    rep.chips.resize(NC);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
-    VG_HIP_CHECK(hipEventCreate(&ev0));
-    VG_HIP_CHECK(hipEventCreate(&ev1));
-    uint64_t scratch_words = 0, rows_words = 0, desc_words_n = 0;
-    try {
-        std::vector<DMat> own;
-        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
-            if (!t->nat.empty()) return t->nat.view();
-            own.emplace_back(&c, t->height, t->width);
-            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
-            return own.back().view();
-        };
-        own.reserve(NC + preprocessed.size());
-        // per chip: the launch shape, its descriptor words (column flags and bus masks, the coupled pairs, the pairs' bus masks) and its slice
-        // of the scratch (u32 words): totals, table [E NB], prefix [E NB]
-        std::vector<vk::PaArgs> args(NC);
-        std::vector<std::vector<uint32_t>> pairs(NC);
-        std::vector<uint64_t> tot_at(NC, 0), tab_at(NC, 0), pre_at(NC, 0), flag_at(NC, 0), pair_at(NC, 0), mask_at(NC, 0);
-        std::vector<uint32_t> desc_words;
-        uint64_t zeroed = 0;
-        for (size_t i = 0; i < NC; i++) {
-            const AirDesc& air = machine_.airs[i];
-            vk::PaArgs& v = args[i];
-            v = vk::PaArgs{};
-            vk::MaArgs& a = v.m;
-            a.K = air.program.num_asserts;
-            PairChipStat& cs = rep.chips[i];
-            cs.width = air.width; cs.n_constraints = a.K; cs.n_interactions = (uint32_t)air.interactions.size(); cs.height = main[i]->height;
-            cs.audited = pair_audit_selected(o, i) ? 1u : 0u;
-            if (!cs.audited || !air.width) continue;
-            const vk::DMatView mv = working(main[i]);
-            a.main = mv.data; a.mstride = mv.stride; a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
-            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
-            a.prog = (const vair::Instr*)prog_dev_[i].data;
-            a.n_instrs = (uint32_t)air.program.instrs.size();
-            a.n_regs = air.program.num_regs;
-            a.iw = iw_dev_[i].data;
-            a.D = D;
-            for (uint32_t k = 0; k < D; k++) a.delta[k] = Fp::from_canonical(o.deltas[k]).v;
-            a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
-            pairs[i] = pa_coupled_pairs(air, a.n);
-            v.P = (uint32_t)pairs[i].size();
-            vk::pa_shape(v);
-            a.evaluations = pa_device_evaluations(air, a.n, D, pairs[i], v.PPS, a.CY);
-            rep.evaluations += a.evaluations;
-            const std::vector<uint32_t> fl = ma_column_flags(air);
-            bool masks_ok = false;
-            const std::vector<uint32_t> bm = ma_bus_masks(air, masks_ok);
-            const std::vector<uint32_t> pmk = pa_bus_masks(air, pairs[i], o.deltas, D, masks_ok);
-            a.bus_walk = masks_ok ? 0u : 1u;
-            flag_at[i] = desc_words.size();
-            desc_words.insert(desc_words.end(), fl.begin(), fl.end());
-            desc_words.insert(desc_words.end(), bm.begin(), bm.end());
-            pair_at[i] = desc_words.size();
-            desc_words.insert(desc_words.end(), pairs[i].begin(), pairs[i].end());
-            desc_words.push_back(0);
-            mask_at[i] = desc_words.size();
-            desc_words.insert(desc_words.end(), pmk.begin(), pmk.end());
-            const uint64_t E = (uint64_t)v.P * DD;
-            tot_at[i] = zeroed; zeroed += vk::pa_totals_words(v);
-            tab_at[i] = zeroed; zeroed += (E * a.NB + 1) & ~1ull;  // the next chip's u64 totals stay 8-byte aligned
-        }
-        scratch_words = zeroed;
-        for (size_t i = 0; i < NC; i++) if (args[i].m.width) { pre_at[i] = scratch_words; scratch_words += (uint64_t)args[i].P * DD * args[i].m.NB; }
-        if (desc_words.empty()) desc_words.push_back(0);
-        desc_words_n = desc_words.size();
-        DBuf desc(&c, desc_words);
-        for (size_t i = 0; i < NC; i++) { args[i].m.flags = desc.data + flag_at[i]; args[i].pairs = desc.data + pair_at[i]; args[i].pmasks = desc.data + mask_at[i]; }
-        c.check_launch("pair_audit ingest");
-        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
-        // the device pass: everything from here to the last download is between the two events
-        VG_HIP_CHECK(hipEventRecord(ev0, st));
-        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)zeroed * 4, st));
-        for (size_t i = 0; i < NC; i++)
-            if (args[i].m.width) vk::launch_pa_count(st, args[i], reinterpret_cast<unsigned long long*>(scratch.data + tot_at[i]), scratch.data + tab_at[i]);
-        c.check_launch("pair_audit count");
-        std::vector<std::vector<uint64_t>> counts(NC), ufree(NC);
-        {
-            std::vector<uint32_t> tw;
-            for (size_t i = 0; i < NC; i++) {
-                const size_t E = (size_t)args[i].P * DD;
-                counts[i].assign(2 * E, 0);
-                ufree[i].assign(DD, 0);
-                if (!args[i].m.width) continue;
-                tw.resize(vk::pa_totals_words(args[i]));
-                c.download_small(tw.data(), scratch.data + tot_at[i], tw.size() * 4);
-                auto u64 = [&](size_t k) { return ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k]; };
-                for (size_t k = 0; k < 2 * E; k++) counts[i][k] = u64(k);
-                for (uint32_t q = 0; q < DD; q++) ufree[i][q] = u64(2 * E + q) - u64(2 * E + 16 + q);  // all pairs - coupled pairs: both singles free
-            }
-        }
-        pair_audit_finish(rep, pairs, counts, ufree, o);
-        // entry index of a listed entry within its chip: its pair's position in the coupled list
-        auto entry_index = [&](const PairEntry& en) {
-            const auto& pl = pairs[en.chip];
-            size_t lo = 0, hi = pl.size();
-            while (lo < hi) {  // ascending (c1, c2)
-                const size_t mid = (lo + hi) / 2;
-                const uint32_t m1 = pl[mid] & 0xffffu, m2 = pl[mid] >> 16;
-                if (m1 < en.c1 || (m1 == en.c1 && m2 < en.c2)) lo = mid + 1; else hi = mid;
-            }
-            return (uint64_t)lo * DD + en.q;
-        };
-        for (size_t e0 = 0; e0 < rep.entries.size();) {
-            const uint32_t chip = rep.entries[e0].chip;
-            size_t e1 = e0;
-            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
-            const uint64_t cut = entry_index(rep.entries[e1 - 1]) + 1;
-            rows_words = std::max<uint64_t>(rows_words, cut * R);
-            e0 = e1;
-        }
-        DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
-        for (size_t e0 = 0; e0 < rep.entries.size();) {
-            // the listed entries of one chip: scan, list, one download
-            const uint32_t chip = rep.entries[e0].chip;
-            size_t e1 = e0;
-            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
-            const vk::PaArgs& v = args[chip];
-            const uint32_t e_cut = (uint32_t)(entry_index(rep.entries[e1 - 1]) + 1);  // entries ascend: the listed ones of a chip are below it
-            vk::launch_pa_scan(st, v, reinterpret_cast<const unsigned long long*>(scratch.data + tot_at[chip]), scratch.data + tab_at[chip], scratch.data + pre_at[chip], e_cut);
-            vk::launch_pa_list(st, v, scratch.data + tab_at[chip], scratch.data + pre_at[chip], e_cut, R, out.data);
-            c.check_launch("pair_audit list");
-            std::vector<uint32_t> w((size_t)e_cut * R);
-            c.download_small(w.data(), out.data, w.size() * 4);
-            for (size_t e = e0; e < e1; e++) {
-                PairEntry& en = rep.entries[e];
-                const uint64_t listed = std::min<uint64_t>(en.compensated, R);
-                const size_t at = (size_t)entry_index(en) * R;
-                en.rows.assign(w.begin() + at, w.begin() + at + listed);
-            }
-            e0 = e1;
-        }
-        VG_HIP_CHECK(hipEventRecord(ev1, st));
-        c.sync();
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
-    } catch (const BusAuditNoMemory&) {
-        throw;
-    } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(st);
-        throw BusAuditNoMemory("pair_audit: the device pool cannot give the pass its scratch: 16 bytes per (coupled pair, delta pair) and 8 per (coupled pair, delta pair, workgroup of rows) of every chip (" +
-                               std::to_string(scratch_words * 4) + " bytes for this witness), " + std::to_string(desc_words_n * 4) + " bytes of pair lists and bus masks, " + std::to_string(rows_words * 4) +
-                               " bytes of listed rows, plus the working-layout copies of uploaded traces; chip_mask audits fewer chips at a time");
-    }
-    rep.host_ms = ms_since(t_host);
-    return rep;
-}
-
-// ---- rank audit (host/rank_audit.hpp; kernels/rank_audit.hip) ------------------------------------------------------------------------------
-RankReport Prover::rank_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const RankAuditOpts& opts_in) {
-    const auto t_host = Clock::now();
-    const RankAuditOpts o = rank_audit_checked_opts(opts_in, machine_.airs.size());
-    std::vector<ConstraintShape> ms, ps;
-    std::vector<int> prep_chips, prep_slot;
-    for (auto t : main) { if (!t) throw std::invalid_argument("rank_audit: null trace"); ms.push_back({t->height, t->width}); }
-    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("rank_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
-    rank_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
-    const size_t NC = machine_.airs.size();
-    const uint32_t R = o.max_rows_per_entry;
-    // per chip its launch shape: a chip that does not fit the LDS is refused before anything is queued
-    std::vector<vk::RaArgs> args(NC);
-    RankReport rep;
-    rep.chips.resize(NC);
-    for (size_t i = 0; i < NC; i++) {
-        const AirDesc& air = machine_.airs[i];
-        vk::RaArgs& a = args[i];
-        a = vk::RaArgs{};
-        RankChipStat& cs = rep.chips[i];
-        cs.width = air.width; cs.n_constraints = air.program.num_asserts; cs.n_interactions = (uint32_t)air.interactions.size(); cs.height = main[i]->height;
-        cs.audited = rank_audit_selected(o, i) ? 1u : 0u;
-        cs.loose.assign(air.width, 0); cs.zeros.assign(air.width, 0);
-        if (!cs.audited || !air.width) continue;
-        a.K = air.program.num_asserts;
-        a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
-        a.n_instrs = (uint32_t)air.program.instrs.size();
-        a.n_regs = air.program.num_regs;
-        a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
-        try {
-            vk::ra_shape(a);
-        } catch (const std::invalid_argument& e) {
-            throw std::invalid_argument(std::string(e.what()) + " [chip " + air.name + "; the host audit has no limit]");
-        }
-        a.evaluations = a.K ? (double)a.n * a.width * (a.n == 1 ? 1 : 2) : 0;
-        rep.evaluations += a.evaluations;
-    }
-
-    DeviceCtx& c = *ctx_;
-    c.activate();
-    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
-    c.activate();
-    struct Running {
-        std::atomic<int>& n;
-        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
-        ~Running() { n.fetch_sub(1); }
-    } running(c.proofs_running);
-    hipStream_t st = c.stream;
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
-    VG_HIP_CHECK(hipEventCreate(&ev0));
-    VG_HIP_CHECK(hipEventCreate(&ev1));
-    uint64_t scratch_words = 0, rows_words = 0, desc_words_n = 0;
-    try {
-        std::vector<DMat> own;
-        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
-            if (!t->nat.empty()) return t->nat.view();
-            own.emplace_back(&c, t->height, t->width);
-            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
-            return own.back().view();
-        };
-        own.reserve(NC + preprocessed.size());
-        // per chip: its weight rows and its slice of the scratch (u32 words): totals, table [w NB], prefix [w NB]
-        std::vector<uint64_t> tot_at(NC, 0), tab_at(NC, 0), pre_at(NC, 0), wr_at(NC, 0);
-        std::vector<uint32_t> desc_words;
-        uint64_t zeroed = 0;
-        for (size_t i = 0; i < NC; i++) {
-            vk::RaArgs& a = args[i];
-            if (!a.width) continue;
-            const AirDesc& air = machine_.airs[i];
-            const vk::DMatView mv = working(main[i]);
-            a.main = mv.data; a.mstride = mv.stride;
-            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
-            a.prog = (const vair::Instr*)prog_dev_[i].data;
-            a.iw = iw_dev_[i].data;
-            const std::vector<uint32_t> wr = ra_weight_rows(air);
-            wr_at[i] = desc_words.size();
-            desc_words.insert(desc_words.end(), wr.begin(), wr.end());
-            tot_at[i] = zeroed; zeroed += vk::ra_totals_words(a);
-            tab_at[i] = zeroed; zeroed += ((uint64_t)a.width * a.NB + 1) & ~1ull;  // the next chip's u64 totals stay 8-byte aligned
-        }
-        scratch_words = zeroed;
-        for (size_t i = 0; i < NC; i++) if (args[i].width) { pre_at[i] = scratch_words; scratch_words += (uint64_t)args[i].width * args[i].NB; }
-        if (desc_words.empty()) desc_words.push_back(0);
-        desc_words_n = desc_words.size();
-        DBuf desc(&c, desc_words);
-        for (size_t i = 0; i < NC; i++) args[i].wr = desc.data + wr_at[i];
-        c.check_launch("rank_audit ingest");
-        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
-        // the device pass: everything from here to the last download is between the two events
-        VG_HIP_CHECK(hipEventRecord(ev0, st));
-        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)zeroed * 4, st));
-        for (size_t i = 0; i < NC; i++)
-            if (args[i].width) vk::launch_ra_count(st, args[i], reinterpret_cast<unsigned long long*>(scratch.data + tot_at[i]), scratch.data + tab_at[i]);
-        c.check_launch("rank_audit count");
-        {
-            std::vector<uint32_t> tw;
-            for (size_t i = 0; i < NC; i++) {
-                if (!args[i].width) continue;
-                RankChipStat& cs = rep.chips[i];
-                tw.resize(vk::ra_totals_words(args[i]));
-                c.download_small(tw.data(), scratch.data + tot_at[i], tw.size() * 4);
-                auto u64 = [&](size_t k) { return ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k]; };
-                cs.nullity = u64(0); cs.zero = u64(1); cs.coupled_rows = u64(2); cs.max_nullity = (uint32_t)u64(3);
-                for (uint32_t k = 0; k < cs.width; k++) { cs.loose[k] = u64(4 + 2 * (size_t)k); cs.zeros[k] = u64(5 + 2 * (size_t)k); }
-            }
-        }
-        rank_audit_finish(rep, o);
-        for (size_t e0 = 0; e0 < rep.entries.size();) {
-            const uint32_t chip = rep.entries[e0].chip;
-            size_t e1 = e0;
-            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
-            rows_words = std::max<uint64_t>(rows_words, ((uint64_t)rep.entries[e1 - 1].column + 1) * R * RA_ROW_WORDS);
-            e0 = e1;
-        }
-        DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
-        for (size_t e0 = 0; e0 < rep.entries.size();) {
-            // the listed columns of one chip: scan, list, one download
-            const uint32_t chip = rep.entries[e0].chip;
-            size_t e1 = e0;
-            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
-            const vk::RaArgs& a = args[chip];
-            const uint32_t c_cut = rep.entries[e1 - 1].column + 1;  // entries ascend: the listed columns of a chip are below it
-            const size_t words = (size_t)c_cut * R * RA_ROW_WORDS;
-            VG_HIP_CHECK(hipMemsetAsync(out.data, 0, words * 4, st));  // unused term slots are zero
-            vk::launch_ra_scan(st, a, scratch.data + tab_at[chip], scratch.data + pre_at[chip], c_cut);
-            vk::launch_ra_list(st, a, scratch.data + tab_at[chip], scratch.data + pre_at[chip], c_cut, R, out.data);
-            c.check_launch("rank_audit list");
-            std::vector<uint32_t> w(words);
-            c.download_small(w.data(), out.data, w.size() * 4);
-            for (size_t e = e0; e < e1; e++) {
-                RankEntry& en = rep.entries[e];
-                const uint64_t listed = std::min<uint64_t>(en.coupled, R);
-                en.rows.resize((size_t)listed);
-                for (size_t k = 0; k < listed; k++) {
-                    const uint32_t* src = w.data() + ((size_t)en.column * R + k) * RA_ROW_WORDS;
-                    en.rows[k].row = src[0]; en.rows[k].n_support = src[1];
-                    for (uint32_t x = 0; x < 2 * RA_TERMS; x++) en.rows[k].terms[x] = src[2 + x];
-                }
-            }
-            e0 = e1;
-        }
-        VG_HIP_CHECK(hipEventRecord(ev1, st));
-        c.sync();
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
-    } catch (const BusAuditNoMemory&) {
-        throw;
-    } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(st);
-        throw BusAuditNoMemory("rank_audit: the device pool cannot give the pass its scratch: 32 + 16 bytes per column of totals and 8 per (column, workgroup of rows) of every chip (" +
-                               std::to_string(scratch_words * 4) + " bytes for this witness), " + std::to_string(desc_words_n * 4) + " bytes of interaction weight rows, " + std::to_string(rows_words * 4) +
-                               " bytes of listed rows (72 per (listed column, row slot)), plus the working-layout copies of uploaded traces; chip_mask audits fewer chips at a time");
-    }
-    rep.host_ms = ms_since(t_host);
-    return rep;
-}
-
-// ---- step audit (host/step_audit.hpp; kernels/step_audit.hip) ------------------------------------------------------------------------------
-StepReport Prover::step_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const StepAuditOpts& opts_in) {
-    const auto t_host = Clock::now();
-    const StepAuditOpts o = step_audit_checked_opts(opts_in, machine_.airs.size());
-    std::vector<ConstraintShape> ms, ps;
-    std::vector<int> prep_chips, prep_slot;
-    for (auto t : main) { if (!t) throw std::invalid_argument("step_audit: null trace"); ms.push_back({t->height, t->width}); }
-    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("step_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
-    step_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
-    const size_t NC = machine_.airs.size();
-    const uint32_t R = o.max_rows_per_entry;
-    // per chip its launch shape: a chip that does not fit the LDS is refused before anything is queued
-    std::vector<vk::SaArgs> sargs(NC);
-    StepReport rep;
-    rep.chips.resize(NC);
-    for (size_t i = 0; i < NC; i++) {
-        const AirDesc& air = machine_.airs[i];
-        sargs[i] = vk::SaArgs{};
-        vk::RaArgs& a = sargs[i].r;
-        sargs[i].n_steps = o.n_steps;
-        for (uint32_t s = 0; s < SA_MAX_STEPS; s++) sargs[i].steps[s] = vg::Fp::from_canonical(o.steps[s]).v;
-        StepChipStat& cs = rep.chips[i];
-        step_audit_chip_block(cs, air, main[i]->height, step_audit_selected(o, i), o.n_steps);
-        if (!cs.audited || !air.width) continue;
-        a.K = air.program.num_asserts;
-        a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
-        a.n_instrs = (uint32_t)air.program.instrs.size();
-        a.n_regs = air.program.num_regs;
-        a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
-        try {
-            vk::sa_shape(sargs[i]);
-        } catch (const std::invalid_argument& e) {
-            throw std::invalid_argument(std::string(e.what()) + " [chip " + air.name + "; the host audit has no limit]");
-        }
-        // dual evaluations, and at most one plain evaluation per (column, step) and q
-        a.evaluations = a.K ? (double)a.n * a.width * (a.n == 1 ? 1 : 2) * (1 + o.n_steps) : 0;
-        rep.evaluations += a.evaluations;
-    }
-
-    DeviceCtx& c = *ctx_;
-    c.activate();
-    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
-    c.activate();
-    struct Running {
-        std::atomic<int>& n;
-        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
-        ~Running() { n.fetch_sub(1); }
-    } running(c.proofs_running);
-    hipStream_t st = c.stream;
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
-    VG_HIP_CHECK(hipEventCreate(&ev0));
-    VG_HIP_CHECK(hipEventCreate(&ev1));
-    uint64_t scratch_words = 0, rows_words = 0, desc_words_n = 0;
-    try {
-        std::vector<DMat> own;
-        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
-            if (!t->nat.empty()) return t->nat.view();
-            own.emplace_back(&c, t->height, t->width);
-            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
-            return own.back().view();
-        };
-        own.reserve(NC + preprocessed.size());
-        // per chip: its weight rows and its slice of the scratch (u32 words): totals, table [w NB], prefix [w NB]
-        std::vector<uint64_t> tot_at(NC, 0), tab_at(NC, 0), pre_at(NC, 0), wr_at(NC, 0);
-        std::vector<uint32_t> desc_words;
-        uint64_t zeroed = 0;
-        for (size_t i = 0; i < NC; i++) {
-            vk::RaArgs& a = sargs[i].r;
-            if (!a.width) continue;
-            const AirDesc& air = machine_.airs[i];
-            const vk::DMatView mv = working(main[i]);
-            a.main = mv.data; a.mstride = mv.stride;
-            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
-            a.prog = (const vair::Instr*)prog_dev_[i].data;
-            a.iw = iw_dev_[i].data;
-            const std::vector<uint32_t> wr = ra_weight_rows(air);
-            wr_at[i] = desc_words.size();
-            desc_words.insert(desc_words.end(), wr.begin(), wr.end());
-            tot_at[i] = zeroed; zeroed += vk::sa_totals_words(sargs[i]);
-            tab_at[i] = zeroed; zeroed += ((uint64_t)a.width * a.NB + 1) & ~1ull;  // the next chip's u64 totals stay 8-byte aligned
-        }
-        scratch_words = zeroed;
-        for (size_t i = 0; i < NC; i++) if (sargs[i].r.width) { pre_at[i] = scratch_words; scratch_words += (uint64_t)sargs[i].r.width * sargs[i].r.NB; }
-        if (desc_words.empty()) desc_words.push_back(0);
-        desc_words_n = desc_words.size();
-        DBuf desc(&c, desc_words);
-        for (size_t i = 0; i < NC; i++) sargs[i].r.wr = desc.data + wr_at[i];
-        c.check_launch("step_audit ingest");
-        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
-        // the device pass: everything from here to the last download is between the two events
-        VG_HIP_CHECK(hipEventRecord(ev0, st));
-        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)zeroed * 4, st));
-        for (size_t i = 0; i < NC; i++)
-            if (sargs[i].r.width) vk::launch_sa_count(st, sargs[i], reinterpret_cast<unsigned long long*>(scratch.data + tot_at[i]), scratch.data + tab_at[i]);
-        c.check_launch("step_audit count");
-        {
-            std::vector<uint32_t> tw;
-            for (size_t i = 0; i < NC; i++) {
-                if (!sargs[i].r.width) continue;
-                StepChipStat& cs = rep.chips[i];
-                tw.resize(vk::sa_totals_words(sargs[i]));
-                c.download_small(tw.data(), scratch.data + tot_at[i], tw.size() * 4);
-                auto u64 = [&](size_t k) { return ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k]; };
-                cs.confirmed_rows = u64(0); cs.refuted_rows = u64(1);
-                for (uint32_t s = 0; s < SA_MAX_STEPS; s++) cs.passes[s] = u64(2 + s);
-                for (uint32_t k = 0; k < cs.width; k++) {
-                    cs.loose[k] = u64(6 + 4 * (size_t)k); cs.zeros[k] = u64(7 + 4 * (size_t)k); cs.exact[k] = u64(8 + 4 * (size_t)k); cs.coupled_exact[k] = u64(9 + 4 * (size_t)k);
-                }
-            }
-        }
-        step_audit_finish(rep, o);
-        for (size_t e0 = 0; e0 < rep.entries.size();) {
-            const uint32_t chip = rep.entries[e0].chip;
-            size_t e1 = e0;
-            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
-            rows_words = std::max<uint64_t>(rows_words, ((uint64_t)rep.entries[e1 - 1].column + 1) * R * SA_ROW_WORDS);
-            e0 = e1;
-        }
-        DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
-        for (size_t e0 = 0; e0 < rep.entries.size();) {
-            // the listed columns of one chip: scan, list, one download
-            const uint32_t chip = rep.entries[e0].chip;
-            size_t e1 = e0;
-            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
-            const vk::SaArgs& sa = sargs[chip];
-            const uint32_t c_cut = rep.entries[e1 - 1].column + 1;  // entries ascend: the listed columns of a chip are below it
-            const size_t words = (size_t)c_cut * R * SA_ROW_WORDS;
-            VG_HIP_CHECK(hipMemsetAsync(out.data, 0, words * 4, st));  // unused term slots are zero
-            vk::launch_ra_scan(st, sa.r, scratch.data + tab_at[chip], scratch.data + pre_at[chip], c_cut);
-            vk::launch_sa_list(st, sa, scratch.data + tab_at[chip], scratch.data + pre_at[chip], c_cut, R, out.data);
-            c.check_launch("step_audit list");
-            std::vector<uint32_t> w(words);
-            c.download_small(w.data(), out.data, w.size() * 4);
-            for (size_t e = e0; e < e1; e++) {
-                StepEntry& en = rep.entries[e];
-                const uint64_t listed = std::min<uint64_t>(en.coupled_exact + en.curved, R);
-                en.rows.resize((size_t)listed);
-                for (size_t k = 0; k < listed; k++) {
-                    const uint32_t* src = w.data() + ((size_t)en.column * R + k) * SA_ROW_WORDS;
-                    en.rows[k].row = src[0]; en.rows[k].pass_mask = src[1]; en.rows[k].zero = src[2]; en.rows[k].n_support = src[3];
-                    for (uint32_t x = 0; x < 2 * RA_TERMS; x++) en.rows[k].terms[x] = src[4 + x];
-                }
-            }
-            e0 = e1;
-        }
-        VG_HIP_CHECK(hipEventRecord(ev1, st));
-        c.sync();
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
-    } catch (const BusAuditNoMemory&) {
-        throw;
-    } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(st);
-        throw BusAuditNoMemory("step_audit: the device pool cannot give the pass its scratch: 48 + 32 bytes per column of totals and 8 per (column, workgroup of rows) of every chip (" +
-                               std::to_string(scratch_words * 4) + " bytes for this witness), " + std::to_string(desc_words_n * 4) + " bytes of interaction weight rows, " + std::to_string(rows_words * 4) +
-                               " bytes of listed rows (80 per (listed column, row slot)), plus the working-layout copies of uploaded traces; chip_mask audits fewer chips at a time");
-    }
-    rep.host_ms = ms_since(t_host);
-    return rep;
-}
-
-// ---- field audit (host/field_audit.hpp; kernels/field_audit.hip) ---------------------------------------------------------------------------
-FieldReport Prover::field_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const RankAuditOpts& opts_in) {
-    const auto t_host = Clock::now();
-    const RankAuditOpts o = field_audit_checked_opts(opts_in, machine_.airs.size());
-    std::vector<ConstraintShape> ms, ps;
-    std::vector<int> prep_chips, prep_slot;
-    for (auto t : main) { if (!t) throw std::invalid_argument("field_audit: null trace"); ms.push_back({t->height, t->width}); }
-    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("field_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
-    field_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
-    const size_t NC = machine_.airs.size();
-    const uint32_t R = o.max_rows_per_entry;
-    // per chip its launch shape: a chip that does not fit the LDS is refused before anything is queued
-    std::vector<vk::FaArgs> args(NC);
-    std::vector<std::vector<uint32_t>> wrs(NC), slot0(NC);  // weight rows; the first slot of every interaction
-    FieldReport rep;
-    rep.chips.resize(NC);
-    for (size_t i = 0; i < NC; i++) {
-        const AirDesc& air = machine_.airs[i];
-        vk::FaArgs& a = args[i];
-        a = vk::FaArgs{};
-        wrs[i] = ra_weight_rows(air);
-        FieldChipStat& cs = rep.chips[i];
-        field_audit_chip_block(cs, air, main[i]->height, rank_audit_selected(o, i), wrs[i]);
-        if (!cs.audited || !air.width) continue;
-        a.K = air.program.num_asserts;
-        a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
-        a.n_instrs = (uint32_t)air.program.instrs.size();
-        a.n_regs = air.program.num_regs;
-        a.M = (uint32_t)air.interactions.size();
-        for (auto& it : cs.interactions) { slot0[i].push_back(a.NS); a.NS += it.n_fields; a.F = std::max(a.F, it.n_fields); }
-        a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
-        try {
-            vk::fa_shape(a);
-        } catch (const std::invalid_argument& e) {
-            throw std::invalid_argument(std::string(e.what()) + " [chip " + air.name + "; the host audit has no limit]");
-        }
-        a.evaluations = a.K && a.M ? (double)a.n * a.width * (a.n == 1 ? 1 : 2) : 0;
-        rep.evaluations += a.evaluations;
-    }
-
-    DeviceCtx& c = *ctx_;
-    c.activate();
-    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
-    c.activate();
-    struct Running {
-        std::atomic<int>& n;
-        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
-        ~Running() { n.fetch_sub(1); }
-    } running(c.proofs_running);
-    hipStream_t st = c.stream;
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
-    VG_HIP_CHECK(hipEventCreate(&ev0));
-    VG_HIP_CHECK(hipEventCreate(&ev1));
-    uint64_t scratch_words = 0, rows_words = 0, desc_words_n = 0;
-    try {
-        std::vector<DMat> own;
-        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
-            if (!t->nat.empty()) return t->nat.view();
-            own.emplace_back(&c, t->height, t->width);
-            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
-            return own.back().view();
-        };
-        own.reserve(NC + preprocessed.size());
-        // per chip: its weight rows and its slice of the scratch (u32 words): totals, table [NS NB], prefix [NS NB]
-        std::vector<uint64_t> tot_at(NC, 0), tab_at(NC, 0), pre_at(NC, 0), wr_at(NC, 0);
-        std::vector<uint32_t> desc_words;
-        uint64_t zeroed = 0;
-        for (size_t i = 0; i < NC; i++) {
-            vk::FaArgs& a = args[i];
-            if (!a.width) continue;
-            const vk::DMatView mv = working(main[i]);
-            a.main = mv.data; a.mstride = mv.stride;
-            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
-            a.prog = (const vair::Instr*)prog_dev_[i].data;
-            a.iw = iw_dev_[i].data;
-            wr_at[i] = desc_words.size();
-            desc_words.insert(desc_words.end(), wrs[i].begin(), wrs[i].end());
-            tot_at[i] = zeroed; zeroed += vk::fa_totals_words(a);
-            tab_at[i] = zeroed; zeroed += ((uint64_t)a.NS * a.NB + 1) & ~1ull;  // the next chip's u64 totals stay 8-byte aligned
-        }
-        scratch_words = zeroed;
-        for (size_t i = 0; i < NC; i++) if (args[i].width) { pre_at[i] = scratch_words; scratch_words += (uint64_t)args[i].NS * args[i].NB; }
-        if (desc_words.empty()) desc_words.push_back(0);
-        desc_words_n = desc_words.size();
-        DBuf desc(&c, desc_words);
-        for (size_t i = 0; i < NC; i++) args[i].wr = desc.data + wr_at[i];
-        c.check_launch("field_audit ingest");
-        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
-        // the device pass: everything from here to the last download is between the two events
-        VG_HIP_CHECK(hipEventRecord(ev0, st));
-        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)zeroed * 4, st));
-        for (size_t i = 0; i < NC; i++)
-            if (args[i].width) vk::launch_fa_count(st, args[i], reinterpret_cast<unsigned long long*>(scratch.data + tot_at[i]), scratch.data + tab_at[i]);
-        c.check_launch("field_audit count");
-        {
-            std::vector<uint32_t> tw;
-            for (size_t i = 0; i < NC; i++) {
-                if (!args[i].width) continue;
-                FieldChipStat& cs = rep.chips[i];
-                tw.resize(vk::fa_totals_words(args[i]));
-                c.download_small(tw.data(), scratch.data + tot_at[i], tw.size() * 4);
-                auto u64 = [&](size_t k) { return ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k]; };
-                cs.live_records = u64(0); cs.floating_fields = u64(1); cs.floating_rows = u64(2);
-                for (size_t m = 0; m < cs.interactions.size(); m++) {
-                    FieldInteractionStat& s = cs.interactions[m];
-                    s.live_rows = u64(3 + m);
-                    for (uint32_t j = 0; j < s.n_fields; j++) s.floating[j] = u64(3 + cs.interactions.size() + slot0[i][m] + j);
-                }
-            }
-        }
-        field_audit_finish(rep, o);
-        auto slot_of = [&](const FieldEntry& e) { return slot0[e.chip][e.interaction] + e.field; };
-        for (size_t e0 = 0; e0 < rep.entries.size();) {
-            const uint32_t chip = rep.entries[e0].chip;
-            size_t e1 = e0;
-            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
-            rows_words = std::max<uint64_t>(rows_words, ((uint64_t)slot_of(rep.entries[e1 - 1]) + 1) * R * RA_ROW_WORDS);
-            e0 = e1;
-        }
-        DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
-        for (size_t e0 = 0; e0 < rep.entries.size();) {
-            // the listed slots of one chip: scan, list, one download
-            const uint32_t chip = rep.entries[e0].chip;
-            size_t e1 = e0;
-            while (e1 < rep.entries.size() && rep.entries[e1].chip == chip) e1++;
-            const vk::FaArgs& a = args[chip];
-            const uint32_t s_cut = slot_of(rep.entries[e1 - 1]) + 1;  // entries ascend: the listed slots of a chip are below it
-            const size_t words = (size_t)s_cut * R * RA_ROW_WORDS;
-            VG_HIP_CHECK(hipMemsetAsync(out.data, 0, words * 4, st));  // unused term slots are zero
-            vk::launch_fa_scan(st, a, scratch.data + tab_at[chip], scratch.data + pre_at[chip], s_cut);
-            vk::launch_fa_list(st, a, scratch.data + tab_at[chip], scratch.data + pre_at[chip], s_cut, R, out.data);
-            c.check_launch("field_audit list");
-            std::vector<uint32_t> w(words);
-            c.download_small(w.data(), out.data, w.size() * 4);
-            for (size_t e = e0; e < e1; e++) {
-                FieldEntry& en = rep.entries[e];
-                const uint64_t listed = std::min<uint64_t>(en.floating, R);
-                en.rows.resize((size_t)listed);
-                for (size_t k = 0; k < listed; k++) {
-                    const uint32_t* src = w.data() + ((size_t)slot_of(en) * R + k) * RA_ROW_WORDS;
-                    en.rows[k].row = src[0]; en.rows[k].n_support = src[1];
-                    for (uint32_t x = 0; x < 2 * RA_TERMS; x++) en.rows[k].terms[x] = src[2 + x];
-                }
-            }
-            e0 = e1;
-        }
-        VG_HIP_CHECK(hipEventRecord(ev1, st));
-        c.sync();
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
-    } catch (const BusAuditNoMemory&) {
-        throw;
-    } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(st);
-        throw BusAuditNoMemory("field_audit: the device pool cannot give the pass its scratch: 24 bytes of totals, 8 per interaction and field, and 8 per (field, workgroup of rows) of every chip (" +
-                               std::to_string(scratch_words * 4) + " bytes for this witness), " + std::to_string(desc_words_n * 4) + " bytes of interaction weight rows, " + std::to_string(rows_words * 4) +
-                               " bytes of listed rows (72 per (listed field, row slot)), plus the working-layout copies of uploaded traces; chip_mask audits fewer chips at a time");
-    }
-    rep.host_ms = ms_since(t_host);
-    return rep;
-}
-
-// ---- link audit (host/link_audit.hpp; kernels/link_audit.hip) ------------------------------------------------------------------------------
-LinkReport Prover::link_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const LinkAuditOpts& opts_in) {
-    const auto t_host = Clock::now();
-    const LinkAuditOpts o = link_audit_checked_opts(opts_in);
-    std::vector<BusShape> ms, ps;
-    std::vector<int> prep_chips, prep_slot;
-    for (auto t : main) { if (!t) throw std::invalid_argument("link_audit: null trace"); ms.push_back({t->height, t->width}); }
-    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("link_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
-    const BusPlan plan = link_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
-    const uint64_t n = plan.n_slots;
-    if (n >= 0xffffffffull) throw std::invalid_argument("link_audit: more than 2^32 - 2 (row, interaction) pairs; record ids are 32-bit");
-    const size_t NC = machine_.airs.size(), NB = plan.buses.size();
-    LinkReport rep;
-    link_audit_blocks(rep, machine_, plan);
-    // per chip the mask pass's launch shape (a chip that does not fit the LDS is refused before anything is queued) and its fields' slots
-    std::vector<vk::FaArgs> args(NC);
-    std::vector<std::vector<uint32_t>> wrs(NC);
-    std::vector<uint32_t> lt(4 + NC, 0);  // launch.hpp: the tally's table of field slots
-    uint32_t n_fields = 0;
-    for (size_t i = 0; i < NC; i++) {
-        const AirDesc& air = machine_.airs[i];
-        vk::FaArgs& a = args[i];
-        a = vk::FaArgs{};
-        lt[4 + i] = (uint32_t)lt.size();
-        for (auto& it : rep.chips[i]) { lt.push_back(n_fields); n_fields += it.n_fields; }
-        if (!air.width || air.interactions.empty()) continue;  // no record, or only constant fields: the zeroed masks are the answer
-        wrs[i] = ra_weight_rows(air);
-        a.K = air.program.num_asserts;
-        a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
-        a.n_instrs = (uint32_t)air.program.instrs.size();
-        a.n_regs = air.program.num_regs;
-        a.M = (uint32_t)air.interactions.size();
-        for (auto& it : rep.chips[i]) { a.NS += it.n_fields; a.F = std::max(a.F, it.n_fields); }
-        a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
-        try {
-            vk::la_shape(a);
-        } catch (const std::invalid_argument& e) {
-            throw std::invalid_argument(std::string(e.what()) + " [chip " + air.name + "; the host audit has no limit]");
-        }
-        a.evaluations = a.K ? (double)a.n * a.width * (a.n == 1 ? 1 : 2) : 0;
-        rep.evaluations += a.evaluations;
-    }
-    lt[0] = n_fields;
-    const uint64_t tally_words = vk::la_tally_words(n_fields, (uint32_t)NB);
-
-    DeviceCtx& c = *ctx_;
-    c.activate();
-    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
-    c.activate();
-    struct Running {
-        std::atomic<int>& n;
-        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
-        ~Running() { n.fetch_sub(1); }
-    } running(c.proofs_running);
-    hipStream_t st = c.stream;
-
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
-    VG_HIP_CHECK(hipEventCreate(&ev0));
-    VG_HIP_CHECK(hipEventCreate(&ev1));
-    uint64_t wr_words = 0, n_open = 0;
-    try {
-        // working-layout copies, as prove makes them (traces generated on the device are already column-major Montgomery)
-        std::vector<DMat> own;
-        std::vector<const uint32_t*> mptr(NC, nullptr), pptr(NC, nullptr);
-        std::vector<uint64_t> mstride(NC, 0), pstride(NC, 0);
-        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
-            if (!t->nat.empty()) return t->nat.view();
-            own.emplace_back(&c, t->height, t->width);
-            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
-            return own.back().view();
-        };
-        own.reserve(NC + preprocessed.size());
-        std::vector<uint64_t> wr_at(NC, 0);
-        std::vector<uint32_t> wr_all;
-        for (size_t i = 0; i < NC; i++) {
-            if (!plan.chips[i].M) continue;  // a chip without interactions is not read
-            const vk::DMatView v = working(main[i]);
-            mptr[i] = v.data; mstride[i] = v.stride;
-            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); pptr[i] = pv.data; pstride[i] = pv.stride; }
-            vk::FaArgs& a = args[i];
-            if (!a.width) continue;
-            a.main = mptr[i]; a.mstride = mstride[i]; a.prep = pptr[i]; a.pstride = pstride[i];
-            a.prog = (const vair::Instr*)prog_dev_[i].data;
-            a.iw = iw_dev_[i].data;
-            wr_at[i] = wr_all.size();
-            wr_all.insert(wr_all.end(), wrs[i].begin(), wrs[i].end());
-        }
-        if (wr_all.empty()) wr_all.push_back(0);
-        wr_words = wr_all.size();
-        c.check_launch("link_audit ingest");
-        DBuf desc(&c, bus_audit_descriptor(machine_, plan, mptr, mstride, pptr, pstride)), wr_dev(&c, wr_all), lt_dev(&c, lt);
-        for (size_t i = 0; i < NC; i++) args[i].wr = wr_dev.data + wr_at[i];
-
-        uint32_t total_inter = 0;
-        std::vector<uint32_t> inter_base(NC, 0);
-        for (size_t i = 0; i < NC; i++) { inter_base[i] = total_inter; total_inter += plan.chips[i].M; }
-        const size_t n_counters = 8 + NB + total_inter;
-        const uint64_t na = n ? n : 1;
-        DBuf keys2(&c, (size_t)(4 * na)), ids2(&c, (size_t)(2 * na)), cnt(&c, (size_t)na), gid(&c, (size_t)na), head_pos(&c, (size_t)na), sums(&c, (size_t)(4 * na)),
-            nrec(&c, (size_t)(2 * na)), mask(&c, (size_t)na), tmask(&c, (size_t)na), sort_tmp(&c, vk::bus_audit_sort_scratch_words(na)), scan_tmp(&c, vk::bus_audit_scan_scratch_words(na)),
-            counters(&c, n_counters), tally(&c, (size_t)(2 * tally_words ? 2 * tally_words : 2));
-        unsigned long long* keys = (unsigned long long*)keys2.data;
-        unsigned long long* sums_p = (unsigned long long*)sums.data;
-        // the device pass: everything from here to the last download is between the two events
-        VG_HIP_CHECK(hipEventRecord(ev0, st));
-        VG_HIP_CHECK(hipMemsetAsync(counters.data, 0, n_counters * 4, st));
-        VG_HIP_CHECK(hipMemsetAsync(sums.data, 0, (size_t)(4 * na) * 4, st));
-        VG_HIP_CHECK(hipMemsetAsync(nrec.data, 0, (size_t)(2 * na) * 4, st));
-        VG_HIP_CHECK(hipMemsetAsync(mask.data, 0, (size_t)na * 4, st));
-        VG_HIP_CHECK(hipMemsetAsync(tally.data, 0, (size_t)(2 * tally_words ? 2 * tally_words : 2) * 4, st));
-
-        for (size_t i = 0; i < NC; i++)
-            if (args[i].width) vk::launch_la_masks(st, args[i], (uint32_t)plan.chips[i].first_id, mask.data);
-        for (size_t i = 0; i < NC; i++)
-            vk::launch_ba_records(st, desc.data, (uint32_t)i, plan.chips[i].height, machine_.airs[i].width, plan.chips[i].M, o.hash_bits, keys, ids2.data, cnt.data,
-                                  counters.data + 8 + NB + inter_base[i]);
-        int shifts[8], n_shifts = 0;
-        for (uint32_t b = 0; b < (o.hash_bits + 7) / 8; b++) shifts[n_shifts++] = 8 * (int)b;
-        if (o.hash_bits <= 56) shifts[n_shifts++] = 56;  // the pass that sinks the dead slots (key ~0) behind the live ones
-        int half = vk::launch_ba_sort(st, keys, ids2.data, n, sort_tmp.data, shifts, n_shifts, 0);
-        vk::launch_ba_groups(st, desc.data, keys + (uint64_t)half * n, ids2.data + (uint64_t)half * n, n, false, gid.data, head_pos.data, scan_tmp.data, counters.data);
-        vk::launch_ba_reduce(st, desc.data, ids2.data + (uint64_t)half * n, cnt.data, gid.data, head_pos.data, n, true, sums_p, nrec.data, counters.data);
-        c.check_launch("link_audit");
-        std::vector<uint32_t> cw(n_counters);
-        c.download_small(cw.data(), counters.data, n_counters * 4);
-        if (cw[2]) {
-            // a key collision (the hash_bits test hook forces it): group by the full padded tuples instead, exactly as Prover::bus_audit does
-            VG_HIP_CHECK(hipMemsetAsync(counters.data + 1, 0, (7 + NB) * 4, st));
-            VG_HIP_CHECK(hipMemsetAsync(sums.data, 0, (size_t)(4 * na) * 4, st));
-            VG_HIP_CHECK(hipMemsetAsync(nrec.data, 0, (size_t)(2 * na) * 4, st));
-            const int all[8] = {0, 8, 16, 24, 32, 40, 48, 56};
-            half = 0;
-            vk::launch_ba_iota(st, ids2.data, n);
-            for (int chunk = (int)(plan.wmax + 1 + 1) / 2 - 1; chunk >= 0; chunk--) {
-                vk::launch_ba_rekey(st, desc.data, (uint32_t)chunk, ids2.data + (uint64_t)half * n, cnt.data, keys + (uint64_t)half * n, n);
-                half = vk::launch_ba_sort(st, keys, ids2.data, n, sort_tmp.data, all, 8, half);
-            }
-            vk::launch_ba_groups(st, desc.data, keys + (uint64_t)half * n, ids2.data + (uint64_t)half * n, n, true, gid.data, head_pos.data, scan_tmp.data, counters.data);
-            vk::launch_ba_reduce(st, desc.data, ids2.data + (uint64_t)half * n, cnt.data, gid.data, head_pos.data, n, false, sums_p, nrec.data, counters.data);
-            c.check_launch("link_audit exact");
-            c.download_small(cw.data(), counters.data, n_counters * 4);
-        }
-        const uint32_t n_live = cw[0], n_groups = cw[1];
-        const uint32_t* ids = ids2.data + (uint64_t)half * n;
-        if (n_groups) VG_HIP_CHECK(hipMemsetAsync(tmask.data, 0xff, (size_t)n_groups * 4, st));
-        vk::launch_la_join(st, ids, mask.data, gid.data, n_live, tmask.data);
-        vk::launch_la_tally(st, desc.data, lt_dev.data, ids, mask.data, gid.data, head_pos.data, tmask.data, n_live, n_fields, (uint32_t)NB, (unsigned long long*)tally.data);
-        c.check_launch("link_audit join");
-        std::vector<uint32_t> tw((size_t)(2 * tally_words ? 2 * tally_words : 2));
-        c.download_small(tw.data(), tally.data, tw.size() * 4);
-        auto u64 = [&](uint64_t k) { return ((uint64_t)tw[2 * k + 1] << 32) | tw[2 * k]; };
-        for (size_t i = 0; i < NC; i++)
-            for (size_t m = 0; m < rep.chips[i].size(); m++) {
-                LinkInteractionStat& s = rep.chips[i][m];
-                s.live_rows = cw[8 + NB + inter_base[i] + m];
-                rep.buses[plan.chips[i].bus_slot[m]].live += s.live_rows;
-                const uint32_t slot = lt[lt[4 + i] + m];
-                for (uint32_t j = 0; j < s.n_fields; j++) { s.floating[j] = u64(slot + j); s.open[j] = u64((uint64_t)n_fields + slot + j); }
-            }
-        for (size_t b = 0; b < NB; b++) {
-            LinkBusStat& bs = rep.buses[b];
-            const uint64_t bb = 2ull * n_fields + 66ull * b;
-            bs.tuples = u64(bb); bs.open_tuples = u64(bb + 1);
-            for (uint32_t j = 0; j < bs.width; j++) { bs.open_in[j] = u64(bb + 2 + j); bs.open_records[j] = u64(bb + 34 + j); }
-            n_open += bs.open_tuples;
-        }
-        rep.total_open = n_open;
-        if (n_open) {
-            const uint32_t n_rep = (uint32_t)std::min<uint64_t>(n_open, o.max_tuples), R = o.max_records_per_tuple, stride = 8 + plan.wmax + 2 * R;
-            DBuf ukeys(&c, (size_t)(4 * n_open)), uvals(&c, (size_t)(2 * n_open)), out(&c, (size_t)n_rep * stride);
-            vk::launch_la_select(st, ids, head_pos.data, tmask.data, n_groups, (uint32_t)n_open, (unsigned long long*)ukeys.data, uvals.data, counters.data);
-            const int id_bytes[4] = {0, 8, 16, 24};  // keys are 32-bit record ids
-            const int uh = vk::launch_ba_sort(st, (unsigned long long*)ukeys.data, uvals.data, n_open, sort_tmp.data, id_bytes, 4, 0);
-            vk::launch_la_report(st, desc.data, ids, mask.data, head_pos.data, nrec.data, tmask.data, uvals.data + (uint64_t)uh * n_open, n_rep, R, out.data);
-            c.check_launch("link_audit report");
-            std::vector<uint32_t> w((size_t)n_rep * stride);
-            c.download_small(w.data(), out.data, w.size() * 4);
-            for (uint32_t t = 0; t < n_rep; t++) {
-                const uint32_t* e = w.data() + (size_t)t * stride;
-                const BusStat& bus = plan.buses.at(e[0]);
-                LinkTuple lk;
-                lk.is_global = bus.is_global; lk.bus_index = bus.bus_index; lk.mask = e[2];
-                lk.fields.assign(e + 8, e + 8 + bus.width);
-                lk.n_send = e[3]; lk.n_recv = e[4];
-                for (uint32_t k = 0; k < e[1] && k < R; k++) {
-                    const BusRecord r = plan.decode(e[8 + plan.wmax + 2 * k]);
-                    lk.records.push_back(LinkRecord{r.chip, r.row, r.interaction, machine_.airs[r.chip].interactions[r.interaction].is_send() ? 1u : 0u, e[8 + plan.wmax + 2 * k + 1]});
-                }
-                rep.tuples.push_back(std::move(lk));
-            }
-        }
-        VG_HIP_CHECK(hipEventRecord(ev1, st));
-        c.sync();
-        float ms_dev = 0;
-        if (hipEventElapsedTime(&ms_dev, ev0, ev1) == hipSuccess) rep.device_ms = ms_dev;
-    } catch (const BusAuditNoMemory&) {
-        throw;
-    } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(st);
-        throw BusAuditNoMemory("link_audit: the device pool cannot give the pass its scratch: 68 bytes for each of the " + std::to_string(n) + " (row, interaction) pairs (the bus audit's " +
-                               std::to_string(BUS_AUDIT_BYTES_PER_SLOT) + ", 4 for the record mask, 4 for the tuple mask: " + std::to_string(68 * n) + " bytes), " + std::to_string(8 * tally_words) +
-                               " bytes of tallies (16 per field, 528 per bus), " + std::to_string(wr_words * 4) + " bytes of interaction weight rows, 24 for each of the " + std::to_string(n_open) +
-                               " open tuples, plus the working-layout copies of uploaded traces");
-    }
-    link_audit_finish(rep, o);
-    rep.host_ms = ms_since(t_host);
-    return rep;
-}
-
-// ---- coverage audit (host/coverage_audit.hpp; kernels/coverage_audit.hip) ------------------------------------------------------------------
-CoverageReport Prover::coverage_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
-                                      const CoverageAuditOpts& opts_in) {
-    const auto t_host = Clock::now();
-    const CoverageAuditOpts o = coverage_audit_checked_opts(opts_in);
-    std::vector<ConstraintShape> ms, ps;
-    std::vector<int> prep_chips, prep_slot;
-    for (auto t : main) { if (!t) throw std::invalid_argument("coverage_audit: null trace"); ms.push_back({t->height, t->width}); }
-    for (auto& pr : preprocessed) { if (!pr.second) throw std::invalid_argument("coverage_audit: null trace"); prep_chips.push_back(pr.first); ps.push_back({pr.second->height, pr.second->width}); }
-    coverage_audit_plan(machine_, ms, prep_chips, ps, prep_slot);
-    const size_t NC = machine_.airs.size();
-    for (size_t i = 0; i < NC; i++)
-        if (machine_.airs[i].program.num_asserts > vk::CA_MAX_CONSTRAINTS)
-            throw std::invalid_argument("coverage_audit: chip " + machine_.airs[i].name + " has " + std::to_string(machine_.airs[i].program.num_asserts) + " constraints; the device audit handles up to " +
-                                        std::to_string(vk::CA_MAX_CONSTRAINTS) + " per chip (the host audit has no limit)");
-    const uint32_t D = o.n_deltas;
-
-    DeviceCtx& c = *ctx_;
-    c.activate();
-    std::unique_lock<std::mutex> one_at_a_time(c.prove_mu);  // a context runs one thing at a time: the audit queues like a proof
-    c.activate();
-    struct Running {
-        std::atomic<int>& n;
-        explicit Running(std::atomic<int>& a) : n(a) { n.fetch_add(1); }
-        ~Running() { n.fetch_sub(1); }
-    } running(c.proofs_running);
-    hipStream_t st = c.stream;
-
-    CoverageReport rep;
-    rep.deltas.assign(o.deltas, o.deltas + D);
-    rep.chips.resize(NC);
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    struct Events { hipEvent_t& a; hipEvent_t& b; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } events{ev0, ev1};
-    VG_HIP_CHECK(hipEventCreate(&ev0));
-    VG_HIP_CHECK(hipEventCreate(&ev1));
-    uint64_t scratch_words = 0, total_cells_all = 0, table_words = 0;
-    try {
-        // working-layout copies, as prove makes them (traces generated on the device are already column-major Montgomery)
-        std::vector<DMat> own;
-        auto working = [&](const DeviceTrace* t) -> vk::DMatView {
-            if (!t->nat.empty()) return t->nat.view();
-            own.emplace_back(&c, t->height, t->width);
-            vk::launch_ingest(st, t->raw.data, own.back().view(), false);
-            return own.back().view();
-        };
-        own.reserve(NC + preprocessed.size());
-        // per chip: the launch shape, its column flags and its slices of the scratch (u32 words; launch.hpp).  Zeroed: the workgroup tables
-        // [GX][cells][4], detected [4] u64; written whole by merge and pack: counts [cells][2] u64, rows [cells][2], packed
-        std::vector<vk::CovArgs> args(NC);
-        std::vector<uint64_t> wg_at(NC, 0), det_at(NC, 0), cnt_at(NC, 0), row_at(NC, 0), pack_at(NC, 0), cap(NC, 0), flag_at(NC, 0);
-        std::vector<uint32_t> flag_words;
-        uint64_t zeroed = 0, packed = 0;
-        for (size_t i = 0; i < NC; i++) {
-            const AirDesc& air = machine_.airs[i];
-            vk::CovArgs& v = args[i];
-            v = vk::CovArgs{};
-            vk::MaArgs& a = v.m;
-            a.K = air.program.num_asserts;
-            v.M = (uint32_t)air.interactions.size();
-            CoverageChipStat& cs = rep.chips[i];
-            cs.width = air.width; cs.n_constraints = a.K; cs.n_interactions = v.M; cs.height = main[i]->height;
-            cs.kills.assign((size_t)(a.K + v.M) * D, 0); cs.sole.assign((size_t)(a.K + v.M) * D, 0);
-            const double evaluations = ma_evaluations(air, main[i]->height, D);
-            rep.evaluations += evaluations;
-            if (!air.width) continue;
-            const vk::DMatView mv = working(main[i]);
-            a.main = mv.data; a.mstride = mv.stride; a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
-            if (prep_slot[i] >= 0) { const vk::DMatView pv = working(preprocessed[(size_t)prep_slot[i]].second); a.prep = pv.data; a.pstride = pv.stride; }
-            a.prog = (const vair::Instr*)prog_dev_[i].data;
-            a.n_instrs = (uint32_t)air.program.instrs.size();
-            a.n_regs = air.program.num_regs;
-            a.iw = iw_dev_[i].data;
-            a.evaluations = evaluations;
-            a.D = D;
-            for (uint32_t k = 0; k < D; k++) a.delta[k] = Fp::from_canonical(o.deltas[k]).v;
-            a.native_chip = !a.K ? vk::MA_BUS_ONLY : (fri_.interpret_air ? vk::CA_INTERPRET : air.native_chip);
-            try {
-                vk::cov_shape(v, o.max_workgroups);
-            } catch (const std::invalid_argument& e) {
-                throw std::invalid_argument(std::string(e.what()) + " (chip " + air.name + ")");
-            }
-            const double baselines = a.K ? (a.n == 1 ? 1.0 : 2.0) * (double)a.n * (a.CY - 1) : 0;  // every column slice evaluates the baselines of its rows
-            a.evaluations += baselines; rep.evaluations += baselines;
-            const std::vector<uint32_t> fl = ma_column_flags(air);
-            bool masks_ok = false;
-            const std::vector<uint32_t> bm = ma_bus_masks(air, masks_ok);
-            a.bus_walk = masks_ok ? 0u : 1u;
-            flag_at[i] = flag_words.size();
-            flag_words.insert(flag_words.end(), fl.begin(), fl.end());
-            flag_words.insert(flag_words.end(), bm.begin(), bm.end());
-            const uint64_t cells = vk::cov_cells(v);
-            total_cells_all += cells;
-            table_words += 4 * cells * v.GX;
-            det_at[i] = zeroed; zeroed += 8;
-            wg_at[i] = zeroed; zeroed += 4 * cells * v.GX;
-            cap[i] = std::min<uint64_t>(cells, o.max_cells);
-            cnt_at[i] = packed; packed += 4 * cells;  // u64s: every offset of this region is even
-            row_at[i] = packed; packed += 2 * cells;
-            pack_at[i] = packed; packed += vk::cov_packed_words(v, cap[i]);
-        }
-        scratch_words = zeroed + packed;
-        if (flag_words.empty()) flag_words.push_back(0);
-        DBuf flags(&c, flag_words);
-        for (size_t i = 0; i < NC; i++) args[i].m.flags = flags.data + flag_at[i];
-        c.check_launch("coverage_audit ingest");
-        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
-        uint32_t* const z = scratch.data;
-        uint32_t* const pk = z + zeroed;
-        // the device pass: everything from here to the last download is between the two events
-        VG_HIP_CHECK(hipEventRecord(ev0, st));
-        if (zeroed) VG_HIP_CHECK(hipMemsetAsync(z, 0, (size_t)zeroed * 4, st));
-        for (size_t i = 0; i < NC; i++) {
-            if (!args[i].m.width) continue;
-            vk::launch_cov_audit(st, args[i], z + wg_at[i], reinterpret_cast<unsigned long long*>(z + det_at[i]));
-            vk::launch_cov_merge(st, args[i], z + wg_at[i], reinterpret_cast<unsigned long long*>(pk + cnt_at[i]), pk + row_at[i]);
-            vk::launch_cov_pack(st, args[i], reinterpret_cast<const unsigned long long*>(pk + cnt_at[i]), pk + row_at[i], (uint32_t)cap[i], pk + pack_at[i]);
-        }
-        c.check_launch("coverage_audit");
-        // downloads: per chip its block (detected, the pack's head and sums), then the listed cells — never the cell table itself
-        std::vector<uint32_t> w;
-        for (size_t i = 0; i < NC; i++) {
-            const vk::CovArgs& v = args[i];
-            CoverageChipStat& cs = rep.chips[i];
-            if (v.m.width) {
-                uint32_t dw[8];
-                c.download_small(dw, z + det_at[i], sizeof dw);
-                for (uint32_t k = 0; k < D; k++) cs.detected[k] = ((uint64_t)dw[2 * k + 1] << 32) | dw[2 * k];
-                const size_t TDD = (size_t)(v.m.K + v.M) * D;
-                w.resize(2 + 4 * TDD);
-                c.download_small(w.data(), pk + pack_at[i], w.size() * 4);
-                const uint64_t nonzero = w[0];
-                for (size_t k = 0; k < TDD; k++) { cs.kills[k] = ((uint64_t)w[3 + 4 * k] << 32) | w[2 + 4 * k]; cs.sole[k] = ((uint64_t)w[5 + 4 * k] << 32) | w[4 + 4 * k]; }
-                rep.total_cells += nonzero;
-                const uint64_t take = std::min<uint64_t>(std::min<uint64_t>(nonzero, cap[i]), o.max_cells - rep.cells.size());
-                if (take) {
-                    w.resize(8 * (size_t)take);
-                    c.download_small(w.data(), pk + pack_at[i] + 2 + 4 * TDD, w.size() * 4);
-                    for (size_t k = 0; k < take; k++) {
-                        const uint32_t* e = &w[8 * k];
-                        CoverageCell cell;
-                        cell.chip = (uint32_t)i; cell.delta = e[0] % D; cell.column = (e[0] / D) % v.m.width; cell.detector = e[0] / D / v.m.width;
-                        cell.kills = ((uint64_t)e[2] << 32) | e[1]; cell.sole = ((uint64_t)e[4] << 32) | e[3]; cell.first_row = e[5]; cell.first_sole_row = e[6];
-                        rep.cells.push_back(cell);
-                    }
-                }
-            }
-            coverage_classify(cs, D);
-        }
-        rep.truncated = rep.total_cells > rep.cells.size();
-        VG_HIP_CHECK(hipEventRecord(ev1, st));
-        c.sync();
-        float ms = 0;
-        if (hipEventElapsedTime(&ms, ev0, ev1) == hipSuccess) rep.device_ms = ms;
-    } catch (const BusAuditNoMemory&) {
-        throw;
-    } catch (const std::bad_alloc&) {
-        (void)hipStreamSynchronize(st);
-        throw BusAuditNoMemory("coverage_audit: the device pool cannot give the pass its scratch: per chip 16 bytes per cell (detector, column, delta) and workgroup along its rows (" +
-                               std::to_string(table_words * 4) + " bytes for this witness; max_workgroups bounds it), 24 per cell (" + std::to_string(total_cells_all) +
-                               " cells for this machine), 16 per (detector, delta), 32 per listed cell (max_cells per chip at most): " + std::to_string(scratch_words * 4) +
-                               " bytes in all, plus 12 per column of flags and the working-layout copies of uploaded traces");
-    }
-    rep.host_ms = ms_since(t_host);
-    return rep;
 }
 
 }  // namespace vhost

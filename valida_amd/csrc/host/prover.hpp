@@ -22,6 +22,10 @@ namespace vhost {
 
 constexpr uint32_t PROOF_MAGIC = 0x31465056u;  // "VPF1" flat wire format, see DESIGN.md "Proof wire format"
 
+// host-side wall clock of the phase times and of the audits' host_ms
+using Clock = std::chrono::steady_clock;
+inline double ms_since(Clock::time_point t0) { return std::chrono::duration<double, std::milli>(Clock::now() - t0).count(); }
+
 struct HostMatrix {  // canonical row-major, host memory (the reference's RowMajorMatrix<Val>)
     const uint32_t* data;
     uint64_t height, width;

@@ -21,7 +21,7 @@
 // bound): finite flips stay with the mutation and pair audits.  It covers the cells of one row; cross-row combinations are not looked for.  It
 // is a statement about THIS witness, not a soundness proof.
 // This header holds what the host and the device implementation share — options, the report and its word image, the row analysis — and the
-// host implementation (plain C++, one thread, no limits).  The device pass is Prover::rank_audit (prover.cpp, kernels/rank_audit.hip).
+// host implementation (plain C++, one thread, no limits).  The device pass is Prover::rank_audit (prover_audits.cpp, kernels/rank_audit.hip).
 #pragma once
 #include <chrono>
 #include <functional>

@@ -20,7 +20,7 @@
 // cross-row combinations are not looked for.
 // This header holds what host and device share — options, report, word image — and the host implementation (plain C++, one thread, no limits):
 // the directions through rank_audit_host's per-row callback, the moves judged by the chip's Program before / after and the interactions
-// before / after as mutation_audit_host judges its own.  The device pass is Prover::step_audit (prover.cpp, kernels/step_audit.hip).
+// before / after as mutation_audit_host judges its own.  The device pass is Prover::step_audit (prover_audits.cpp, kernels/step_audit.hip).
 #pragma once
 #include "rank_audit.hpp"
 
