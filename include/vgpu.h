@@ -776,6 +776,62 @@ const uint32_t* vgpu_step_report_words(const vgpu_step_report_t* r);
 void vgpu_step_report_timing(const vgpu_step_report_t* r, double out[3]);
 void vgpu_step_report_free(vgpu_step_report_t* r);
 
+/* ---- Invariant audit: the affine-linear relations every row of a chip keeps.  The other audits ask what the constraints and bus records bind;
+ * this one asks which relations the WITNESS keeps that nothing may be asking for, and on how many rows the chip's own constraints and records
+ * enforce each of them to first order.  Inputs: exactly what vgpu_prove and the audits take.
+ *   invariants   chip h, main matrix M (n x w): the augmented row a_r = (1, M[r][0], .., M[r][w - 1]); the invariants are the l in F_p^(w + 1)
+ *                with l . a_r = 0 for every r.  R = the reduced row echelon form of the n x (w + 1) matrix of the a_r, columns in that order
+ *                (unique: no elimination order, grid or row order changes a word; column 0 is always a pivot); rho_A = rank, d = w + 1 - rho_A.
+ *   basis        one invariant per non-pivot main column f: l_f = 1, l_p = -R[row of p][f] for every pivot column p (only pivots left of f
+ *                occur), 0 elsewhere: "column f is this affine function of earlier columns".  CONSTANT (kind 0) when no main column other
+ *                than f has a non-zero coefficient (M[r][f] = -l_0 on every row), otherwise a RELATION (kind 1).
+ *   enforcement  c = (l_1 .. l_w) against the rank audit's Jacobian J_r (the same matrix, word for word; n = 1 by its rule): l is ENFORCED at
+ *                row r iff c lies in the row space of J_r, otherwise FREE at r: some first-order-unnoticed move of the row's cells breaks the
+ *                relation.  Each invariant is judged against J_r alone, never against J_r plus other invariants.
+ * What it is not: affine-linear relations only (b (b - 1) = 0 is not found); one row (relations between a row and its successor are not looked
+ * for); THIS witness (a short program has accidental relations); the verdict is per basis vector (a sum of two free invariants can be
+ * enforced); enforcement is first order, with the rank audit's caveats; `check`'s exit status never depends on it.
+ * Options: max_entries, max_rows_per_entry, chip_mask as vgpu_rank_audit_opts_t, same defaults and refusals; max_terms: (column, coefficient)
+ * terms listed per invariant, 0 the default 8, at most 4096; opts may be NULL; reserved != 0 is refused.
+ * vgpu_invariant_audit runs on the device (kernels/invariant_audit.hip), queued on the prover context.  Phase 1: a streaming exact elimination of
+ * the augmented rows, one wave per slice of rows with its reduced basis in LDS, at most 2048 workgroups per chip, then a tree of fan 16 that
+ * eliminates the workgroups' bases into the one RREF and writes the d canonical vectors.  Phase 2 (skipped when d = 0): one wave per trace row, the rank
+ * audit's dual evaluation and LDS elimination, then one reduce-only sweep per invariant; free rows are counted per workgroup and listed by
+ * count -> scan -> list, no atomic admits a row.  Scratch from the pool: per chip (w + 1) (w + 2) words per phase-1 workgroup and a sixteenth of that again for the tree (64 MB at
+ * most), (w + 1)^2 + 2 words of merged basis, 8 d bytes of totals, 8 d bytes per workgroup of rows, the interaction weight rows, 4 max_rows_per_entry bytes per listed
+ * invariant; VGPU_ERR_OOM with a message when the pool cannot give them.  VGPU_ERR_INVALID_ARG with the chip's name and the arithmetic for a chip
+ * whose phase 1 (4 x ((w + 1) ((w + 1) | 1) + 3 (w + 1) + 32 ((w + 1) | 1) + 8) bytes: w <= 184) or phase 2 (the rank audit's sum with its
+ * 4 x 6 w bytes of counters replaced by 4 x (w^2 + 4 w) bytes for the invariants and theirs when that is more, d = w counted) does not fit 160 KB
+ * of LDS with one wave per workgroup; one lane per augmented column, three words per lane, would allow 191 columns.
+ * vgpu_invariant_audit_host: the same contract on the host, one thread, no limits.
+ * Report image (vgpu_invariant_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x31524956 "VIR1" [1] word count [2] max_terms [3] truncated [4,5] total_entries = the sum of d over the audited chips (exact even when
+ *   the list is cut) [6] reported [7] n_chips
+ *   per chip, in machine order, 14 words: width, constraints, interactions, audited (0 / 1), height (u64), rho_A, d, constant columns, relations,
+ *   invariants enforced on every row, on some rows, on no row, 0.  A chip that is not audited keeps its first six words, the rest 0.
+ *   per entry, ascending (chip, column f), 12 + 2 T + L words: chip, column f, kind, l_0, support (main columns with a non-zero coefficient, f
+ *   included; exact), T = listed terms = min(support, max_terms), L = listed free rows = min(free_rows, max_rows_per_entry), 0, enforced_rows
+ *   (u64), free_rows (u64), then T (column, coefficient) terms ascending by column, then the first L free rows, ascending. */
+typedef struct vgpu_invariant_audit_opts {
+    uint64_t max_entries;
+    uint32_t max_rows_per_entry;
+    uint32_t chip_mask;
+    uint32_t max_terms;
+    uint32_t reserved[3];
+} vgpu_invariant_audit_opts_t;
+typedef struct vgpu_invariant_report vgpu_invariant_report_t;
+int32_t vgpu_invariant_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                             uint32_t n_prep, const vgpu_invariant_audit_opts_t* opts, vgpu_invariant_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_invariant_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                                  const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                                  const vgpu_invariant_audit_opts_t* opts, vgpu_invariant_report_t** out);
+uint64_t vgpu_invariant_report_len(const vgpu_invariant_report_t* r);
+const uint32_t* vgpu_invariant_report_words(const vgpu_invariant_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: dual row evaluations of phase 2 */
+void vgpu_invariant_report_timing(const vgpu_invariant_report_t* r, double out[3]);
+void vgpu_invariant_report_free(vgpu_invariant_report_t* r);
+
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
  *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct

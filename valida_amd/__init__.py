@@ -1401,6 +1401,102 @@ def step_audit_host(machine, main_matrices, preprocessed, steps=None, max_entrie
     return _audit_host("step", machine, main_matrices, preprocessed, opts)
 
 
+class InvariantAuditOpts(ctypes.Structure):  # vgpu_invariant_audit_opts_t
+    _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("max_terms", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 3)]
+
+
+class InvariantReport(_AuditReport):
+    """The invariant audit of a witness (vgpu_invariant_audit / vgpu_invariant_audit_host; the contract is stated in include/vgpu.h), as plain
+    Python values: max_terms, truncated, total_entries (the sum of d over the audited chips), reported,
+    chips = [dict(chip, width, constraints, interactions, audited, height, rank (rho_A), invariants (d), constant_columns, relations (counts),
+    every, some, never (invariants enforced on every row, on some rows, on no row))],
+    entries = [dict(chip, column, kind ("constant" / "relation"), l0, support, terms=[(column, coefficient)], enforced_rows, free_rows,
+    rows=[the first free rows])] ascending by (chip, column): l0 + sum(coefficient * M[r][column]) = 0 on every row r of the witness,
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (dual row evaluations of the enforcement phase).
+    Affine-linear, one row, THIS witness, per basis vector, first order: candidates for missing constraints, not findings."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 8 or w[0] != 0x31524956 or w[1] != len(w):
+            raise ValueError("not an invariant report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.max_terms = w[2]
+        self.truncated = bool(w[3])
+        self.total_entries, self.reported = w[4] | (w[5] << 32), w[6]
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 8
+        self.chips = []
+        for c in range(w[7]):
+            self.chips.append(dict(chip=c, width=w[pos], constraints=w[pos + 1], interactions=w[pos + 2], audited=bool(w[pos + 3]), height=u64(pos + 4), rank=w[pos + 6],
+                                   invariants=w[pos + 7], constant_columns=w[pos + 8], relations=w[pos + 9], every=w[pos + 10], some=w[pos + 11], never=w[pos + 12]))
+            pos += 14
+        self.entries = []
+        for _ in range(self.reported):
+            T, L = w[pos + 5], w[pos + 6]
+            at = pos + 12
+            self.entries.append(dict(chip=w[pos], column=w[pos + 1], kind="relation" if w[pos + 2] else "constant", l0=w[pos + 3], support=w[pos + 4],
+                                     terms=[(w[at + 2 * i], w[at + 2 * i + 1]) for i in range(T)], enforced_rows=u64(pos + 8), free_rows=u64(pos + 10),
+                                     rows=w[at + 2 * T:at + 2 * T + L]))
+            pos = at + 2 * T + L
+        assert pos == len(w)
+
+    def _columns(self, chip, keep):
+        return [e["column"] for e in self.entries if e["chip"] == chip and keep(e)]
+
+    def constant_columns(self, chip):
+        """The listed columns of `chip` that hold one value on every row."""
+        return self._columns(chip, lambda e: e["kind"] == "constant")
+
+    def relations(self, chip):
+        """The listed columns of `chip` that are an affine function of earlier columns (and not constant)."""
+        return self._columns(chip, lambda e: e["kind"] == "relation")
+
+    def never_enforced(self, chip):
+        """The listed columns of `chip` whose invariant no row's constraints and records enforce: candidates for a missing constraint."""
+        return self._columns(chip, lambda e: e["enforced_rows"] == 0)
+
+    def holds(self, main_matrices):
+        """The (chip, column) pairs of the listed entries whose relation FAILS on some row of the given canonical traces (one matrix per chip;
+        plain numpy, no library call): [] on the audited witness, and a way to test one witness's invariants against another program's traces.
+        Raises for an entry whose vector was cut at max_terms."""
+        bad = []
+        for e in self.entries:
+            if e["support"] > len(e["terms"]):
+                raise VgpuError(-1, "invariant_audit: the vector of chip %d column %d is cut (%d terms, %d listed): it cannot be evaluated" %
+                                (e["chip"], e["column"], e["support"], len(e["terms"])))
+            m = np.asarray(main_matrices[e["chip"]], dtype=np.uint64)
+            acc = np.full(m.shape[0], e["l0"], dtype=np.uint64)
+            for col, coef in e["terms"]:
+                acc = (acc + m[:, col] % np.uint64(P) * np.uint64(coef)) % np.uint64(P)
+            if acc.any():
+                bad.append((e["chip"], e["column"]))
+        return bad
+
+    def to_dict(self):
+        return dict(max_terms=self.max_terms, truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms,
+                    host_ms=self.host_ms, evaluations=self.evaluations, chips=self.chips, entries=self.entries)
+
+
+def _invariant_opts(max_entries, max_rows_per_entry, max_terms, chips):
+    # as _rank_opts: explicit zeros are refused here, with the library's status code
+    if int(max_entries) < 1 or int(max_rows_per_entry) < 1 or int(max_terms) < 1:
+        raise VgpuError(-1, "invariant_audit: max_entries, max_rows_per_entry and max_terms must be at least 1")
+    return InvariantAuditOpts(int(max_entries), int(max_rows_per_entry), _chip_mask("invariant", chips), int(max_terms), (ctypes.c_uint32 * 3)(0, 0, 0))
+
+
+def invariant_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, chips=None):
+    """The invariant audit on the HOST (vgpu_invariant_audit_host: no device, one thread): main_matrices = one canonical matrix per chip,
+    preprocessed = [(chip index, matrix)], max_terms = the (column, coefficient) terms listed per invariant, chips = the chip indices to audit
+    (default: all); an InvariantReport back."""
+    opts = _invariant_opts(max_entries, max_rows_per_entry, max_terms, chips)
+    return _audit_host("invariant", machine, main_matrices, preprocessed, opts)
+
+
 class FieldReport(_AuditReport):
     """The field audit of a witness (vgpu_field_audit / vgpu_field_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
     truncated, total_entries ((chip, interaction, field) with a floating row), reported,
@@ -1709,7 +1805,7 @@ def coverage_audit_host(machine, main_matrices, preprocessed, deltas=None, max_c
     return _audit_host("coverage", machine, main_matrices, preprocessed, opts)
 
 
-_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, field=FieldReport,
+_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, field=FieldReport,
                       link=LinkReport, coverage=CoverageReport)
 
 
@@ -1930,6 +2026,13 @@ class Prover:
         p - 1, 2), chips = the chip indices to audit (default: all); a StepReport back."""
         opts = _step_opts(steps, max_entries, max_rows_per_entry, chips)
         return self._audit("step", main, preprocessed, opts)
+
+    def invariant_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, chips=None):
+        """The affine-linear relations every row of each chip of this witness keeps, and on how many rows the chip's own constraints and bus
+        records enforce each of them to first order (vgpu_invariant_audit); the arguments of prove, max_terms = the (column, coefficient) terms
+        listed per invariant, chips = the chip indices to audit (default: all); an InvariantReport back."""
+        opts = _invariant_opts(max_entries, max_rows_per_entry, max_terms, chips)
+        return self._audit("invariant", main, preprocessed, opts)
 
     def field_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
         """Which fields of the chips' bus records this witness's constraints leave undetermined (vgpu_field_audit): per row and live record,

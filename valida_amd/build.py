@@ -32,6 +32,7 @@ SOURCES = [
     "kernels/field_audit.hip",
     "kernels/link_audit.hip",
     "kernels/step_audit.hip",
+    "kernels/invariant_audit.hip",
     "host/prover.cpp",
     "host/prover_audits.cpp",
     "host/sharded_prover.cpp",

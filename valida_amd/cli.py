@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -78,6 +78,16 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         0-7, 11-14 on 23 rows (whole lines: degree 3 <= 3 steps); refuted columns 5-8 on 72 rows` (a half with nothing to say is omitted; the
         parenthesis only when the steps are enough for the chip's constraint degree).  One row, THIS witness, the canonical vectors only: the
         exit status does not depend on this flag.
+        --invariants adds the invariant audit of the same witness (vgpu_invariant_audit: per chip every affine-linear relation among the main
+        columns that holds on every row of the witness — one per non-pivot column of the reduced row echelon form of the rows (1, M[r]) — and
+        per relation the rows on which the chip's own constraints and bus records enforce it to first order, judged against the rank audit's
+        Jacobian), on the same path (device or --host), restricted by the same --chips.  The JSON report gets one more key, "invariants"
+        (InvariantReport.to_json's object); stdout gets one line per chip that has an invariant, `add: 7 invariants (4 constant columns);
+        enforced on every row: columns 12-14` (the parts name the RELATIONS by verdict — every row, `enforced on some rows`, `never enforced` —
+        and appear only when present; constant columns are counted, with `, N never enforced` when some are).  Never enforced is a candidate
+        missing constraint or a column this program never exercises.  Affine-linear relations only (b (b - 1) = 0 is not found), within one row
+        (none between a row and its successor), on THIS witness (a short program has accidental relations), per basis vector (a sum of two
+        free invariants can be enforced), first order with the rank audit's caveats: the exit status does not depend on this flag.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -281,6 +291,32 @@ def step_lines(report):
     return lines
 
 
+def invariant_lines(report):
+    """One line per chip of an invariant report that has an invariant: how many, the constant columns among them, the relations by verdict."""
+    import valida_amd as va
+
+    lines = []
+    for c in report.chips:
+        if not c["invariants"]:
+            continue
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        mine = [e for e in report.entries if e["chip"] == c["chip"]]
+        consts = [e for e in mine if e["kind"] == "constant"]
+        rel = [e for e in mine if e["kind"] == "relation"]
+        head = "%d invariant%s" % (c["invariants"], "" if c["invariants"] == 1 else "s")
+        if c["constant_columns"]:
+            loose = len([e for e in consts if e["enforced_rows"] == 0])
+            head += " (%d constant column%s%s)" % (c["constant_columns"], "" if c["constant_columns"] == 1 else "s", ", %d never enforced" % loose if loose else "")
+        parts = [head]
+        for label, keep in (("enforced on every row", lambda e: e["free_rows"] == 0), ("enforced on some rows", lambda e: e["free_rows"] and e["enforced_rows"]),
+                            ("never enforced", lambda e: e["enforced_rows"] == 0)):
+            cols = [e["column"] for e in rel if keep(e)]
+            if cols:
+                parts.append("%s: columns %s" % (label, index_ranges(cols)))
+        lines.append("%s: %s" % (name, "; ".join(parts)))
+    return lines
+
+
 def field_lines(report):
     """One line per (chip, interaction) of a field report with a floating field: the bus, the fields, the most rows one of them floats on."""
     import valida_amd as va
@@ -383,8 +419,11 @@ def main(argv=None):
                     "no chip on the bus pins them; first order, on this witness, each record judged alone; never changes the exit status)")
     ap.add_argument("--steps", action="store_true", help="check: also the step audit (finite steps along each row's null directions: which of the rank audit's "
                     "freedoms are trades every check accepts, which are first-order artefacts; never changes the exit status)")
+    ap.add_argument("--invariants", action="store_true", help="check: also the invariant audit (the affine-linear relations every row of a chip keeps on this witness, "
+                    "and on how many rows the chip's own constraints and bus records enforce each: never enforced = a candidate missing constraint or a column the "
+                    "program never exercises; affine-linear only, one row, this witness, per basis vector, first order; never changes the exit status)")
     ap.add_argument("--step-sizes", default="1,-1,2", help="check --steps: 1 to 4 distinct step sizes, comma-separated integers mod p (as --step-sizes=1,-1,2)")
-    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields / --steps: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
+    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields / --steps / --invariants: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -419,6 +458,7 @@ def main(argv=None):
                 freport = va.field_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.fields else None
                 lreport = va.link_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_tuples=args.max_tuples, max_records_per_tuple=args.max_records) if args.links else None
                 sreport = va.step_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), steps=parse_deltas(args.step_sizes), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.steps else None
+                ireport = va.invariant_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.invariants else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -433,6 +473,7 @@ def main(argv=None):
                 freport = prover.field_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips)) if args.fields else None
                 lreport = prover.link_audit(main, prep, max_tuples=args.max_tuples, max_records_per_tuple=args.max_records) if args.links else None
                 sreport = prover.step_audit(main, prep, steps=parse_deltas(args.step_sizes), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.steps else None
+                ireport = prover.invariant_audit(main, prep, max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.invariants else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -450,12 +491,15 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), links=lreport.to_dict()))
             if sreport is not None:
                 text = json.dumps(dict(json.loads(text), steps=sreport.to_dict()))
+            if ireport is not None:
+                text = json.dumps(dict(json.loads(text), invariants=ireport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
                     coverage_lines(kreport) if kreport is not None else []) + (pair_lines(preport) if preport is not None else []) + (
                     rank_lines(rreport) if rreport is not None else []) + (field_lines(freport) if freport is not None else []) + (
-                    link_lines(lreport) if lreport is not None else []) + (step_lines(sreport) if sreport is not None else []):
+                    link_lines(lreport) if lreport is not None else []) + (step_lines(sreport) if sreport is not None else []) + (
+                    invariant_lines(ireport) if ireport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

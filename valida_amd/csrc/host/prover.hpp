@@ -16,6 +16,7 @@
 #include "field_audit.hpp"
 #include "link_audit.hpp"
 #include "step_audit.hpp"
+#include "invariant_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -158,6 +159,10 @@ class Prover {
     // Step audit of a witness (host/step_audit.hpp, kernels/step_audit.hip): finite steps along the rank audit's canonical null vectors, judged by the
     // mutation audit's rule; queued on the context like the other audits, scratch from the pool.
     StepReport step_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const StepAuditOpts& opts);
+    // Invariant audit of a witness (host/invariant_audit.hpp, kernels/invariant_audit.hip): the affine-linear relations every row of a chip keeps
+    // (a streaming elimination of the augmented rows and a merge of the workgroups' bases) and, per relation, the rows on which the rank audit's
+    // Jacobian enforces it; queued on the context like the other audits, scratch from the pool.
+    InvariantReport invariant_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const InvariantAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

@@ -684,6 +684,156 @@ StepReport Prover::step_audit(const std::vector<const DeviceTrace*>& main, const
     return rep;
 }
 
+// ---- invariant audit (host/invariant_audit.hpp; kernels/invariant_audit.hip) -----------------------------------------------------------------
+InvariantReport Prover::invariant_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const InvariantAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const InvariantAuditOpts o = invariant_audit_checked_opts(opts_in, machine_.airs.size());
+    const auto tr = audit_traces<ConstraintShape>("invariant_audit", main, preprocessed);
+    std::vector<int> prep_slot;
+    invariant_audit_plan(machine_, tr.ms, tr.prep_chips, tr.ps, prep_slot);
+    const size_t NC = machine_.airs.size();
+    const uint32_t R = o.max_rows_per_entry;
+    // per chip its launch shapes: a chip that does not fit the LDS is refused before anything is queued (phase 2 with d = w, the most there can be)
+    std::vector<vk::IaArgs> args(NC);
+    InvariantReport rep;
+    rep.chips.resize(NC);
+    for (size_t i = 0; i < NC; i++) {
+        const AirDesc& air = machine_.airs[i];
+        args[i] = vk::IaArgs{};
+        InvariantChipStat& cs = rep.chips[i];
+        invariant_audit_chip_block(cs, air, main[i]->height, invariant_audit_selected(o, i));
+        if (!cs.audited || !air.width) continue;
+        audit_chip_sizes(args[i].r, air, main[i]->height, fri_.interpret_air);
+        audit_chip_shape(air, [&] { vk::ia_basis_shape(args[i]); args[i].d = air.width; vk::ia_shape(args[i]); });
+    }
+
+    DeviceCtx& c = *ctx_;
+    AuditPass pass(c, main.size() + preprocessed.size());
+    const hipStream_t st = pass.stream;
+
+    uint64_t basis_words = 0, scratch_words = 0, rows_words = 0, desc_words_n = 0;
+    audit_or_no_memory(st, [&] {
+        // per chip: its weight rows and its slice of the basis scratch (u32 words): the workgroups' bases, the merged one
+        std::vector<uint64_t> wr_at(NC, 0), part_at(NC, 0), inv_at(NC, 0);
+        std::vector<size_t> e_at(NC + 1, 0);  // chip i's entries are [e_at[i], e_at[i + 1]) until the list is cut
+        std::vector<uint32_t> desc_words;
+        for (size_t i = 0; i < NC; i++) {
+            vk::RaArgs& a = args[i].r;
+            if (!a.width) continue;
+            pass.bind(a, main[i], audit_prep(preprocessed, prep_slot, i), prog_dev_[i]);
+            a.iw = iw_dev_[i].data;
+            const std::vector<uint32_t> wr = ra_weight_rows(machine_.airs[i]);
+            wr_at[i] = desc_words.size();
+            desc_words.insert(desc_words.end(), wr.begin(), wr.end());
+            part_at[i] = basis_words; basis_words += vk::ia_part_words(args[i]);
+            inv_at[i] = basis_words; basis_words += vk::ia_inv_words(args[i]);
+        }
+        if (desc_words.empty()) desc_words.push_back(0);
+        desc_words_n = desc_words.size();
+        DBuf desc(&c, desc_words);
+        for (size_t i = 0; i < NC; i++) args[i].r.wr = desc.data + wr_at[i];
+        c.check_launch("invariant_audit ingest");
+        DBuf basis(&c, (size_t)(basis_words ? basis_words : 1));
+        // the device pass: everything from here to the last download is between the two events
+        pass.begin();
+        // phase 1: every chip's invariant basis
+        for (size_t i = 0; i < NC; i++) {
+            if (!args[i].r.width) continue;
+            vk::launch_ia_basis(st, args[i], basis.data + part_at[i]);
+            vk::launch_ia_merge(st, args[i], basis.data + part_at[i], basis.data + inv_at[i]);
+        }
+        c.check_launch("invariant_audit basis");
+        {
+            std::vector<uint32_t> iv;
+            for (size_t i = 0; i < NC; i++) {
+                e_at[i] = rep.entries.size();
+                vk::IaArgs& ia = args[i];
+                ia.d = 0;
+                if (!ia.r.width) continue;
+                const uint32_t AW = ia.r.width + 1;
+                iv.resize(2 + AW);
+                c.download_small(iv.data(), basis.data + inv_at[i], iv.size() * 4);
+                const uint32_t d = iv[1];
+                if (iv[0] + d != AW || d > ia.r.width) throw std::logic_error("invariant_audit: the merged basis is inconsistent");
+                std::vector<uint8_t> pivot(AW);
+                for (uint32_t k = 0; k < AW; k++) pivot[k] = iv[2 + k] != 0;
+                std::vector<vg::Fp> vec((size_t)d * AW);
+                if (d) {
+                    iv.resize((size_t)d * AW);
+                    c.download_small(iv.data(), basis.data + inv_at[i] + 2 + AW, iv.size() * 4);
+                    for (size_t k = 0; k < vec.size(); k++) vec[k] = vg::Fp::raw(iv[k]);
+                }
+                invariant_audit_entries(rep.chips[i], (uint32_t)i, pivot, vec, o.max_terms, rep.entries);
+                ia.d = d;
+                ia.vec = basis.data + inv_at[i] + 2 + AW;
+                if (!d) continue;
+                vk::ia_shape(ia);  // with the chip's d: it fitted with d = w
+                ia.r.evaluations = ia.r.K ? (double)ia.r.n * ia.r.width * (ia.r.n == 1 ? 1 : 2) : 0;
+                rep.evaluations += ia.r.evaluations;
+            }
+            e_at[NC] = rep.entries.size();
+        }
+        // phase 2: per invariant the rows that do not enforce it
+        AuditScratch sc(NC);
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].d) sc.add(i, vk::ia_totals_words(args[i]), (uint64_t)args[i].d * args[i].r.NB);
+        scratch_words = sc.place_prefixes();
+        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
+        if (sc.zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)sc.zeroed * 4, st));
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].d) vk::launch_ia_count(st, args[i], reinterpret_cast<unsigned long long*>(scratch.data + sc.tot_at[i]), scratch.data + sc.tab_at[i]);
+        c.check_launch("invariant_audit count");
+        {
+            std::vector<uint32_t> tw;
+            for (size_t i = 0; i < NC; i++) {
+                if (!args[i].d) continue;
+                tw.resize(vk::ia_totals_words(args[i]));
+                c.download_small(tw.data(), scratch.data + sc.tot_at[i], tw.size() * 4);
+                for (uint32_t k = 0; k < args[i].d; k++) {
+                    InvariantEntry& en = rep.entries[e_at[i] + k];
+                    en.free_rows = audit_u64(tw, k);
+                    en.enforced = rep.chips[i].height - en.free_rows;
+                }
+            }
+        }
+        invariant_audit_finish(rep, o);
+        // the listed invariants of a chip are its first ones: entry e of the list is invariant e - e_at[chip]
+        audit_chip_runs(rep.entries, [&](uint32_t chip, size_t e0, size_t e1) {
+            rows_words = std::max<uint64_t>(rows_words, (uint64_t)(e1 - e0) * R);
+            (void)chip;
+        });
+        DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
+        audit_chip_runs(rep.entries, [&](uint32_t chip, size_t e0, size_t e1) {
+            bool any = false;
+            for (size_t e = e0; e < e1; e++) any |= rep.entries[e].free_rows != 0;
+            if (!any) return;
+            // the listed invariants of one chip: scan, list, one download
+            const vk::IaArgs& ia = args[chip];
+            const uint32_t i_cut = (uint32_t)(e1 - e0);
+            const size_t words = (size_t)i_cut * R;
+            VG_HIP_CHECK(hipMemsetAsync(out.data, 0, words * 4, st));
+            vk::launch_ra_scan(st, ia.r, scratch.data + sc.tab_at[chip], scratch.data + sc.pre_at[chip], i_cut);
+            vk::launch_ia_list(st, ia, scratch.data + sc.tab_at[chip], scratch.data + sc.pre_at[chip], i_cut, R, out.data);
+            c.check_launch("invariant_audit list");
+            std::vector<uint32_t> w(words);
+            c.download_small(w.data(), out.data, w.size() * 4);
+            for (size_t e = e0; e < e1; e++) {
+                InvariantEntry& en = rep.entries[e];
+                const uint64_t listed = std::min<uint64_t>(en.free_rows, R);
+                en.rows.assign(w.begin() + (e - e0) * R, w.begin() + (e - e0) * R + (size_t)listed);
+            }
+        });
+        pass.end(rep);
+    }, [&] {
+        return std::string("invariant_audit: the device pool cannot give the pass its scratch: per chip (w + 1) (w + 2) words per workgroup of phase 1 (at most 2048, 64 MB) and a sixteenth of that for the merge tree, (w + 1)^2 + 2 of merged basis (" +
+                           std::to_string(basis_words * 4) + " bytes for this witness), 8 bytes per invariant of totals and 8 per (invariant, workgroup of rows) (" + std::to_string(scratch_words * 4) +
+                           " bytes), " + std::to_string(desc_words_n * 4) + " bytes of interaction weight rows, " + std::to_string(rows_words * 4) +
+                           " bytes of listed rows, plus the working-layout copies of uploaded traces; chip_mask audits fewer chips at a time");
+    });
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 // ---- field audit (host/field_audit.hpp; kernels/field_audit.hip) ---------------------------------------------------------------------------
 FieldReport Prover::field_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const RankAuditOpts& opts_in) {
     const auto t_host = Clock::now();

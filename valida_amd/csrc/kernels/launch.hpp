@@ -277,6 +277,32 @@ void sa_shape(SaArgs& a);  // ra_shape for this audit's LDS; throws std::invalid
 size_t sa_lds_bytes(const SaArgs& a, uint32_t NW, uint32_t T);
 void launch_sa_count(hipStream_t st, const SaArgs& a, unsigned long long* totals, uint32_t* table);
 void launch_sa_list(hipStream_t st, const SaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t c_cut, uint32_t R, uint32_t* rows);
+// invariant_audit.hip — the passes of the invariant audit (host/invariant_audit.hpp: contract; Prover::invariant_audit drives them), per chip.
+// Phase 1: NB1 workgroups of one wave eliminate RB consecutive augmented rows (1, M[r][0..w)) each into a reduced basis; part: per workgroup
+// w + 1 pivot flags and [w + 1][w + 1] basis rows (row p: the row of pivot column p; rows of other columns are not written).  The merge (a tree
+// of fan IA_MERGE_FAN, one wave per node) eliminates them into one basis; inv: [0] rho_A, [1] d, [2 + c] pivot flag of augmented column c, then d vectors of w + 1 Montgomery
+// words, the i-th non-pivot column's canonical invariant.  Phase 2: the rank audit's launch shape and inputs plus the d invariants;
+// totals: u64 [i] free rows of invariant i (zeroed); table / prefix: [d][NB] u32 free rows per workgroup and their exclusive prefix (table
+// zeroed; the scan is launch_ra_scan); rows: [d][R] u32.
+struct IaArgs {
+    RaArgs r;             // evaluations: the rank audit's dual row evaluations at most
+    uint32_t d;           // invariants of the chip (known after the merge)
+    const uint32_t* vec;  // inv + 2 + (w + 1): the merge's vectors, row stride w + 1
+    uint32_t RB, NB1;     // ia_basis_shape
+};
+constexpr uint32_t IA_MAX_WIDTH = 191, IA_MAX_WORKGROUPS = 2048, IA_TILE_ROWS = 32, IA_MERGE_FAN = 16;
+// the workgroups' slots and, behind them, the spare slots of the merge tree's second level (the levels ping-pong)
+inline uint64_t ia_part_words(const IaArgs& a) { return ((uint64_t)a.NB1 + (a.NB1 + IA_MERGE_FAN - 1) / IA_MERGE_FAN) * (a.r.width + 1ull) * (a.r.width + 2ull); }
+inline uint64_t ia_inv_words(const IaArgs& a) { return 2ull + (a.r.width + 1ull) * (a.r.width + 1ull); }
+inline uint64_t ia_totals_words(const IaArgs& a) { return 2ull * a.d; }  // u32 words of the u64 totals
+size_t ia_basis_lds_bytes(uint32_t width);
+void ia_basis_shape(IaArgs& a);  // RB and NB1 from the height; throws std::invalid_argument when the chip's basis does not fit the LDS
+void launch_ia_basis(hipStream_t st, const IaArgs& a, uint32_t* part);
+void launch_ia_merge(hipStream_t st, const IaArgs& a, uint32_t* part, uint32_t* inv);  // part is overwritten by the levels of the tree
+void ia_shape(IaArgs& a);  // ra_shape for this audit's LDS with a.d invariants; throws std::invalid_argument when the chip does not fit
+size_t ia_lds_bytes(const IaArgs& a, uint32_t NW, uint32_t T);
+void launch_ia_count(hipStream_t st, const IaArgs& a, unsigned long long* totals, uint32_t* table);
+void launch_ia_list(hipStream_t st, const IaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t i_cut, uint32_t R, uint32_t* rows);
 // field_audit.hip — the passes of the field audit (host/field_audit.hpp: contract; Prover::field_audit drives them), per chip.  One wave per
 // trace row, one wave per workgroup, T rows per workgroup one after the other, NB workgroups.  A SLOT of a chip is (interaction, field) in
 // order, NS of them.  totals: u64 [0] live records, [1] floating fields, [2] rows with a floating field, [3 + m] live rows of interaction m,
