@@ -832,6 +832,68 @@ const uint32_t* vgpu_invariant_report_words(const vgpu_invariant_report_t* r);
 void vgpu_invariant_report_timing(const vgpu_invariant_report_t* r, double out[3]);
 void vgpu_invariant_report_free(vgpu_invariant_report_t* r);
 
+/* ---- Transition audit: the invariant audit over a two-row window and under a gate: the affine-linear relations between a row and its successor
+ * that the WITNESS keeps on every window, or on every window where a boolean column holds one value, and the windows at which the chip's own
+ * constraints and records hold each of them to first order.  Inputs: exactly what vgpu_prove and the audits take.
+ *   windows      chip h, main matrix M (n x w): window r = 0 .. n - 2 (no wrap: the AIR's when_transition domain) is the row
+ *                a_r = (1, M[r][0..w), M[r + 1][0..w)) of AW = 2 w + 1 WINDOW COLUMNS: 0 the constant, 1 + c `local` c, 1 + w + c `next` c.
+ *                n = 1: no windows; the chip's block keeps its first six words, the rest 0.
+ *   gates        window column j >= 1 is BOOLEAN when its values over all windows lie in {0, 1} and both occur.  Gate 0: every window; then for
+ *                every boolean j ascending (j = 1), (j = 0).  max_gates cuts this list (gate 0 included); n_bool and n_gates stay exact.  A gate
+ *                of fewer than min_gate_windows windows is listed but not audited; gate 0 always is.
+ *   space        R_g = the reduced row echelon form of the a_r of the windows where g holds, columns in that order (unique: no grid, tree or
+ *                row order changes a word); rho_g, d_g = AW - rho_g; pivots(g) is a subset of pivots(0).
+ *   entries      the canonical vector of a non-pivot column f: l_f = 1, l_p = -R_g[row of p][f] for the pivots p (left of f), 0 elsewhere.  Gate 0
+ *                lists every non-pivot f of the `next` block whose vector has a non-zero `local` coefficient (kind 2) and counts the others
+ *                (local_only: the invariant audit's subject; next_only: the same relations shifted).  Gate g >= 1 lists every f in
+ *                pivots(0) \ pivots(g) but the gate's own column.  kind 0: a constant (only l_0 and l_f), 1: one block, 2: both blocks.
+ *   verdict      per window r of the entry's gate, J the rank audit's Jacobian (the same matrix, word for word): FREE at r iff l's `local` part
+ *                is outside the row space of J_r or its `next` part outside that of J_{r + 1}, otherwise HELD at r.  One-sided: free is a
+ *                certificate; held is exact for a chip none of whose constraints reads `next`, otherwise "no one-row move breaks it".
+ * What it is not: affine-linear only; single gates (no conjunction of two gates); no joint 2 w-column Jacobian; THIS witness; per basis vector;
+ * first order, with the rank audit's caveats; `check`'s exit status never depends on it.
+ * Options: max_entries, max_rows_per_entry, chip_mask as vgpu_rank_audit_opts_t, same defaults and refusals (entries cut from the list are not
+ * judged); max_terms: (window column, coefficient) terms listed per entry, 0 the default 8, at most 4096; min_gate_windows: 0 the default 64;
+ * max_gates: 0 the default 256, at most 4096; opts may be NULL; reserved != 0 is refused.
+ * vgpu_transition_audit runs on the device (kernels/transition_audit.hip), queued on the prover context: the column flags (ballots per wave, one
+ * OR per workgroup), a streaming exact elimination of the gated windows (one wave per slice, gates over the grid's y, a tree of fan 16 to the one
+ * RREF per gate), then per trace row the rank audit's dual evaluation and LDS elimination and up to two reduce-only sweeps per listed entry, one
+ * bit per (entry, half, row); free windows are counted and listed by count -> scan -> list, no atomic admits a row.  VGPU_ERR_INVALID_ARG with
+ * the chip's name and the arithmetic for a chip with 2 w + 1 > 184 or whose phase 2 does not fit 160 KB of LDS with one wave and one entry
+ * staged; VGPU_ERR_OOM with the arithmetic when the pool cannot give the scratch.
+ * vgpu_transition_audit_host: the same contract on the host, one thread, no limits.
+ * Report image (vgpu_transition_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x31525456 "VTR1" [1] word count [2] max_terms [3] truncated [4,5] total_entries (exact even when the list is cut) [6] reported
+ *   [7] n_chips [8] gate blocks [9] min_gate_windows [10] max_gates [11] 0
+ *   per chip, in machine order, 16 words: width, constraints, interactions, audited (0 / 1), height (u64), n_bool, n_gates = 1 + 2 n_bool, gates
+ *   listed, gates audited, rho_0, d_0, local_only, next_only, transitions (the three split d_0), gated (entries of the gates >= 1).
+ *   per listed gate, ascending (chip, position), 10 words: chip, window column (0: gate 0), value, audited, windows (u64), rho_g, d_g, entries
+ *   of the gate (exact), 0.
+ *   per entry, ascending (chip, gate, column f), 14 + 2 T + L words: chip, gate column, gate value, window column f, kind, l_0, support (window
+ *   columns >= 1 with a non-zero coefficient, f included; exact), T = min(support, max_terms), L = min(free_windows, max_rows_per_entry), 0,
+ *   free_windows (u64), held_windows (u64), then T (window column, coefficient) terms ascending, then the first L free windows, ascending. */
+typedef struct vgpu_transition_audit_opts {
+    uint64_t max_entries;
+    uint32_t max_rows_per_entry;
+    uint32_t chip_mask;
+    uint32_t max_terms;
+    uint32_t min_gate_windows;
+    uint32_t max_gates;
+    uint32_t reserved[3];
+} vgpu_transition_audit_opts_t;
+typedef struct vgpu_transition_report vgpu_transition_report_t;
+int32_t vgpu_transition_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                              uint32_t n_prep, const vgpu_transition_audit_opts_t* opts, vgpu_transition_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_transition_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                                   const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                                   const vgpu_transition_audit_opts_t* opts, vgpu_transition_report_t** out);
+uint64_t vgpu_transition_report_len(const vgpu_transition_report_t* r);
+const uint32_t* vgpu_transition_report_words(const vgpu_transition_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: dual row evaluations of phase 2 */
+void vgpu_transition_report_timing(const vgpu_transition_report_t* r, double out[3]);
+void vgpu_transition_report_free(vgpu_transition_report_t* r);
+
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
  *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct

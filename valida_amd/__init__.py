@@ -1497,6 +1497,120 @@ def invariant_audit_host(machine, main_matrices, preprocessed, max_entries=1024,
     return _audit_host("invariant", machine, main_matrices, preprocessed, opts)
 
 
+class TransitionAuditOpts(ctypes.Structure):  # vgpu_transition_audit_opts_t
+    _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("max_terms", ctypes.c_uint32),
+                ("min_gate_windows", ctypes.c_uint32), ("max_gates", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
+
+
+class TransitionReport(_AuditReport):
+    """The transition audit of a witness (vgpu_transition_audit / vgpu_transition_audit_host; the contract is stated in include/vgpu.h), as plain
+    Python values: max_terms, min_gate_windows, max_gates, truncated, total_entries, reported,
+    chips = [dict(chip, width, constraints, interactions, audited, height, n_bool, n_gates, gates_listed, gates_audited, rank (rho_0), dim (d_0),
+    local_only, next_only, transitions (d_0 split three ways), gated (entries of the gates >= 1))],
+    gates = [dict(chip, column, value, audited, windows, rank, dim, entries)] (column 0: gate 0, every window),
+    entries = [dict(chip, gate=(window column, value) or None, column f, kind ("constant" / "one_block" / "both_blocks"), l0, support,
+    terms=[(window column, coefficient)], free_windows, held_windows, rows=[the first free windows])] ascending by (chip, gate, column):
+    l0 + sum(coefficient * a_r[window column]) = 0 on every window r of the gate, a_r = (1, M[r], M[r + 1]): window column 1 + c is `local`
+    column c, 1 + width + c is `next` column c.
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (dual row evaluations of the verdicts).
+    Affine-linear, single gates, THIS witness, per basis vector, first order and one row at a time: candidates for missing transition
+    constraints, not findings."""
+
+    KINDS = ("constant", "one_block", "both_blocks")
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 12 or w[0] != 0x31525456 or w[1] != len(w):
+            raise ValueError("not a transition report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.max_terms = w[2]
+        self.truncated = bool(w[3])
+        self.total_entries, self.reported = w[4] | (w[5] << 32), w[6]
+        self.min_gate_windows, self.max_gates = w[9], w[10]
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 12
+        self.chips = []
+        for c in range(w[7]):
+            self.chips.append(dict(chip=c, width=w[pos], constraints=w[pos + 1], interactions=w[pos + 2], audited=bool(w[pos + 3]), height=u64(pos + 4), n_bool=w[pos + 6],
+                                   n_gates=w[pos + 7], gates_listed=w[pos + 8], gates_audited=w[pos + 9], rank=w[pos + 10], dim=w[pos + 11], local_only=w[pos + 12],
+                                   next_only=w[pos + 13], transitions=w[pos + 14], gated=w[pos + 15]))
+            pos += 16
+        self.gates = []
+        for _ in range(w[8]):
+            self.gates.append(dict(chip=w[pos], column=w[pos + 1], value=w[pos + 2], audited=bool(w[pos + 3]), windows=u64(pos + 4), rank=w[pos + 6], dim=w[pos + 7],
+                                   entries=w[pos + 8]))
+            pos += 10
+        self.entries = []
+        for _ in range(self.reported):
+            T, L = w[pos + 7], w[pos + 8]
+            at = pos + 14
+            self.entries.append(dict(chip=w[pos], gate=(w[pos + 1], w[pos + 2]) if w[pos + 1] else None, column=w[pos + 3], kind=self.KINDS[w[pos + 4]], l0=w[pos + 5],
+                                     support=w[pos + 6], terms=[(w[at + 2 * i], w[at + 2 * i + 1]) for i in range(T)], free_windows=u64(pos + 10),
+                                     held_windows=u64(pos + 12), rows=w[at + 2 * T:at + 2 * T + L]))
+            pos = at + 2 * T + L
+        assert pos == len(w)
+
+    def name_of(self, chip, window_column):
+        """'1', 'local[c]' or 'next[c]' for a window column of `chip`."""
+        W = self.chips[chip]["width"]
+        if window_column == 0:
+            return "1"
+        return "local[%d]" % (window_column - 1) if window_column <= W else "next[%d]" % (window_column - 1 - W)
+
+    def never_held(self, chip):
+        """The listed entries of `chip` that no window of their gate holds: candidates for a missing transition constraint."""
+        return [e for e in self.entries if e["chip"] == chip and e["held_windows"] == 0]
+
+    def holds(self, main_matrices):
+        """The (chip, gate, column) triples of the listed entries whose relation FAILS on some window of its gate in the given canonical traces (one
+        matrix per chip; plain numpy, no library call): [] on the audited witness, and a way to test one witness's relations against another
+        program's traces.  Raises for an entry whose vector was cut at max_terms."""
+        bad = []
+        for e in self.entries:
+            if e["support"] > len(e["terms"]):
+                raise VgpuError(-1, "transition_audit: the vector of chip %d gate %s column %d is cut (%d terms, %d listed): it cannot be evaluated" %
+                                (e["chip"], e["gate"], e["column"], e["support"], len(e["terms"])))
+            m = np.asarray(main_matrices[e["chip"]], dtype=np.uint64) % np.uint64(P)
+            if m.shape[0] < 2:
+                continue
+            a = np.concatenate([np.ones((m.shape[0] - 1, 1), dtype=np.uint64), m[:-1], m[1:]], axis=1)  # the windows
+            acc = np.full(a.shape[0], e["l0"], dtype=np.uint64)
+            for col, coef in e["terms"]:
+                acc = (acc + a[:, col] * np.uint64(coef)) % np.uint64(P)
+            if e["gate"] is not None:
+                acc = acc[a[:, e["gate"][0]] == np.uint64(e["gate"][1])]
+            if acc.any():
+                bad.append((e["chip"], e["gate"], e["column"]))
+        return bad
+
+    def to_dict(self):
+        return dict(max_terms=self.max_terms, min_gate_windows=self.min_gate_windows, max_gates=self.max_gates, truncated=self.truncated, total_entries=self.total_entries,
+                    reported=self.reported, device_ms=self.device_ms, host_ms=self.host_ms, evaluations=self.evaluations, chips=self.chips, gates=self.gates, entries=self.entries)
+
+
+def _transition_opts(max_entries, max_rows_per_entry, max_terms, min_gate_windows, max_gates, chips):
+    # as _rank_opts: explicit zeros are refused here, with the library's status code
+    if int(max_entries) < 1 or int(max_rows_per_entry) < 1 or int(max_terms) < 1 or int(min_gate_windows) < 1 or int(max_gates) < 1:
+        raise VgpuError(-1, "transition_audit: max_entries, max_rows_per_entry, max_terms, min_gate_windows and max_gates must be at least 1")
+    if int(min_gate_windows) > 0xFFFFFFFF or int(max_gates) > 0xFFFFFFFF or int(max_terms) > 0xFFFFFFFF:
+        raise VgpuError(-1, "transition_audit: max_terms, min_gate_windows and max_gates are 32-bit counts")
+    return TransitionAuditOpts(int(max_entries), int(max_rows_per_entry), _chip_mask("transition", chips), int(max_terms), int(min_gate_windows), int(max_gates),
+                               (ctypes.c_uint32 * 3)(0, 0, 0))
+
+
+def transition_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, min_gate_windows=64, max_gates=256, chips=None):
+    """The transition audit on the HOST (vgpu_transition_audit_host: no device, one thread, no width limit): main_matrices = one canonical
+    matrix per chip, preprocessed = [(chip index, matrix)], max_terms = the (window column, coefficient) terms listed per entry,
+    min_gate_windows = the fewest windows of an audited gate, max_gates = the gates listed per chip, chips = the chip indices to audit (default:
+    all); a TransitionReport back."""
+    opts = _transition_opts(max_entries, max_rows_per_entry, max_terms, min_gate_windows, max_gates, chips)
+    return _audit_host("transition", machine, main_matrices, preprocessed, opts)
+
+
 class FieldReport(_AuditReport):
     """The field audit of a witness (vgpu_field_audit / vgpu_field_audit_host; the contract is stated in include/vgpu.h), as plain Python values:
     truncated, total_entries ((chip, interaction, field) with a floating row), reported,
@@ -1805,7 +1919,7 @@ def coverage_audit_host(machine, main_matrices, preprocessed, deltas=None, max_c
     return _audit_host("coverage", machine, main_matrices, preprocessed, opts)
 
 
-_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, field=FieldReport,
+_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, field=FieldReport,
                       link=LinkReport, coverage=CoverageReport)
 
 
@@ -2033,6 +2147,14 @@ class Prover:
         listed per invariant, chips = the chip indices to audit (default: all); an InvariantReport back."""
         opts = _invariant_opts(max_entries, max_rows_per_entry, max_terms, chips)
         return self._audit("invariant", main, preprocessed, opts)
+
+    def transition_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, min_gate_windows=64, max_gates=256, chips=None):
+        """Which affine-linear relations between a row and its successor this witness keeps, on every window or under a boolean gate, and at
+        which windows the chip's constraints and records hold each of them to first order (vgpu_transition_audit); the arguments of prove,
+        max_terms = the (window column, coefficient) terms listed per entry, min_gate_windows = the fewest windows of an audited gate, max_gates
+        = the gates listed per chip, chips = the chip indices to audit (default: all); a TransitionReport back."""
+        opts = _transition_opts(max_entries, max_rows_per_entry, max_terms, min_gate_windows, max_gates, chips)
+        return self._audit("transition", main, preprocessed, opts)
 
     def field_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None):
         """Which fields of the chips' bus records this witness's constraints leave undetermined (vgpu_field_audit): per row and live record,

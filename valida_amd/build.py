@@ -33,6 +33,7 @@ SOURCES = [
     "kernels/link_audit.hip",
     "kernels/step_audit.hip",
     "kernels/invariant_audit.hip",
+    "kernels/transition_audit.hip",
     "host/prover.cpp",
     "host/prover_audits.cpp",
     "host/sharded_prover.cpp",

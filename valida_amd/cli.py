@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -88,6 +88,15 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         missing constraint or a column this program never exercises.  Affine-linear relations only (b (b - 1) = 0 is not found), within one row
         (none between a row and its successor), on THIS witness (a short program has accidental relations), per basis vector (a sum of two
         free invariants can be enforced), first order with the rank audit's caveats: the exit status does not depend on this flag.
+        --transitions adds the transition audit of the same witness (vgpu_transition_audit: the invariant audit over the two-row windows
+        (1, M[r], M[r + 1]), r = 0 .. n - 2, on every window and on the windows where a boolean window column holds one value — the gates — and
+        per listed relation the windows at which the rank audit's Jacobian of one of the two rows lets it break), on the same path (device or
+        --host), restricted by the same --chips; --min-gate-windows N (default 64) is the fewest windows of an audited gate, --max-gates N
+        (default 256) the gates listed per chip.  The JSON report gets one more key, "transitions" (TransitionReport.to_json's object); stdout
+        gets one line per chip that has an entry, `mem: 1 transition relation (0 held on every window); 21 gated relations under 8 of 11
+        audited gates (13 gates in all), 5 never held`.  Never held is a candidate missing transition constraint.  Affine-linear, single gates
+        (no conjunction of two), THIS witness, per basis vector, first order and one row at a time (held is exact only for chips whose
+        constraints do not read the next row): the exit status does not depend on this flag.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -291,6 +300,30 @@ def step_lines(report):
     return lines
 
 
+def transition_lines(report):
+    """One line per chip of a transition report that has an entry: the ungated transition relations, the gated ones and their gates."""
+    import valida_amd as va
+
+    lines = []
+    for c in report.chips:
+        if not c["transitions"] and not c["gated"]:
+            continue
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        mine = [e for e in report.entries if e["chip"] == c["chip"]]
+        ungated = [e for e in mine if e["gate"] is None]
+        gated = [e for e in mine if e["gate"] is not None]
+        parts = []
+        if c["transitions"]:
+            parts.append("%d transition relation%s (%d held on every window)" % (c["transitions"], "" if c["transitions"] == 1 else "s", len([e for e in ungated if not e["free_windows"]])))
+        if c["gated"]:
+            under = len(set(e["gate"] for e in gated))
+            cut = "" if len(gated) == c["gated"] else ", %d listed" % len(gated)
+            parts.append("%d gated relation%s%s under %d of %d audited gates (%d gates in all), %d never held" % (
+                c["gated"], "" if c["gated"] == 1 else "s", cut, under, c["gates_audited"], c["n_gates"], len([e for e in gated if not e["held_windows"]])))
+        lines.append("%s: %s" % (name, "; ".join(parts)))
+    return lines
+
+
 def invariant_lines(report):
     """One line per chip of an invariant report that has an invariant: how many, the constant columns among them, the relations by verdict."""
     import valida_amd as va
@@ -422,8 +455,13 @@ def main(argv=None):
     ap.add_argument("--invariants", action="store_true", help="check: also the invariant audit (the affine-linear relations every row of a chip keeps on this witness, "
                     "and on how many rows the chip's own constraints and bus records enforce each: never enforced = a candidate missing constraint or a column the "
                     "program never exercises; affine-linear only, one row, this witness, per basis vector, first order; never changes the exit status)")
+    ap.add_argument("--transitions", action="store_true", help="check: also the transition audit (the affine-linear relations between a row and its successor that this "
+                    "witness keeps on every window or under a boolean gate, and the windows at which the chip's constraints hold each: never held = a candidate missing "
+                    "transition constraint; affine-linear only, single gates, this witness, per basis vector, first order, one row at a time; never changes the exit status)")
+    ap.add_argument("--min-gate-windows", type=int, default=64, help="check --transitions: a gate that holds on fewer windows is counted but not audited (default 64)")
+    ap.add_argument("--max-gates", type=int, default=256, help="check --transitions: the gates listed per chip, the ungated one included (default 256)")
     ap.add_argument("--step-sizes", default="1,-1,2", help="check --steps: 1 to 4 distinct step sizes, comma-separated integers mod p (as --step-sizes=1,-1,2)")
-    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields / --steps / --invariants: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
+    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields / --steps / --invariants / --transitions: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -459,6 +497,8 @@ def main(argv=None):
                 lreport = va.link_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_tuples=args.max_tuples, max_records_per_tuple=args.max_records) if args.links else None
                 sreport = va.step_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), steps=parse_deltas(args.step_sizes), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.steps else None
                 ireport = va.invariant_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.invariants else None
+                treport = va.transition_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_terms=256, min_gate_windows=args.min_gate_windows, max_gates=args.max_gates,
+                                                   chips=parse_chips(args.chips)) if args.transitions else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -474,6 +514,7 @@ def main(argv=None):
                 lreport = prover.link_audit(main, prep, max_tuples=args.max_tuples, max_records_per_tuple=args.max_records) if args.links else None
                 sreport = prover.step_audit(main, prep, steps=parse_deltas(args.step_sizes), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.steps else None
                 ireport = prover.invariant_audit(main, prep, max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.invariants else None
+                treport = prover.transition_audit(main, prep, max_terms=256, min_gate_windows=args.min_gate_windows, max_gates=args.max_gates, chips=parse_chips(args.chips)) if args.transitions else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -493,13 +534,15 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), steps=sreport.to_dict()))
             if ireport is not None:
                 text = json.dumps(dict(json.loads(text), invariants=ireport.to_dict()))
+            if treport is not None:
+                text = json.dumps(dict(json.loads(text), transitions=treport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
                     coverage_lines(kreport) if kreport is not None else []) + (pair_lines(preport) if preport is not None else []) + (
                     rank_lines(rreport) if rreport is not None else []) + (field_lines(freport) if freport is not None else []) + (
                     link_lines(lreport) if lreport is not None else []) + (step_lines(sreport) if sreport is not None else []) + (
-                    invariant_lines(ireport) if ireport is not None else []):
+                    invariant_lines(ireport) if ireport is not None else []) + (transition_lines(treport) if treport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

@@ -17,6 +17,7 @@
 #include "link_audit.hpp"
 #include "step_audit.hpp"
 #include "invariant_audit.hpp"
+#include "transition_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -163,6 +164,11 @@ class Prover {
     // (a streaming elimination of the augmented rows and a merge of the workgroups' bases) and, per relation, the rows on which the rank audit's
     // Jacobian enforces it; queued on the context like the other audits, scratch from the pool.
     InvariantReport invariant_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const InvariantAuditOpts& opts);
+    // Transition audit of a witness (host/transition_audit.hpp, kernels/transition_audit.hip): the affine-linear relations between a row and its
+    // successor that every window keeps, or every window on which a boolean column holds one value (the invariant audit's elimination over two-row
+    // windows, gates over the grid's y), and per listed relation the windows at which the rank audit's Jacobian of either row lets it break;
+    // queued on the context like the other audits, scratch from the pool.
+    TransitionReport transition_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const TransitionAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

@@ -834,6 +834,187 @@ InvariantReport Prover::invariant_audit(const std::vector<const DeviceTrace*>& m
     return rep;
 }
 
+// ---- transition audit (host/transition_audit.hpp; kernels/transition_audit.hip) --------------------------------------------------------------
+TransitionReport Prover::transition_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const TransitionAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const TransitionAuditOpts o = transition_audit_checked_opts(opts_in, machine_.airs.size());
+    const auto tr = audit_traces<ConstraintShape>("transition_audit", main, preprocessed);
+    std::vector<int> prep_slot;
+    transition_audit_plan(machine_, tr.ms, tr.prep_chips, tr.ps, prep_slot);
+    const size_t NC = machine_.airs.size();
+    const uint32_t R = o.max_rows_per_entry;
+    // per chip its launch shapes: a chip that does not fit is refused before anything is queued (phase 1 by its window, phase 2 with one entry staged)
+    std::vector<vk::TaArgs> args(NC);
+    TransitionReport rep;
+    rep.chips.resize(NC);
+    for (size_t i = 0; i < NC; i++) {
+        const AirDesc& air = machine_.airs[i];
+        args[i] = vk::TaArgs{};
+        TransitionChipStat& cs = rep.chips[i];
+        transition_audit_chip_block(cs, air, main[i]->height, transition_audit_selected(o, i));
+        if (!transition_audit_has_windows(cs)) continue;
+        audit_chip_sizes(args[i].r, air, main[i]->height, fri_.interpret_air);
+        audit_chip_shape(air, [&] { vk::ta_basis_shape(args[i], o.max_gates); args[i].E = 0; vk::ta_shape(args[i]); });
+    }
+
+    DeviceCtx& c = *ctx_;
+    AuditPass pass(c, main.size() + preprocessed.size());
+    const hipStream_t st = pass.stream;
+
+    uint64_t flag_words = 0, basis_words = 0, entry_words = 0, bits_words = 0, desc_words_n = 0;
+    audit_or_no_memory(st, [&] {
+        std::vector<uint64_t> wr_at(NC, 0), fl_at(NC, 0);
+        std::vector<uint32_t> desc_words;
+        for (size_t i = 0; i < NC; i++) {
+            vk::RaArgs& a = args[i].r;
+            if (!a.width) continue;
+            pass.bind(a, main[i], audit_prep(preprocessed, prep_slot, i), prog_dev_[i]);
+            a.iw = iw_dev_[i].data;
+            const std::vector<uint32_t> wr = ra_weight_rows(machine_.airs[i]);
+            wr_at[i] = desc_words.size();
+            desc_words.insert(desc_words.end(), wr.begin(), wr.end());
+            // per window column a u64 of ones, then a u32 of flags (AW + 1 of them: the next chip's u64 stay 8-byte aligned)
+            fl_at[i] = flag_words; flag_words += 3ull * (2ull * a.width + 2);
+        }
+        if (desc_words.empty()) desc_words.push_back(0);
+        desc_words_n = desc_words.size();
+        DBuf desc(&c, desc_words);
+        for (size_t i = 0; i < NC; i++) args[i].r.wr = desc.data + wr_at[i];
+        c.check_launch("transition_audit ingest");
+        DBuf flags(&c, (size_t)(flag_words ? flag_words : 1));
+        // the device pass: everything from here to the last download is between the two events
+        pass.begin();
+        // the boolean window columns of every chip
+        if (flag_words) VG_HIP_CHECK(hipMemsetAsync(flags.data, 0, (size_t)flag_words * 4, st));
+        for (size_t i = 0; i < NC; i++) {
+            if (!args[i].r.width) continue;
+            const uint64_t AW1 = 2ull * args[i].r.width + 2;
+            vk::launch_ta_flags(st, args[i], flags.data + fl_at[i] + 2 * AW1, reinterpret_cast<unsigned long long*>(flags.data + fl_at[i]));
+        }
+        c.check_launch("transition_audit flags");
+        std::vector<size_t> g_at(NC + 1, 0);  // chip i's gates are [g_at[i], g_at[i + 1])
+        {
+            std::vector<uint32_t> fw((size_t)flag_words);
+            if (flag_words) c.download_small(fw.data(), flags.data, fw.size() * 4);
+            for (size_t i = 0; i < NC; i++) {
+                g_at[i] = rep.gates.size();
+                if (!args[i].r.width) continue;
+                const uint32_t AW = 2 * args[i].r.width + 1;
+                std::vector<uint32_t> fl(AW);
+                std::vector<uint64_t> ones(AW);
+                for (uint32_t j = 0; j < AW; j++) { ones[j] = audit_u64(fw, (size_t)(fl_at[i] / 2) + j); fl[j] = fw[(size_t)fl_at[i] + 2 * (AW + 1) + j]; }
+                transition_audit_gates(rep.chips[i], (uint32_t)i, fl, ones, o, rep.gates);
+            }
+            g_at[NC] = rep.gates.size();
+        }
+        // phase 1: per chip the reduced basis of every audited gate, one chip's scratch at a time
+        for (size_t i = 0; i < NC; i++) {
+            vk::TaArgs& ta = args[i];
+            if (!ta.r.width) continue;
+            const uint32_t W = ta.r.width, AW = 2 * W + 1;
+            std::vector<uint32_t> gw;  // the audited gates, in order
+            std::vector<size_t> which;
+            for (size_t g = g_at[i]; g < g_at[i + 1]; g++) {
+                if (!rep.gates[g].audited) continue;
+                gw.push_back(rep.gates[g].column); gw.push_back(rep.gates[g].value ? vg::Fp::one().v : 0u);
+                which.push_back(g);
+            }
+            ta.G = (uint32_t)which.size();
+            vk::ta_basis_shape(ta, ta.G);
+            DBuf gates(&c, gw);
+            ta.gates = gates.data;
+            const uint64_t part_words = vk::ta_part_words(ta), inv_words = vk::ta_inv_words(ta);
+            basis_words = std::max(basis_words, part_words + ta.G * inv_words);
+            DBuf part(&c, (size_t)part_words), inv(&c, (size_t)(ta.G * inv_words));
+            vk::launch_ta_basis(st, ta, part.data);
+            vk::launch_ta_merge(st, ta, part.data, inv.data);
+            c.check_launch("transition_audit basis");
+            std::vector<uint32_t> iv((size_t)(ta.G * inv_words));
+            c.download_small(iv.data(), inv.data, iv.size() * 4);
+            TransitionBasis b0;
+            for (size_t k = 0; k < which.size(); k++) {
+                const uint32_t* v = iv.data() + k * inv_words;
+                const uint32_t d = v[1];
+                if (v[0] + d != AW || d >= AW) throw std::logic_error("transition_audit: the merged basis is inconsistent");
+                TransitionBasis b;
+                b.pivot.resize(AW);
+                for (uint32_t x = 0; x < AW; x++) b.pivot[x] = v[2 + x] != 0;
+                b.vec.resize((size_t)d * AW);
+                for (size_t x = 0; x < b.vec.size(); x++) b.vec[x] = vg::Fp::raw(v[2 + AW + x]);
+                if (k == 0) b0 = b;
+                transition_audit_entries(rep.chips[i], rep.gates[which[k]], b0, b, o.max_terms, rep.entries);
+            }
+            ta.gates = nullptr;
+        }
+        transition_audit_cut(rep, o);
+        // phase 2: the verdicts of the listed entries, one chip's scratch at a time
+        audit_chip_runs(rep.entries, [&](uint32_t chip, size_t e0, size_t e1) {
+            vk::TaArgs& ta = args[chip];
+            vk::RaArgs& a = ta.r;
+            const uint32_t W = a.width, E = (uint32_t)(e1 - e0);
+            std::vector<uint32_t> ev((size_t)E * 2 * W), eg((size_t)E * 4, 0);
+            std::vector<uint64_t> windows(E, 0);
+            for (uint32_t k = 0; k < E; k++) {
+                const TransitionEntry& en = rep.entries[e0 + k];
+                uint32_t nz = 0;
+                for (uint32_t x = 0; x < 2 * W; x++) { ev[(size_t)k * 2 * W + x] = en.l[1 + x].v; if (en.l[1 + x].v) nz |= x < W ? 1u : 2u; }
+                eg[4 * (size_t)k] = en.gate_column; eg[4 * (size_t)k + 1] = en.gate_value ? vg::Fp::one().v : 0u; eg[4 * (size_t)k + 2] = nz;
+                for (size_t g = g_at[chip]; g < g_at[chip + 1]; g++)
+                    if (rep.gates[g].column == en.gate_column && rep.gates[g].value == en.gate_value) windows[k] = rep.gates[g].windows;
+            }
+            ta.E = E;
+            vk::ta_shape(ta);  // with the chip's entries: it fitted with one
+            a.evaluations = a.K ? (double)a.n * a.width * 2 : 0;
+            rep.evaluations += a.evaluations;
+            const uint64_t tab = (uint64_t)E * ta.NB2;
+            entry_words = std::max<uint64_t>(entry_words, ev.size() + eg.size() + 2ull * E + 2 * tab + (uint64_t)E * R);
+            bits_words = std::max(bits_words, vk::ta_bits_words(ta));
+            DBuf evec(&c, ev), egate(&c, eg);
+            ta.evec = evec.data; ta.egate = egate.data;
+            DBuf bits(&c, (size_t)vk::ta_bits_words(ta));
+            DBuf scratch(&c, (size_t)(2ull * E + 2 * tab)), out(&c, (size_t)E * R);
+            uint32_t *table = scratch.data + 2ull * E, *prefix = table + tab;
+            VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)(2ull * E + tab) * 4, st));
+            vk::launch_ta_enforce(st, ta, bits.data);
+            vk::launch_ta_count(st, ta, bits.data, reinterpret_cast<unsigned long long*>(scratch.data), table);
+            c.check_launch("transition_audit count");
+            std::vector<uint32_t> tw(2 * (size_t)E);
+            c.download_small(tw.data(), scratch.data, tw.size() * 4);
+            bool any = false;
+            for (uint32_t k = 0; k < E; k++) {
+                TransitionEntry& en = rep.entries[e0 + k];
+                en.free_windows = audit_u64(tw, k);
+                if (en.free_windows > windows[k]) throw std::logic_error("transition_audit: more free windows than the gate has");
+                en.held_windows = windows[k] - en.free_windows;
+                any |= en.free_windows != 0;
+            }
+            if (any) {
+                VG_HIP_CHECK(hipMemsetAsync(out.data, 0, (size_t)E * R * 4, st));
+                vk::launch_ta_scan(st, ta, table, prefix);
+                vk::launch_ta_list(st, ta, bits.data, table, prefix, R, out.data);
+                c.check_launch("transition_audit list");
+                std::vector<uint32_t> w((size_t)E * R);
+                c.download_small(w.data(), out.data, w.size() * 4);
+                for (uint32_t k = 0; k < E; k++) {
+                    TransitionEntry& en = rep.entries[e0 + k];
+                    const uint64_t listed = std::min<uint64_t>(en.free_windows, R);
+                    en.rows.assign(w.begin() + (size_t)k * R, w.begin() + (size_t)k * R + (size_t)listed);
+                }
+            }
+            ta.evec = ta.egate = nullptr;
+        });
+        pass.end(rep);
+    }, [&] {
+        return std::string("transition_audit: the device pool cannot give the pass its scratch: 12 bytes per window column of flags (" + std::to_string(flag_words * 4) +
+                           " bytes), per chip and audited gate (2 w + 1) (2 w + 2) words per slice of phase 1 (at most 2048 slices and 128 MB per chip) and a sixteenth of that for the merge tree, (2 w + 1)^2 + 2 of merged basis (" +
+                           std::to_string(basis_words * 4) + " bytes for the largest chip of this witness), per chip with listed entries 8 w + 24 + 4 R bytes per entry and 8 per (entry, 256 windows or more) (" +
+                           std::to_string(entry_words * 4) + " bytes) and one bit per (entry, half, row) in words of 32 entries (" + std::to_string(bits_words * 4) + " bytes), " +
+                           std::to_string(desc_words_n * 4) + " bytes of interaction weight rows, plus the working-layout copies of uploaded traces; chip_mask audits fewer chips and max_entries lists fewer entries at a time");
+    });
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 // ---- field audit (host/field_audit.hpp; kernels/field_audit.hip) ---------------------------------------------------------------------------
 FieldReport Prover::field_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const RankAuditOpts& opts_in) {
     const auto t_host = Clock::now();

@@ -303,6 +303,44 @@ void ia_shape(IaArgs& a);  // ra_shape for this audit's LDS with a.d invariants;
 size_t ia_lds_bytes(const IaArgs& a, uint32_t NW, uint32_t T);
 void launch_ia_count(hipStream_t st, const IaArgs& a, unsigned long long* totals, uint32_t* table);
 void launch_ia_list(hipStream_t st, const IaArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t i_cut, uint32_t R, uint32_t* rows);
+// transition_audit.hip — the passes of the transition audit (host/transition_audit.hpp: contract; Prover::transition_audit drives them), per chip.
+// A WINDOW r = 0 .. n - 2 is the row (1, M[r][0..w), M[r + 1][0..w)) of AW = 2 w + 1 window columns.  Flags: per window column j >= 1 the OR of
+// TA_OUTSIDE / TA_ANY0 / TA_ANY1 over the windows, flags [AW] u32 and ones [AW] u64 the windows on which the column is 1 (both zeroed).  Phase 1:
+// grid (NB1, G): workgroup (x, g), one wave, eliminates the windows [x RB, x RB + RB) on which gate g holds into a reduced basis; part: per gate
+// NB1 + ceil(NB1 / 16) slots of AW pivot flags and [AW][AW] basis rows (the invariant audit's slot with w + 1 replaced by AW); the merge (a tree of
+// fan IA_MERGE_FAN, gates over gridDim.y) leaves per gate at inv + g ta_inv_words: [0] rho, [1] d, [2 + c] pivot flag of window column c, then d
+// vectors of AW Montgomery words.  Phase 2: the rank audit's launch shape and inputs plus the E listed entries: evec [E][2 w] (the `local` part of
+// the vector, then the `next` part), egate [E][4] (gate column, gate value as a Montgomery word, bit 0 / 1: the local / next part is non-zero, 0);
+// bits [n][2][EW] u32, EW = ceil(E / 32): bit e of [r][0]: window r exists, the entry's gate holds on it and the local part is outside the row
+// space of J_r; of [r][1]: the same for window r - 1 and the next part.  Count / list: grid (NB2, ceil(E / 256)), thread <-> entry, WPB windows per
+// workgroup: free at window r = [r][0] | [r + 1][1]; totals [E] u64 (zeroed), table / prefix [E][NB2] u32, rows [E][R] u32.
+struct TaArgs {
+    RaArgs r;               // evaluations: the rank audit's dual row evaluations at most
+    uint32_t RB, NB1;       // ta_basis_shape: windows per phase-1 slice, slices
+    uint32_t G;             // audited gates of the chip
+    const uint32_t* gates;  // [G][2] window column (0: every window), value as a Montgomery word
+    uint32_t E, EC;         // listed entries; entries staged in LDS at a time (ta_shape)
+    const uint32_t* evec;
+    const uint32_t* egate;
+    uint32_t WPB, NB2;      // ta_shape: windows per workgroup of the count and list passes, workgroups
+};
+constexpr uint32_t TA_MAX_WINDOW = 184, TA_TILE_WINDOWS = 32, TA_BOOL_ROWS = 4096;
+inline uint64_t ta_slot_words(const TaArgs& a) { return (2ull * a.r.width + 1) * (2ull * a.r.width + 2); }
+inline uint64_t ta_gate_slots(const TaArgs& a) { return (uint64_t)a.NB1 + (a.NB1 + IA_MERGE_FAN - 1) / IA_MERGE_FAN; }
+inline uint64_t ta_part_words(const TaArgs& a) { return (uint64_t)a.G * ta_gate_slots(a) * ta_slot_words(a); }
+inline uint64_t ta_inv_words(const TaArgs& a) { return 2ull + (2ull * a.r.width + 1) * (2ull * a.r.width + 1); }
+inline uint64_t ta_bits_words(const TaArgs& a) { return a.r.n * 2ull * ((a.E + 31u) / 32u); }
+size_t ta_basis_lds_bytes(uint32_t width);
+void ta_basis_shape(TaArgs& a, uint32_t gates);  // RB and NB1 for at most `gates` gates; throws std::invalid_argument when 2 w + 1 > TA_MAX_WINDOW
+void launch_ta_flags(hipStream_t st, const TaArgs& a, uint32_t* flags, unsigned long long* ones);
+void launch_ta_basis(hipStream_t st, const TaArgs& a, uint32_t* part);
+void launch_ta_merge(hipStream_t st, const TaArgs& a, uint32_t* part, uint32_t* inv);  // part is overwritten by the levels of the tree
+void ta_shape(TaArgs& a);  // ra_shape for this audit's LDS with a.E entries (0: the fit with one entry staged is checked); throws std::invalid_argument when the chip does not fit
+size_t ta_lds_bytes(const TaArgs& a, uint32_t NW, uint32_t T, uint32_t EC);
+void launch_ta_enforce(hipStream_t st, const TaArgs& a, uint32_t* bits);
+void launch_ta_count(hipStream_t st, const TaArgs& a, const uint32_t* bits, unsigned long long* totals, uint32_t* table);
+void launch_ta_scan(hipStream_t st, const TaArgs& a, const uint32_t* table, uint32_t* prefix);
+void launch_ta_list(hipStream_t st, const TaArgs& a, const uint32_t* bits, const uint32_t* table, const uint32_t* prefix, uint32_t R, uint32_t* rows);
 // field_audit.hip — the passes of the field audit (host/field_audit.hpp: contract; Prover::field_audit drives them), per chip.  One wave per
 // trace row, one wave per workgroup, T rows per workgroup one after the other, NB workgroups.  A SLOT of a chip is (interaction, field) in
 // order, NS of them.  totals: u64 [0] live records, [1] floating fields, [2] rows with a floating field, [3 + m] live rows of interaction m,
