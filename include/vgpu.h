@@ -276,6 +276,14 @@ int32_t vgpu_host_commit_root(const vgpu_config_t* cfg, const uint32_t* const* m
 /* FRI fold_even_odd of an Ext5 vector (n x 5 words, bit-reversed domain order) — App. B10 */
 int32_t vgpu_fri_fold(vgpu_prover_t* p, const uint32_t* f, uint64_t n, const uint32_t beta[5], uint32_t* out);
 
+/* Test hook: primitive `op` of the device's field arithmetic (kernels/field_probe.hip: reduce_once, sub_mod, the Montgomery reductions, Ext5
+ * products, the radix-16 butterfly network, the signed S-box, the Poseidon-16 permutation — the functions the proving kernels call) on n_items
+ * operand tuples, one work item each.  Operands and results are RAW STORED (Montgomery) WORDS, nothing is converted: word k of item i is
+ * operands[k * n_items + i] / results[k * n_items + i].  operand_words / result_words: the buffers' sizes, n_items times the op's words per item (else
+ * VGPU_ERR_INVALID_ARG).  Ops and their shapes: valida_amd.FIELD_PROBE_OPS.  Arithmetic operands outside an op's documented domain give
+ * unspecified words; a butterfly item whose low / lowbits would index past the twiddle tables is refused. */
+int32_t vgpu_field_probe(vgpu_prover_t* p, uint32_t op, const uint32_t* operands, uint64_t operand_words, uint64_t n_items, uint32_t* results, uint64_t result_words);
+
 /* Machine::prove (basic/src/lib.rs:147-675).  main[i] = trace of chip i; preprocessed traces are given
  * with their chip indices in chip order (BasicMachine: program, range).
  * debug_flags: 1 = keep the per-chip intermediate matrices (vgpu_proof_debug_*); 2 = run check_constraints and

@@ -60,6 +60,17 @@ def rust_type(ctype, names):
     return rust
 
 
+# A C identifier that is a Rust keyword (strict or reserved) becomes a raw identifier: `in` -> `r#in` (self / Self / super / crate cannot be raw: refused)
+RUST_KEYWORDS = set("""as break const continue dyn else enum extern false fn for if impl in let loop match mod move mut pub ref return static struct trait true
+type unsafe use where while async await abstract become box do final macro override priv typeof unsized virtual yield try gen""".split())
+
+
+def rust_ident(name):
+    if name in ("self", "Self", "super", "crate"):
+        raise ValueError("include/vgpu.h: the identifier %r cannot be written in Rust: rename it" % name)
+    return "r#" + name if name in RUST_KEYWORDS else name
+
+
 def split_decl(decl):
     """'const uint32_t perm_challenges[15]' -> (type tokens, name, array length or None)"""
     decl = decl.strip()
@@ -160,14 +171,14 @@ def generate():
         out.append("#[repr(C)]\n#[derive(Clone, Copy)]\npub struct %s {  // %s" % (names[s], s))
         for ty, name, arr in fields:
             if isinstance(ty, tuple):  # nullable C function pointer: same size and alignment as a pointer
-                ps = ", ".join("%s: %s" % (an, rust_type(aty, names)) for aty, an, _ in ty[2])
+                ps = ", ".join("%s: %s" % (rust_ident(an), rust_type(aty, names)) for aty, an, _ in ty[2])
                 rt = 'Option<unsafe extern "C" fn(%s)%s>' % (ps, "" if ty[1] == "void" else " -> " + rust_type(ty[1], names))
-                out.append("    pub %s: %s," % (name, rt))
+                out.append("    pub %s: %s," % (rust_ident(name), rt))
                 continue
             rt = rust_type(ty, names)
             if arr is not None:
                 rt = "[%s; %s]" % (rt, arr)
-            out.append("    pub %s: %s," % (name, rt))
+            out.append("    pub %s: %s," % (rust_ident(name), rt))
         out.append("}")
     out.append("")
     out.append('#[link(name = "vgpu")]\nextern "C" {')
@@ -176,7 +187,7 @@ def generate():
         for ty, an, arr in args:
             if arr is not None:  # array parameters decay to pointers
                 ty = ty + "*"
-            ps.append("%s: %s" % (an, rust_type(ty, names)))
+            ps.append("%s: %s" % (rust_ident(an), rust_type(ty, names)))
         r = "" if ret == "void" else " -> " + rust_type(ret, names)
         out.append("    pub fn %s(%s)%s;" % (name, ", ".join(ps), r))
     out.append("}")

@@ -362,6 +362,30 @@ def poseidon16_permute(rc, state):
     return s
 
 
+# vgpu_field_probe: op name -> (op code, operand words per item, result words per item), in the order of vk::FieldProbeOp (kernels/launch.hpp).
+# The butterfly ops take 16 points, low, lowbits; monty_reduce / monty_reduce_wide / monty_signed take the 64-bit operand as (low word, high word).
+FIELD_PROBE_OPS = {name: (code, iw, ow) for code, (name, iw, ow) in enumerate([
+    ("reduce_once", 1, 1), ("sub_mod", 2, 1), ("add", 2, 1), ("sub", 2, 1), ("neg", 1, 1), ("mul", 2, 1), ("monty_reduce", 2, 1), ("monty_reduce_wide", 2, 1),
+    ("from_canonical", 1, 1), ("canonical", 1, 1), ("inv", 1, 1), ("ext_mul", 10, 5), ("ext_square", 5, 5), ("ext_scale", 6, 5), ("ext_inv", 5, 5),
+    ("bfly_dit_lb0", 18, 16), ("bfly_dit", 18, 16), ("bfly_dif_lb0", 18, 16), ("bfly_dif", 18, 16), ("monty_signed", 2, 1), ("sbox", 1, 1), ("sbox_plus", 2, 1),
+    ("permute", 16, 16), ("permute_plain", 16, 16)])}
+
+
+def field_probe(prover, op, operands):
+    """Test hook (vgpu_field_probe): primitive `op` (a key of FIELD_PROBE_OPS) of the DEVICE's field arithmetic on operands[i] = one item's raw
+    stored words, one work item each -> (n_items, result words) raw stored words.  Nothing is converted on the way in or out."""
+    code, iw, ow = FIELD_PROBE_OPS[op]
+    a = np.ascontiguousarray(operands, dtype=np.uint32)
+    if a.ndim != 2 or a.shape[1] != iw or a.shape[0] == 0:
+        raise ValueError("field_probe(%s): operands must be a non-empty (n_items, %d) array" % (op, iw))
+    n = a.shape[0]
+    src = np.ascontiguousarray(a.T)
+    out = np.zeros((ow, n), dtype=np.uint32)
+    _check(lib().vgpu_field_probe(prover._h, ctypes.c_uint32(code), src.ctypes.data_as(c_u32p), ctypes.c_uint64(src.size), ctypes.c_uint64(n),
+                                  out.ctypes.data_as(c_u32p), ctypes.c_uint64(out.size)))
+    return np.ascontiguousarray(out.T)
+
+
 class _PinnedBlock:
     def __init__(self, nbytes):
         self.ptr = ctypes.c_void_p()

@@ -832,6 +832,25 @@ int32_t vgpu_fri_fold(vgpu_prover_t* p, const uint32_t* f, uint64_t n, const uin
     })
 }
 
+// test hook: one primitive of the device's field arithmetic on raw stored words (kernels/field_probe.hip)
+int32_t vgpu_field_probe(vgpu_prover_t* p, uint32_t op, const uint32_t* operands, uint64_t operand_words, uint64_t n_items, uint32_t* results, uint64_t result_words) {
+    VG_TRY({
+        int iw = 0, ow = 0;
+        if (!p || !operands || !results) throw std::invalid_argument("null argument");
+        if (!vk::field_probe_shape(op, &iw, &ow)) throw std::invalid_argument("field probe: unknown op");
+        if (n_items == 0 || n_items > (1ull << 24)) throw std::invalid_argument("field probe: 1 .. 2^24 items");
+        if (operand_words != n_items * (uint64_t)iw || result_words != n_items * (uint64_t)ow) throw std::invalid_argument("field probe: buffer sizes do not match the op's shape");
+        vk::field_probe_check_twiddle_range(op, operands, n_items);  // low / lowbits of the butterfly ops index the twiddle tables
+        DeviceCtx& c = p->p->ctx();
+        c.activate();
+        DBuf din(&c, (size_t)operand_words), dout(&c, (size_t)result_words);
+        c.upload(din.data, operands, operand_words * 4);
+        vk::launch_field_probe(c.stream, op, din.data, n_items, c.tables, c.poseidon_tab, c.poseidon_sparse, dout.data);
+        c.check_launch("field probe");
+        c.download(results, dout.data, result_words * 4);
+    })
+}
+
 // A trace handle handed to prove must exist and live on THIS prover's device.  Traces of another context of the same device (a host that
 // uploads / generates segment i+1 on a context of its own while this one proves segment i) are accepted: `foreign` collects their
 // contexts, which the caller drains (their queued work must have produced the traces) and keeps alive for the duration of the proof.

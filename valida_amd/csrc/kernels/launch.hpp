@@ -55,6 +55,19 @@ void launch_clock_probe(hipStream_t st, uint64_t* out3, uint32_t iters);  // out
 // n_cols columns of Wq = 2^log_wq blocks of `rows` rows (block r in the natural order of the sub-coset bitrev(r)) -> columns in global natural order
 void launch_interleave_blocks(hipStream_t st, const uint32_t* src, uint32_t* dst, uint64_t rows, uint32_t log_wq, uint64_t n_cols);
 void launch_export_rows(hipStream_t st, DMatView src, uint64_t row0, uint64_t nrows, uint32_t* dst_dev);
+// field_probe.hip (test hook): primitive `op` of field.hpp / butterfly.hpp / poseidon_perm.hpp on n operand tuples of raw stored words, word k of item i
+// at in[k * n + i] / out[k * n + i].  The butterfly ops read twiddles at tw[(1 << (lowbits + st)) - 1 + low + (k << lowbits)], st < 4, k < 8: the
+// CALLER keeps low < 2^lowbits and lowbits <= 10 (the compact tables cover stages 1..14), and low = lowbits = 0 in the LB0 forms — the launcher
+// sees device memory only and checks nothing; field_probe_check_twiddle_range does it on the HOST copy of the operands before they are uploaded
+// (vgpu_field_probe and the emulation harness both call it) and throws std::invalid_argument.
+enum FieldProbeOp {
+    FP_REDUCE_ONCE = 0, FP_SUB_MOD, FP_ADD, FP_SUB, FP_NEG, FP_MUL, FP_MONTY_REDUCE, FP_MONTY_REDUCE_WIDE, FP_FROM_CANONICAL, FP_CANONICAL, FP_INV,
+    FP_EXT_MUL, FP_EXT_SQUARE, FP_EXT_SCALE, FP_EXT_INV, FP_BFLY_DIT_LB0, FP_BFLY_DIT, FP_BFLY_DIF_LB0, FP_BFLY_DIF, FP_MONTY_SIGNED, FP_SBOX, FP_SBOX_PLUS,
+    FP_PERMUTE, FP_PERMUTE_PLAIN, FIELD_PROBE_OPS
+};
+bool field_probe_shape(uint32_t op, int* in_words, int* out_words);  // words per item; false: unknown op
+void field_probe_check_twiddle_range(uint32_t op, const uint32_t* in_host, uint64_t n);
+void launch_field_probe(hipStream_t st, uint32_t op, const uint32_t* in_dev, uint64_t n, const DeviceTables& tb, const uint32_t* pos_dev, bool sparse, uint32_t* out_dev);
 // ntt.hip
 void launch_intt(hipStream_t st, DMatView m, const DeviceTables& tb);
 void launch_coset_ntt(hipStream_t st, DMatView coeffs, DMatView dst, uint64_t dst_row0, Fp shift, const DeviceTables& tb);
