@@ -114,6 +114,55 @@ def byte_loop_program(iters):
             (ADD32, [-16, -16, -32]), (ADD32, [-4, -4, 1, 0, 1]), (BNE, [loop, -4, iters, 0, 1]), (STOP, [])]
 
 
+# ---- programs at the edges of the ALU chips and of the program chip's histogram (tests/test_tracegen_edges_*.py) -------------------------------
+SUB32, MUL32, DIV32, LT32, SHL32, SHR32, OR32, XOR32, SDIV32, NE32, MULHU32, SRA32, MULHS32, LTE32, EQ32, SLT32, SLE32 = 101, 102, 103, 104, 105, 106, 108, 109, 110, 111, 112, 113, 114, 115, 116, 117, 118
+ALU_EDGE_WORDS = [0, 1, 0xFF, 0x100, 0xFFFF, 0x10000, 0x00FFFFFF, 0x01000000, 0x7FFFFFFF, 0x80000000, 0x80000001, 0xFFFFFFFE, 0xFFFFFFFF, P - 1, P, P + 1,
+                  0x00FF00FF, 0xFF00FF00, 0x01010101, 0xFEFEFEFE]
+# (b, c): carries made by a carry-in, borrows with and without an incoming borrow, equal operands, a first difference in byte 0 and in byte 3,
+# differences in every byte, compares across the sign bit, the words around p
+ALU_EDGE_PAIRS = [(0xFFFF, 1), (0xFFFFFFFF, 1), (0x00FFFFFF, 1), (0x100, 0xFF), (0, 1), (0x10000, 1), (0x01000000, 1), (0x100, 1), (0, 0), (0xFFFFFFFF, 0xFFFFFFFF),
+                  (0x80000000, 0x80000000), (0x01000000, 0x00FFFFFF), (0x00FFFFFF, 0x01000000), (0xFFFFFFFE, 0xFFFFFFFF), (0xFFFFFFFF, 0xFFFFFFFE),
+                  (0x80000000, 0x80000001), (0x00FF00FF, 0xFF00FF00), (0xFF00FF00, 0x00FF00FF), (0x01010101, 0xFEFEFEFE), (0xFEFEFEFE, 0x01010101),
+                  (0x7FFFFFFF, 0x80000000), (0x80000000, 0x7FFFFFFF), (0xFFFFFFFF, 0), (0, 0xFFFFFFFF), (P - 1, P), (P, P + 1), (P + 1, P - 1), (P, P)]
+ALU_EDGE_SHIFTS = [(b, c) for b in (1, 0x80000001, 0xFFFFFFFF, 0x7FFFFFFF) for c in (0, 1, 7, 8, 15, 16, 24, 31)]
+
+
+def borrows_through_a_byte(b, c):
+    """Whether b - c borrows out of any of its four bytes (byte-wise b[i] < c[i] somewhere, or a borrow that reaches an equal byte)."""
+    borrow = 0
+    for k in range(4):
+        x, y = (b >> 8 * k) & 255, (c >> 8 * k) & 255
+        borrow = int(x - borrow < y)
+        if borrow:
+            return True
+    return False
+
+
+def alu_edges_program(borrow_free=False):
+    """Straight-line: the words of ALU_EDGE_WORDS (and the shift amounts) loaded with IMM32 into fp - 4 (k + 1), then every ALU opcode over
+    ALU_EDGE_PAIRS, the result into one scratch cell.  A division leaves out the pairs on which the reference's VM panics (a zero divisor, the
+    signed overflow); borrow_free leaves out the subtractions that borrow."""
+    slot = {w: -4 * (k + 1) for k, w in enumerate(ALU_EDGE_WORDS)}
+    amount = {c: -4 * (len(ALU_EDGE_WORDS) + 1 + k) for k, c in enumerate(sorted({c for _, c in ALU_EDGE_SHIFTS}))}
+    dst = -4 * (len(slot) + len(amount) + 1)
+    p = [imm32(a, w) for w, a in slot.items()] + [imm32(a, c) for c, a in amount.items()]
+    for b, c in ALU_EDGE_PAIRS:
+        for op in (ADD32, SUB32, LT32, LTE32, SLT32, SLE32, AND32, OR32, XOR32, MUL32, MULHS32, MULHU32, DIV32, SDIV32, NE32, EQ32):
+            if op in (DIV32, SDIV32) and (c == 0 or (op == SDIV32 and (b, c) == (0x80000000, 0xFFFFFFFF))):
+                continue
+            if op == SUB32 and borrow_free and borrows_through_a_byte(b, c):
+                continue
+            p.append((op, [dst, slot[b], slot[c], 0, 0]))
+    for b, c in ALU_EDGE_SHIFTS:
+        p += [(op, [dst, slot[b], amount[c], 0, 0]) for op in (SHL32, SHR32, SRA32)]
+    return p + [(STOP, [])]
+
+
+def long_rom_program(n=5000):
+    """n straight-line IMM32 and a STOP: the pcs run past the 4096 bins the program chip's histogram keeps in LDS, the last fetch among them."""
+    return [imm32(-4 * (1 + i % 16), i) for i in range(n)] + [(STOP, [])]
+
+
 def np_u32(desc_ptr, n, w):
     import ctypes
 
