@@ -902,6 +902,72 @@ const uint32_t* vgpu_transition_report_words(const vgpu_transition_report_t* r);
 void vgpu_transition_report_timing(const vgpu_transition_report_t* r, double out[3]);
 void vgpu_transition_report_free(vgpu_transition_report_t* r);
 
+/* ---- Product audit: the products of two columns the witness keeps affine.  The invariant audit finds affine-linear relations only; the
+ * constraints a chip consists of are mostly of degree two (b^2 = b, s t = 0, s t = s, s x = y, a b = c).  This audit lists, per chip, every
+ * product of two independent columns that is an affine function of the row on every row of the WITNESS, and on how many rows the chip's own
+ * constraints and records enforce it to first order.  Inputs: exactly what vgpu_prove and the audits take.
+ *   space        chip h, main matrix M (n x w): a_r = (1, M[r][0], .., M[r][w - 1]); R = the reduced row echelon form of the a_r (the invariant
+ *                audit's R, word for word), Pi its pivot columns (column 0 always), rho = |Pi|.  The q = rho - 1 pivot main columns are the
+ *                INDEPENDENT columns.  A non-pivot column is an affine function of earlier ones (the invariant audit reports that) and takes
+ *                no part.
+ *   pairs        all (i, j), i <= j, both independent columns, in lexicographic order: m = q (q + 1) / 2.
+ *   relation     pair (i, j) is a relation iff some beta in F_p^(w + 1), supported on Pi, has M[r][i] M[r][j] = beta . a_r on every row r.  The
+ *                columns of Pi are linearly independent over the rows, so beta is unique: no grid, order or seed changes a word.
+ *   kinds        0 BOOLEAN: i = j and beta = e_i.  1 ZERO: beta = 0.  2 SELECT: i != j and beta = e_i or beta = e_j (one column is 1 wherever
+ *                the other is non-zero).  3 OTHER.
+ *   verdict      the gradient of x_i x_j - beta . (1, x) at row r is g_r in F_p^w, g_r[k] = [k = i] M[r][j] + [k = j] M[r][i] - beta_(k + 1) (for
+ *                i = j the first two terms add up to 2 M[r][i]).  ENFORCED at r iff g_r lies in the row space of the rank audit's Jacobian J_r
+ *                (the same matrix, word for word; n = 1 by its rule).  FLAT iff g_r = 0: counted among the enforced rows and also on its own;
+ *                first order says nothing there (x y = 0 at x = y = 0).  FREE otherwise: some first-order-unnoticed move of the row's cells
+ *                breaks the relation.
+ * What it is not: single products only (s a - s b = 0 is not found unless s a and s b are each affine); one row; THIS witness (a short program
+ * has accidental relations); first order, with the rank audit's caveats; `check`'s exit status never depends on it.
+ * Options: max_entries, max_rows_per_entry, chip_mask, max_terms, reserved as vgpu_invariant_audit_opts_t, same defaults and refusals.
+ * vgpu_product_audit runs on the device (kernels/product_audit.hip), queued on the prover context.  (1) Pivots: the invariant audit's phase 1 and
+ * merge.  (2) Basis rows: the rho rows that are not in the span of the rows before them, one wave per slice of rows eliminating over the rho
+ * compacted columns and remembering the rows that raised the rank, then an ordered merge tree of fan 16 (the first-independent rows of L ++ R are
+ * those of first-independent(L) ++ first-independent(R)): the same rows whatever the grid.  (3) Solve: the rho x rho matrix of the basis rows over
+ * Pi inverted by Gauss-Jordan in one workgroup (in LDS when 8 rho^2 + 16 bytes fit, else in pool scratch), beta of every pair = inverse x
+ * products at the basis rows.  (4) Sweep: per row and live pair M[r][i] M[r][j] == beta . a_r[Pi], a tile of 64 rows as [rho][64] and the beta of 32
+ * pairs as [32][rho] in LDS, one thread per (row, pair), a mismatch stores 0 into the pair's flag; a first launch over the first 256 rows with all m
+ * pairs, the survivors compacted, a second launch over all rows with the survivors.  (5) Enforce: one wave per trace row, the rank audit's dual
+ * evaluation and LDS elimination once per row, then per relation g_r built from its sparse (column, coefficient) list (staged through LDS in
+ * groups) and the row's two cells, one reduce-only sweep and the flat bit; free rows are counted per workgroup and listed by count -> scan ->
+ * list, no atomic admits a row.  Scratch from the pool; VGPU_ERR_OOM with the arithmetic when the pool cannot give it.  VGPU_ERR_INVALID_ARG
+ * with the chip's name and the arithmetic wherever the invariant audit would refuse the chip, and for a chip whose enforcement phase (the rank
+ * audit's sum plus 4 x ((2 NW + 2) E + the entry group) bytes for E relations) does not fit 160 KB of LDS with one wave per workgroup.
+ * vgpu_product_audit_host: the same contract on the host, one thread, no limits.
+ * Report image (vgpu_product_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x31525156 "VQR1" [1] word count [2] max_terms [3] truncated [4,5] total_entries = the relations of the audited chips (exact even when
+ *   the list is cut) [6] reported [7] n_chips
+ *   per chip, in machine order, 16 words: [0] width [1] constraints [2] interactions [3] audited (0 / 1) [4,5] height (u64) [6] rho [7] m (pairs)
+ *   [8] relations [9] boolean [10] zero [11] select [12] other [13] relations enforced on every row [14] on some rows [15] on no row.  q is not
+ *   stored: q = rho - 1 (0 for rho = 0), and the block has no padding.  A chip that is not audited keeps its first six words, the rest 0.
+ *   per entry, ascending (chip, i, j), 16 + 2 T + L words: chip, i, j, kind, beta_0, support (main columns with a non-zero coefficient in beta;
+ *   exact), T = listed terms = min(support, max_terms), L = listed free rows = min(free_rows, max_rows_per_entry), enforced_rows (u64), free_rows
+ *   (u64), flat_rows (u64), 0, 0, then T (column, coefficient) terms ascending by column, then the first L free rows, ascending:
+ *   M[r][i] M[r][j] = beta_0 + sum(coefficient * M[r][column]). */
+typedef struct vgpu_product_audit_opts {
+    uint64_t max_entries;
+    uint32_t max_rows_per_entry;
+    uint32_t chip_mask;
+    uint32_t max_terms;
+    uint32_t reserved[3];
+} vgpu_product_audit_opts_t;
+typedef struct vgpu_product_report vgpu_product_report_t;
+int32_t vgpu_product_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                           uint32_t n_prep, const vgpu_product_audit_opts_t* opts, vgpu_product_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_product_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                                const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                                const vgpu_product_audit_opts_t* opts, vgpu_product_report_t** out);
+uint64_t vgpu_product_report_len(const vgpu_product_report_t* r);
+const uint32_t* vgpu_product_report_words(const vgpu_product_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: dual row evaluations of the
+ * enforcement phase */
+void vgpu_product_report_timing(const vgpu_product_report_t* r, double out[3]);
+void vgpu_product_report_free(vgpu_product_report_t* r);
+
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
  *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct

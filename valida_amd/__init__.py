@@ -1521,6 +1521,103 @@ def invariant_audit_host(machine, main_matrices, preprocessed, max_entries=1024,
     return _audit_host("invariant", machine, main_matrices, preprocessed, opts)
 
 
+class ProductAuditOpts(ctypes.Structure):  # vgpu_product_audit_opts_t
+    _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("max_terms", ctypes.c_uint32),
+                ("reserved", ctypes.c_uint32 * 3)]
+
+
+PRODUCT_KINDS = ("boolean", "zero", "select", "other")
+
+
+class ProductReport(_AuditReport):
+    """The product audit of a witness (vgpu_product_audit / vgpu_product_audit_host; the contract is stated in include/vgpu.h), as plain Python
+    values: max_terms, truncated, total_entries (the relations of the audited chips), reported,
+    chips = [dict(chip, width, constraints, interactions, audited, height, rank (rho), independent (q = rho - 1), pairs (m), relations, boolean,
+    zero, select, other (counts), every, some, never (relations enforced on every row, on some rows, on no row))],
+    entries = [dict(chip, i, j, kind ("boolean" / "zero" / "select" / "other"), b0, support, terms=[(column, coefficient)], enforced_rows,
+    free_rows, flat_rows, rows=[the first free rows])] ascending by (chip, i, j): M[r][i] * M[r][j] = b0 + sum(coefficient * M[r][column]) on
+    every row r of the witness,
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (dual row evaluations of the enforcement phase).
+    Single products, one row, THIS witness, first order: candidates for missing constraints, not findings."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 8 or w[0] != 0x31525156 or w[1] != len(w):
+            raise ValueError("not a product report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.max_terms = w[2]
+        self.truncated = bool(w[3])
+        self.total_entries, self.reported = w[4] | (w[5] << 32), w[6]
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 8
+        self.chips = []
+        for c in range(w[7]):
+            self.chips.append(dict(chip=c, width=w[pos], constraints=w[pos + 1], interactions=w[pos + 2], audited=bool(w[pos + 3]), height=u64(pos + 4), rank=w[pos + 6],
+                                   independent=max(w[pos + 6], 1) - 1, pairs=w[pos + 7], relations=w[pos + 8], boolean=w[pos + 9], zero=w[pos + 10], select=w[pos + 11],
+                                   other=w[pos + 12], every=w[pos + 13], some=w[pos + 14], never=w[pos + 15]))
+            pos += 16
+        self.entries = []
+        for _ in range(self.reported):
+            T, L = w[pos + 6], w[pos + 7]
+            at = pos + 16
+            self.entries.append(dict(chip=w[pos], i=w[pos + 1], j=w[pos + 2], kind=PRODUCT_KINDS[w[pos + 3]], b0=w[pos + 4], support=w[pos + 5],
+                                     terms=[(w[at + 2 * k], w[at + 2 * k + 1]) for k in range(T)], enforced_rows=u64(pos + 8), free_rows=u64(pos + 10),
+                                     flat_rows=u64(pos + 12), rows=w[at + 2 * T:at + 2 * T + L]))
+            pos = at + 2 * T + L
+        assert pos == len(w)
+
+    def _pairs(self, chip, keep):
+        return [(e["i"], e["j"]) for e in self.entries if e["chip"] == chip and keep(e)]
+
+    def relations(self, chip):
+        """The listed pairs (i, j) of `chip` whose product is an affine function of the row."""
+        return self._pairs(chip, lambda e: True)
+
+    def never_enforced(self, chip):
+        """The listed pairs of `chip` whose relation no row's constraints and records enforce: candidates for a missing constraint."""
+        return self._pairs(chip, lambda e: e["enforced_rows"] == 0)
+
+    def holds(self, main_matrices):
+        """The (chip, i, j) of the listed entries whose relation FAILS on some row of the given canonical traces (one matrix per chip; plain
+        numpy, no library call): [] on the audited witness, and a way to test one witness's relations against another program's traces.
+        Raises for an entry whose beta was cut at max_terms."""
+        bad = []
+        for e in self.entries:
+            if e["support"] > len(e["terms"]):
+                raise VgpuError(-1, "product_audit: the beta of chip %d pair (%d, %d) is cut (%d terms, %d listed): it cannot be evaluated" %
+                                (e["chip"], e["i"], e["j"], e["support"], len(e["terms"])))
+            m = np.asarray(main_matrices[e["chip"]], dtype=np.uint64) % np.uint64(P)
+            acc = np.full(m.shape[0], e["b0"], dtype=np.uint64)
+            for col, coef in e["terms"]:
+                acc = (acc + m[:, col] * np.uint64(coef)) % np.uint64(P)
+            if (acc != m[:, e["i"]] * m[:, e["j"]] % np.uint64(P)).any():
+                bad.append((e["chip"], e["i"], e["j"]))
+        return bad
+
+    def to_dict(self):
+        return dict(max_terms=self.max_terms, truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms,
+                    host_ms=self.host_ms, evaluations=self.evaluations, chips=self.chips, entries=self.entries)
+
+
+def _product_opts(max_entries, max_rows_per_entry, max_terms, chips):
+    # as _rank_opts: explicit zeros are refused here, with the library's status code
+    if int(max_entries) < 1 or int(max_rows_per_entry) < 1 or int(max_terms) < 1:
+        raise VgpuError(-1, "product_audit: max_entries, max_rows_per_entry and max_terms must be at least 1")
+    return ProductAuditOpts(int(max_entries), int(max_rows_per_entry), _chip_mask("product", chips), int(max_terms), (ctypes.c_uint32 * 3)(0, 0, 0))
+
+
+def product_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, chips=None):
+    """The product audit on the HOST (vgpu_product_audit_host: no device, one thread): main_matrices = one canonical matrix per chip,
+    preprocessed = [(chip index, matrix)], max_terms = the (column, coefficient) terms listed per relation, chips = the chip indices to audit
+    (default: all); a ProductReport back."""
+    opts = _product_opts(max_entries, max_rows_per_entry, max_terms, chips)
+    return _audit_host("product", machine, main_matrices, preprocessed, opts)
+
+
 class TransitionAuditOpts(ctypes.Structure):  # vgpu_transition_audit_opts_t
     _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("max_terms", ctypes.c_uint32),
                 ("min_gate_windows", ctypes.c_uint32), ("max_gates", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
@@ -1943,7 +2040,7 @@ def coverage_audit_host(machine, main_matrices, preprocessed, deltas=None, max_c
     return _audit_host("coverage", machine, main_matrices, preprocessed, opts)
 
 
-_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, field=FieldReport,
+_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, product=ProductReport, field=FieldReport,
                       link=LinkReport, coverage=CoverageReport)
 
 
@@ -2171,6 +2268,13 @@ class Prover:
         listed per invariant, chips = the chip indices to audit (default: all); an InvariantReport back."""
         opts = _invariant_opts(max_entries, max_rows_per_entry, max_terms, chips)
         return self._audit("invariant", main, preprocessed, opts)
+
+    def product_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, chips=None):
+        """Which products of two independent columns this witness keeps an affine function of the row, and on which rows the chip's constraints
+        and records enforce each relation to first order (vgpu_product_audit); the arguments of prove, max_terms = the (column, coefficient)
+        terms listed per relation, chips = the chip indices to audit (default: all); a ProductReport back."""
+        opts = _product_opts(max_entries, max_rows_per_entry, max_terms, chips)
+        return self._audit("product", main, preprocessed, opts)
 
     def transition_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, min_gate_windows=64, max_gates=256, chips=None):
         """Which affine-linear relations between a row and its successor this witness keeps, on every window or under a boolean gate, and at

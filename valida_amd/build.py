@@ -34,6 +34,7 @@ SOURCES = [
     "kernels/step_audit.hip",
     "kernels/invariant_audit.hip",
     "kernels/transition_audit.hip",
+    "kernels/product_audit.hip",
     "kernels/field_probe.hip",
     "host/prover.cpp",
     "host/prover_audits.cpp",

@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--products] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -97,6 +97,15 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         audited gates (13 gates in all), 5 never held`.  Never held is a candidate missing transition constraint.  Affine-linear, single gates
         (no conjunction of two), THIS witness, per basis vector, first order and one row at a time (held is exact only for chips whose
         constraints do not read the next row): the exit status does not depend on this flag.
+        --products adds the product audit of the same witness (vgpu_product_audit: per chip every product of two independent columns — the
+        pivot main columns of the invariant audit's reduced row echelon form — that is an affine function of the row on every row of the
+        witness, and per relation the rows on which the chip's own constraints and bus records enforce it to first order, judged against the
+        rank audit's Jacobian), on the same path (device or --host), restricted by the same --chips.  The JSON report gets one more key,
+        "products" (ProductReport.to_json's object); stdout gets one line per chip that has a relation, `add: 29 product relations of 45
+        pairs (5 boolean, 7 zero, 9 select, 8 other); enforced on every row 17, on some rows 12, never 0`.  Never enforced is a candidate
+        missing constraint (a forgotten b^2 = b, s t = 0, s x = y) or a column this program never exercises.  Single products only (s a - s b
+        = 0 is found only when s a and s b are each affine), within one row, on THIS witness (a short program has accidental relations), first
+        order with the rank audit's caveats: the exit status does not depend on this flag.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -350,6 +359,21 @@ def invariant_lines(report):
     return lines
 
 
+def product_lines(report):
+    """One line per chip of a product report that has a relation: how many of how many pairs, by kind and by verdict."""
+    import valida_amd as va
+
+    lines = []
+    for c in report.chips:
+        if not c["relations"]:
+            continue
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        lines.append("%s: %d product relation%s of %d pair%s (%d boolean, %d zero, %d select, %d other); enforced on every row %d, on some rows %d, never %d" % (
+            name, c["relations"], "" if c["relations"] == 1 else "s", c["pairs"], "" if c["pairs"] == 1 else "s", c["boolean"], c["zero"], c["select"], c["other"],
+            c["every"], c["some"], c["never"]))
+    return lines
+
+
 def field_lines(report):
     """One line per (chip, interaction) of a field report with a floating field: the bus, the fields, the most rows one of them floats on."""
     import valida_amd as va
@@ -458,10 +482,13 @@ def main(argv=None):
     ap.add_argument("--transitions", action="store_true", help="check: also the transition audit (the affine-linear relations between a row and its successor that this "
                     "witness keeps on every window or under a boolean gate, and the windows at which the chip's constraints hold each: never held = a candidate missing "
                     "transition constraint; affine-linear only, single gates, this witness, per basis vector, first order, one row at a time; never changes the exit status)")
+    ap.add_argument("--products", action="store_true", help="check: also the product audit (the products of two independent columns that are an affine function of the row "
+                    "on every row of this witness — b^2 = b, s t = 0, s t = s, s x = y, a b = c — and on how many rows the chip's own constraints and bus records enforce each: "
+                    "never enforced = a candidate missing constraint; single products, one row, this witness, first order; never changes the exit status)")
     ap.add_argument("--min-gate-windows", type=int, default=64, help="check --transitions: a gate that holds on fewer windows is counted but not audited (default 64)")
     ap.add_argument("--max-gates", type=int, default=256, help="check --transitions: the gates listed per chip, the ungated one included (default 256)")
     ap.add_argument("--step-sizes", default="1,-1,2", help="check --steps: 1 to 4 distinct step sizes, comma-separated integers mod p (as --step-sizes=1,-1,2)")
-    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields / --steps / --invariants / --transitions: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
+    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields / --steps / --invariants / --transitions / --products: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -499,6 +526,7 @@ def main(argv=None):
                 ireport = va.invariant_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.invariants else None
                 treport = va.transition_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_terms=256, min_gate_windows=args.min_gate_windows, max_gates=args.max_gates,
                                                    chips=parse_chips(args.chips)) if args.transitions else None
+                qreport = va.product_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.products else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -515,6 +543,7 @@ def main(argv=None):
                 sreport = prover.step_audit(main, prep, steps=parse_deltas(args.step_sizes), max_entries=1 << 20, chips=parse_chips(args.chips)) if args.steps else None
                 ireport = prover.invariant_audit(main, prep, max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.invariants else None
                 treport = prover.transition_audit(main, prep, max_terms=256, min_gate_windows=args.min_gate_windows, max_gates=args.max_gates, chips=parse_chips(args.chips)) if args.transitions else None
+                qreport = prover.product_audit(main, prep, max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.products else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -536,13 +565,16 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), invariants=ireport.to_dict()))
             if treport is not None:
                 text = json.dumps(dict(json.loads(text), transitions=treport.to_dict()))
+            if qreport is not None:
+                text = json.dumps(dict(json.loads(text), products=qreport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
                     coverage_lines(kreport) if kreport is not None else []) + (pair_lines(preport) if preport is not None else []) + (
                     rank_lines(rreport) if rreport is not None else []) + (field_lines(freport) if freport is not None else []) + (
                     link_lines(lreport) if lreport is not None else []) + (step_lines(sreport) if sreport is not None else []) + (
-                    invariant_lines(ireport) if ireport is not None else []) + (transition_lines(treport) if treport is not None else []):
+                    invariant_lines(ireport) if ireport is not None else []) + (transition_lines(treport) if treport is not None else []) + (
+                    product_lines(qreport) if qreport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

@@ -18,6 +18,7 @@
 #include "step_audit.hpp"
 #include "invariant_audit.hpp"
 #include "transition_audit.hpp"
+#include "product_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -169,6 +170,10 @@ class Prover {
     // windows, gates over the grid's y), and per listed relation the windows at which the rank audit's Jacobian of either row lets it break;
     // queued on the context like the other audits, scratch from the pool.
     TransitionReport transition_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const TransitionAuditOpts& opts);
+    // Product audit of a witness (host/product_audit.hpp, kernels/product_audit.hip): the products of two independent columns that are an affine
+    // function of the row on every row (the invariant audit's pivots, the first-independent rows, an inverse, a pruned sweep over rows x pairs) and,
+    // per relation, the rows on which the rank audit's Jacobian enforces it; queued on the context like the other audits, scratch from the pool.
+    ProductReport product_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const ProductAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

@@ -834,6 +834,213 @@ InvariantReport Prover::invariant_audit(const std::vector<const DeviceTrace*>& m
     return rep;
 }
 
+// ---- product audit (host/product_audit.hpp; kernels/product_audit.hip) -----------------------------------------------------------------------
+ProductReport Prover::product_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const ProductAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const ProductAuditOpts o = product_audit_checked_opts(opts_in, machine_.airs.size());
+    const auto tr = audit_traces<ConstraintShape>("product_audit", main, preprocessed);
+    std::vector<int> prep_slot;
+    product_audit_plan(machine_, tr.ms, tr.prep_chips, tr.ps, prep_slot);
+    const size_t NC = machine_.airs.size();
+    const uint32_t R = o.max_rows_per_entry;
+    // per chip its launch shapes: a chip the invariant audit would refuse is refused here, before anything is queued
+    std::vector<vk::IaArgs> iargs(NC);
+    std::vector<vk::PqArgs> args(NC);
+    ProductReport rep;
+    rep.chips.resize(NC);
+    for (size_t i = 0; i < NC; i++) {
+        const AirDesc& air = machine_.airs[i];
+        iargs[i] = vk::IaArgs{};
+        args[i] = vk::PqArgs{};
+        ProductChipStat& cs = rep.chips[i];
+        product_audit_chip_block(cs, air, main[i]->height, product_audit_selected(o, i));
+        if (!cs.audited || !air.width) continue;
+        audit_chip_sizes(iargs[i].r, air, main[i]->height, fri_.interpret_air);
+        try {
+            audit_chip_shape(air, [&] { vk::ia_basis_shape(iargs[i]); iargs[i].d = air.width; vk::ia_shape(iargs[i]); });
+        } catch (const std::invalid_argument& e) {
+            throw std::invalid_argument(pq_renamed(e));
+        }
+    }
+
+    DeviceCtx& c = *ctx_;
+    AuditPass pass(c, main.size() + preprocessed.size());
+    const hipStream_t st = pass.stream;
+
+    uint64_t basis_words = 0, space_words = 0, scratch_words = 0, rows_words = 0, desc_words_n = 0;
+    audit_or_no_memory(st, [&] {
+        std::vector<uint64_t> wr_at(NC, 0), part_at(NC, 0), inv_at(NC, 0);
+        std::vector<size_t> e_at(NC + 1, 0);  // chip i's entries are [e_at[i], e_at[i + 1]) until the list is cut
+        std::vector<ProductVec> vecs;          // one per entry
+        std::vector<std::vector<uint32_t>> pivots(NC);  // per chip the augmented pivot columns, ascending
+        std::vector<uint32_t> desc_words;
+        for (size_t i = 0; i < NC; i++) {
+            vk::RaArgs& a = iargs[i].r;
+            if (!a.width) continue;
+            pass.bind(a, main[i], audit_prep(preprocessed, prep_slot, i), prog_dev_[i]);
+            a.iw = iw_dev_[i].data;
+            const std::vector<uint32_t> wr = ra_weight_rows(machine_.airs[i]);
+            wr_at[i] = desc_words.size();
+            desc_words.insert(desc_words.end(), wr.begin(), wr.end());
+            part_at[i] = basis_words; basis_words += vk::ia_part_words(iargs[i]);
+            inv_at[i] = basis_words; basis_words += vk::ia_inv_words(iargs[i]);
+        }
+        if (desc_words.empty()) desc_words.push_back(0);
+        desc_words_n = desc_words.size();
+        DBuf desc(&c, desc_words);
+        for (size_t i = 0; i < NC; i++) iargs[i].r.wr = desc.data + wr_at[i];
+        c.check_launch("product_audit ingest");
+        // the device pass: everything from here to the last download is between the two events
+        pass.begin();
+        {
+            // (1) every chip's pivot columns: the invariant audit's phase 1 and merge; their scratch goes back to the pool before the rest is taken
+            DBuf basis(&c, (size_t)(basis_words ? basis_words : 1));
+            for (size_t i = 0; i < NC; i++) {
+                if (!iargs[i].r.width) continue;
+                vk::launch_ia_basis(st, iargs[i], basis.data + part_at[i]);
+                vk::launch_ia_merge(st, iargs[i], basis.data + part_at[i], basis.data + inv_at[i]);
+            }
+            c.check_launch("product_audit pivots");
+            std::vector<uint32_t> iv;
+            for (size_t i = 0; i < NC; i++) {
+                if (!iargs[i].r.width) continue;
+                const uint32_t AW = iargs[i].r.width + 1;
+                iv.resize(2 + AW);
+                c.download_small(iv.data(), basis.data + inv_at[i], iv.size() * 4);
+                std::vector<uint32_t> pcols;
+                for (uint32_t k = 0; k < AW; k++) if (iv[2 + k]) pcols.push_back(k);
+                if (iv[0] != pcols.size() || pcols.empty() || pcols[0] != 0) throw std::logic_error("product_audit: the merged basis is inconsistent");
+                product_audit_space(rep.chips[i], pcols);
+                args[i].r = iargs[i].r;
+                args[i].rho = (uint32_t)pcols.size();
+                pivots[i] = std::move(pcols);
+            }
+        }
+        // (2) - (4) per chip: the basis rows, the inverse, beta of every pair, the two sweeps; its relations come back as (pair, beta)
+        std::vector<DBuf> keep;  // what the enforcement phase reads: the chips' lists
+        for (size_t i = 0; i < NC; i++) {
+            e_at[i] = rep.entries.size();
+            vk::PqArgs& pa = args[i];
+            if (pa.rho < 2) continue;
+            const uint32_t rho = pa.rho, m = (uint32_t)vk::pq_pairs(rho);
+            const std::vector<uint32_t>& pcols = pivots[i];
+            DBuf pc(&c, pcols);
+            pa.pcols = pc.data;
+            vk::pq_rows_shape(pa);
+            const uint64_t rows_w = vk::pq_rows_words(pa), aug_w = vk::pq_solve_in_lds(rho) ? 0 : 2ull * rho * rho;
+            // rows [rho + 1], status [1], count [1], G, inv, the slices' slots, aug, beta [m][rho], flags [m], two pair lists [m]
+            const uint64_t at_rows = 0, at_status = at_rows + rho + 1, at_count = at_status + 1, at_G = at_count + 1, at_inv = at_G + (uint64_t)rho * rho, at_part = at_inv + (uint64_t)rho * rho,
+                           at_aug = at_part + rows_w, at_beta = at_aug + aug_w, at_flags = at_beta + (uint64_t)m * rho, at_l1 = at_flags + m, at_l2 = at_l1 + m, words = at_l2 + m;
+            space_words = std::max(space_words, words);
+            DBuf sp(&c, (size_t)words);
+            uint32_t* d = sp.data;
+            VG_HIP_CHECK(hipMemsetAsync(d + at_rows, 0, (size_t)(rho + 3) * 4, st));  // rows, status, count: row 0 is a row of the trace
+            vk::launch_pq_rows(st, pa, d + at_part);
+            vk::launch_pq_rowmerge(st, pa, d + at_part, d + at_rows);
+            vk::launch_pq_solve(st, pa, d + at_rows, aug_w ? d + at_aug : nullptr, d + at_G, d + at_inv, d + at_status);
+            vk::launch_pq_beta(st, pa, d + at_G, d + at_inv, d + at_beta, d + at_flags);
+            const uint64_t prefix_rows = std::min<uint64_t>(pa.r.n, vk::PQ_PREFIX_ROWS);
+            vk::launch_pq_sweep(st, pa, "k_pq_sweep.prefix", prefix_rows, d + at_beta, nullptr, m, d + at_flags);
+            vk::launch_pq_compact(st, d + at_flags, nullptr, m, d + at_l1, d + at_count);
+            c.check_launch("product_audit prefix sweep");
+            uint32_t head[3];  // rows[0], status, count
+            c.download_small(head, d + at_rows, 4);
+            c.download_small(head + 1, d + at_status, 8);
+            if (head[0] != rho || head[1] != 0) throw std::logic_error("product_audit: the basis rows of chip " + machine_.airs[i].name + " are not independent");
+            uint32_t n_rel = head[2];
+            if (n_rel > m) throw std::logic_error("product_audit: more survivors than pairs");
+            const uint32_t* rel_dev = d + at_l1;
+            if (n_rel && prefix_rows < pa.r.n) {
+                vk::launch_pq_sweep(st, pa, "k_pq_sweep.survivors", pa.r.n, d + at_beta, d + at_l1, n_rel, d + at_flags);
+                vk::launch_pq_compact(st, d + at_flags, d + at_l1, n_rel, d + at_l2, d + at_count);
+                c.check_launch("product_audit survivor sweep");
+                const uint32_t before = n_rel;
+                c.download_small(&n_rel, d + at_count, 4);
+                if (n_rel > before) throw std::logic_error("product_audit: more relations than survivors");
+                rel_dev = d + at_l2;
+            }
+            if (!n_rel) continue;
+            std::vector<uint32_t> rel(n_rel), betas((size_t)n_rel * rho);
+            DBuf gb(&c, betas.size());
+            vk::launch_pq_gather(st, pa, d + at_beta, rel_dev, n_rel, gb.data);
+            c.check_launch("product_audit gather");
+            c.download_small(rel.data(), rel_dev, rel.size() * 4);
+            c.download_small(betas.data(), gb.data, betas.size() * 4);
+            product_audit_chip_entries(rep.chips[i], (uint32_t)i, pcols, rel, betas, o.max_terms, rep.entries, vecs);
+            // (5) the chip's relations as the enforcement kernel takes them, and its launch shape with them
+            const ProductLists l = product_audit_lists(vecs.data() + e_at[i], n_rel, vk::PQ_GROUP_ENTRIES, vk::PQ_GROUP_WORDS);
+            pa.E = n_rel; pa.G = (uint32_t)l.gstart.size() - 1; pa.GE = l.GE; pa.GW = l.GW;
+            keep.emplace_back(&c, l.eoff); pa.eoff = keep.back().data;
+            keep.emplace_back(&c, l.ewords); pa.ewords = keep.back().data;
+            keep.emplace_back(&c, l.gstart); pa.gstart = keep.back().data;
+            audit_chip_shape(machine_.airs[i], [&] { vk::pq_shape(pa); });
+            pa.r.evaluations = pa.r.K ? (double)pa.r.n * pa.r.width * (pa.r.n == 1 ? 1 : 2) : 0;
+            rep.evaluations += pa.r.evaluations;
+        }
+        e_at[NC] = rep.entries.size();
+        // per relation the rows that do not enforce it
+        AuditScratch sc(NC);
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].E) sc.add(i, vk::pq_totals_words(args[i]), (uint64_t)args[i].E * args[i].r.NB);
+        scratch_words = sc.place_prefixes();
+        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
+        if (sc.zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)sc.zeroed * 4, st));
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].E) vk::launch_pq_count(st, args[i], reinterpret_cast<unsigned long long*>(scratch.data + sc.tot_at[i]), scratch.data + sc.tab_at[i]);
+        c.check_launch("product_audit count");
+        {
+            std::vector<uint32_t> tw;
+            for (size_t i = 0; i < NC; i++) {
+                if (!args[i].E) continue;
+                tw.resize(vk::pq_totals_words(args[i]));
+                c.download_small(tw.data(), scratch.data + sc.tot_at[i], tw.size() * 4);
+                for (uint32_t k = 0; k < args[i].E; k++) {
+                    ProductEntry& en = rep.entries[e_at[i] + k];
+                    en.free_rows = audit_u64(tw, 2 * k);
+                    en.flat_rows = audit_u64(tw, 2 * k + 1);
+                    en.enforced = rep.chips[i].height - en.free_rows;
+                }
+            }
+        }
+        product_audit_finish(rep, o);
+        // the listed relations of a chip are its first ones: entry e of the list is relation e - e_at[chip]
+        audit_chip_runs(rep.entries, [&](uint32_t chip, size_t e0, size_t e1) {
+            rows_words = std::max<uint64_t>(rows_words, (uint64_t)(e1 - e0) * R);
+            (void)chip;
+        });
+        DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
+        audit_chip_runs(rep.entries, [&](uint32_t chip, size_t e0, size_t e1) {
+            bool any = false;
+            for (size_t e = e0; e < e1; e++) any |= rep.entries[e].free_rows != 0;
+            if (!any) return;
+            // the listed relations of one chip: scan, list, one download
+            const vk::PqArgs& pa = args[chip];
+            const uint32_t i_cut = (uint32_t)(e1 - e0);
+            const size_t words = (size_t)i_cut * R;
+            VG_HIP_CHECK(hipMemsetAsync(out.data, 0, words * 4, st));
+            vk::launch_ra_scan(st, pa.r, scratch.data + sc.tab_at[chip], scratch.data + sc.pre_at[chip], i_cut);
+            vk::launch_pq_list(st, pa, scratch.data + sc.tab_at[chip], scratch.data + sc.pre_at[chip], i_cut, R, out.data);
+            c.check_launch("product_audit list");
+            std::vector<uint32_t> w(words);
+            c.download_small(w.data(), out.data, w.size() * 4);
+            for (size_t e = e0; e < e1; e++) {
+                ProductEntry& en = rep.entries[e];
+                const uint64_t listed = std::min<uint64_t>(en.free_rows, R);
+                en.rows.assign(w.begin() + (e - e0) * R, w.begin() + (e - e0) * R + (size_t)listed);
+            }
+        });
+        pass.end(rep);
+    }, [&] {
+        return std::string("product_audit: the device pool cannot give the pass its scratch: for the pivots the invariant audit's (w + 1) (w + 2) words per workgroup of its phase 1 (at most 2048, 64 MB), a sixteenth of that for the merge tree and (w + 1)^2 + 2 of merged basis (" +
+                           std::to_string(basis_words * 4) + " bytes for this witness, given back before the rest is taken); per chip, one chip at a time, rho + 1 words per slice of rows (at most 2048) and a sixteenth of that, 2 rho^2 for the basis rows and their inverse (4 rho^2 when rho > 142), m rho of beta and 3 m of flags and pair lists for m = rho (rho - 1) / 2 pairs (" +
+                           std::to_string(space_words * 4) + " bytes for the widest chip so far); 16 bytes per relation of totals and 8 per (relation, workgroup of rows) (" + std::to_string(scratch_words * 4) +
+                           " bytes), the relations' sparse lists, " + std::to_string(desc_words_n * 4) + " bytes of interaction weight rows, " + std::to_string(rows_words * 4) +
+                           " bytes of listed rows, plus the working-layout copies of uploaded traces; chip_mask audits fewer chips at a time");
+    });
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 // ---- transition audit (host/transition_audit.hpp; kernels/transition_audit.hip) --------------------------------------------------------------
 TransitionReport Prover::transition_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const TransitionAuditOpts& opts_in) {
     const auto t_host = Clock::now();

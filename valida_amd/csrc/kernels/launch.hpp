@@ -354,6 +354,44 @@ void launch_ta_enforce(hipStream_t st, const TaArgs& a, uint32_t* bits);
 void launch_ta_count(hipStream_t st, const TaArgs& a, const uint32_t* bits, unsigned long long* totals, uint32_t* table);
 void launch_ta_scan(hipStream_t st, const TaArgs& a, const uint32_t* table, uint32_t* prefix);
 void launch_ta_list(hipStream_t st, const TaArgs& a, const uint32_t* bits, const uint32_t* table, const uint32_t* prefix, uint32_t R, uint32_t* rows);
+// product_audit.hip — the passes of the product audit (host/product_audit.hpp: contract; Prover::product_audit drives them), per chip.  The
+// pivots are the invariant audit's (launch_ia_basis, launch_ia_merge: inv [2 + c]); pcols [rho]: the augmented pivot columns ascending (pcols[0] =
+// 0, the constant; pcols[t] - 1 is a main column), q = rho - 1 independent columns, m = q (q + 1) / 2 pairs p <-> (ti, tj), 1 <= ti <= tj <= q,
+// lexicographic.  Basis rows: NB2 workgroups of one wave eliminate RS consecutive rows each over the rho compacted columns and write the rows that
+// raised the rank to a slot of rho + 1 words ([0] how many, then the rows ascending); the merge (a tree of fan IA_MERGE_FAN, one wave per node)
+// inserts the slots' rows in order and keeps the ones that raise the rank: slot 0 of its result holds the rho first-independent rows.  Solve: G
+// [rho][rho] the basis rows over Pi, inv [rho][rho] its inverse (aug: 2 rho^2 words of pool scratch, or null when pq_solve_in_lds(rho)), status
+// [0] != 0: singular.  beta [m][rho], flags [m] (set to 1 by launch_pq_beta).  Sweep: pair list [n_list] (null: the pairs 0 .. n_list - 1), rows
+// [0, n_rows): a mismatch stores 0 into flags[pair].  Compact: the listed pairs (null: 0 .. n_in - 1) whose flag is set, in order, and their count.
+// Enforce: the rank audit's launch shape and inputs plus the E relations as sparse lists: eoff [E + 1] word offsets into ewords, entry e = main
+// columns i, j, then (column, -beta as a Montgomery word) pairs; gstart [G + 1] the first entry of each group (a group is staged in LDS at a time:
+// at most GE entries and GW words); totals: u64 [2 e] free rows, [2 e + 1] flat rows of relation e (zeroed); table / prefix: [E][NB] u32 free rows
+// per workgroup and their exclusive prefix (table zeroed; the scan is launch_ra_scan); rows: [i_cut][R] u32.
+struct PqArgs {
+    RaArgs r;               // evaluations: the rank audit's dual row evaluations at most
+    uint32_t rho;           // |Pi|
+    const uint32_t* pcols;
+    uint32_t RS, NB2;       // pq_rows_shape: rows per slice of the basis-row phase, slices
+    uint32_t E, G, GE, GW;  // relations; groups, the most entries and the most words of a group
+    const uint32_t *eoff, *ewords, *gstart;
+};
+constexpr uint32_t PQ_TILE_ROWS = 64, PQ_TILE_PAIRS = 32, PQ_PREFIX_ROWS = 256, PQ_GROUP_ENTRIES = 512, PQ_GROUP_WORDS = 8192;
+inline uint64_t pq_pairs(uint32_t rho) { return rho ? (uint64_t)(rho - 1) * rho / 2 : 0; }
+inline uint64_t pq_rows_words(const PqArgs& a) { return ((uint64_t)a.NB2 + (a.NB2 + IA_MERGE_FAN - 1) / IA_MERGE_FAN) * (a.rho + 1ull); }
+inline bool pq_solve_in_lds(uint32_t rho) { return 4ull * (16ull + rho + 2ull * rho * rho) <= 160ull * 1024; }
+inline uint64_t pq_totals_words(const PqArgs& a) { return 4ull * a.E; }  // u32 words of the u64 totals
+void pq_rows_shape(PqArgs& a);  // RS and NB2 from the height and rho
+void launch_pq_rows(hipStream_t st, const PqArgs& a, uint32_t* part);
+void launch_pq_rowmerge(hipStream_t st, const PqArgs& a, uint32_t* part, uint32_t* rows);  // part is overwritten by the levels of the tree; rows [rho + 1]
+void launch_pq_solve(hipStream_t st, const PqArgs& a, const uint32_t* rows, uint32_t* aug, uint32_t* G, uint32_t* inv, uint32_t* status);
+void launch_pq_beta(hipStream_t st, const PqArgs& a, const uint32_t* G, const uint32_t* inv, uint32_t* beta, uint32_t* flags);
+void launch_pq_sweep(hipStream_t st, const PqArgs& a, const char* name, uint64_t n_rows, const uint32_t* beta, const uint32_t* list, uint32_t n_list, uint32_t* flags);
+void launch_pq_compact(hipStream_t st, const uint32_t* flags, const uint32_t* list, uint32_t n_in, uint32_t* out, uint32_t* count);
+void launch_pq_gather(hipStream_t st, const PqArgs& a, const uint32_t* beta, const uint32_t* list, uint32_t n_list, uint32_t* out);
+void pq_shape(PqArgs& a);  // ra_shape for this audit's LDS with a.E relations in groups of a.GE entries and a.GW words; throws std::invalid_argument when the chip does not fit
+size_t pq_lds_bytes(const PqArgs& a, uint32_t NW, uint32_t T);
+void launch_pq_count(hipStream_t st, const PqArgs& a, unsigned long long* totals, uint32_t* table);
+void launch_pq_list(hipStream_t st, const PqArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t i_cut, uint32_t R, uint32_t* rows);
 // field_audit.hip — the passes of the field audit (host/field_audit.hpp: contract; Prover::field_audit drives them), per chip.  One wave per
 // trace row, one wave per workgroup, T rows per workgroup one after the other, NB workgroups.  A SLOT of a chip is (interaction, field) in
 // order, NS of them.  totals: u64 [0] live records, [1] floating fields, [2] rows with a floating field, [3 + m] live rows of interaction m,
