@@ -72,6 +72,11 @@ typedef struct vgpu_interaction {
     uint32_t is_send;     /* InteractionType::*Send / *Receive */
 } vgpu_interaction_t;
 
+/* The expression calls return a handle and no status.  A handle stands for the expression AS WRITTEN: the capture shares and folds equal
+ * sub-expressions (x * 0 is the constant 0), but an expression's degree is the reference's (symbolic_expression.rs:36-62: a product adds its
+ * operands' degrees whatever they are), so an AIR gets the log_quotient_degree it gets when captured by SymbolicAirBuilder.  Misuse -- a column
+ * outside [0, width) or [0, preprocessed_width), a handle this AIR has not returned -- gives the handle 0xFFFFFFFF (which is never valid), and the
+ * AIR is refused by vgpu_machine_push_air with VGPU_ERR_INVALID_ARG and a message naming the AIR and the first misuse. */
 int32_t vgpu_air_new(const char* name, uint32_t width, uint32_t preprocessed_width, vgpu_air_t** out);
 void vgpu_air_free(vgpu_air_t* air);
 uint32_t vgpu_air_constant(vgpu_air_t* air, uint32_t canonical);                                  /* SymbolicExpression::Constant */
@@ -90,7 +95,8 @@ int32_t vgpu_air_add_interaction(vgpu_air_t* air, const vgpu_interaction_t* it);
 typedef struct vgpu_machine vgpu_machine_t;
 int32_t vgpu_machine_new(vgpu_machine_t** out);
 /* compiles the constraint program.  log_quotient_degree 1 (every reference chip) .. 3 (constraint degree <= 9) is implemented;
- * beyond that VGPU_ERR_UNSUPPORTED with a message naming the AIR and its degree */
+ * beyond that VGPU_ERR_UNSUPPORTED with a message naming the AIR and its degree.  VGPU_ERR_INVALID_ARG: the capture was misused (above), or the
+ * program needs more registers than the device interpreters hold in a workgroup's LDS (592 at log_quotient_degree 1, 640 above) */
 int32_t vgpu_machine_push_air(vgpu_machine_t* m, const vgpu_air_t* air);
 int32_t vgpu_machine_basic(vgpu_machine_t** out);                         /* the 14-chip BasicMachine from the in-tree chip definitions */
 /* the same 14 chips, but captured the way a foreign host captures them: each chip's eval runs against a builder that only

@@ -142,22 +142,26 @@ void oracle_mmcs_root(uint64_t n_mats, const uint32_t* const* mats, const uint64
 // Returns the number of constraints (out may be null to query it).
 uint32_t oracle_eval_constraints(uint32_t chip, const uint32_t* local, const uint32_t* next, const uint32_t* prep_local, const uint32_t* prep_next,
                                  uint32_t is_first, uint32_t is_last, uint32_t is_transition, uint32_t* out, uint32_t cap) {
-    (void)prep_local; (void)prep_next;  // no BasicMachine chip reads its preprocessed columns in eval
     const size_t w = chips::chip_shape((int)chip).width;
+    // no BasicMachine chip reads its preprocessed columns in eval (their callers may pass short buffers); a scripted AIR may
+    const size_t pw = chips::is_script((int)chip) ? chips::chip_shape((int)chip).preprocessed_width : 0;
     struct Rec {
         using Expr = Fp;
-        std::vector<Fp> l, n;
+        std::vector<Fp> l, n, pl, pn;
         Fp first, last, trans;
         std::vector<Fp> vals;
         Fp from_u32(uint32_t k) const { return Fp(k); }
         const Fp* main_local() const { return l.data(); }
         const Fp* main_next() const { return n.data(); }
+        const Fp* prep_local() const { return pl.data(); }
+        const Fp* prep_next() const { return pn.data(); }
         Fp is_first_row() const { return first; }
         Fp is_last_row() const { return last; }
         Fp is_transition() const { return trans; }
         void assert_zero(const Fp& x) { vals.push_back(x); }
-    } b{std::vector<Fp>(w), std::vector<Fp>(w), Fp(is_first), Fp(is_last), Fp(is_transition), {}};
+    } b{std::vector<Fp>(w), std::vector<Fp>(w), std::vector<Fp>(pw), std::vector<Fp>(pw), Fp(is_first), Fp(is_last), Fp(is_transition), {}};
     for (size_t c = 0; c < w; c++) { b.l[c] = Fp(local[c]); b.n[c] = Fp(next[c]); }
+    for (size_t c = 0; c < pw; c++) { b.pl[c] = Fp(prep_local[c]); b.pn[c] = Fp(prep_next[c]); }
     chips::eval((int)chip, b);
     if (out) for (size_t i = 0; i < b.vals.size() && i < cap; i++) out[i] = b.vals[i].v;
     return (uint32_t)b.vals.size();
@@ -182,6 +186,23 @@ uint32_t oracle_interaction_words(uint32_t chip, uint32_t* out, uint32_t cap) {
 }
 // [width, preprocessed width] of chip `chip` from the oracle's column structs
 void oracle_chip_shape(uint32_t chip, uint32_t out[2]) { auto s = chips::chip_shape((int)chip); out[0] = (uint32_t)s.width; out[1] = (uint32_t)s.preprocessed_width; }
+// A scripted AIR (chips.hpp) for slot `slot` = chip id TEST_SCRIPT0 + slot.  0, or nonzero with the reason in `msg`: the word list is
+// checked here, once, so that no later evaluation can run off its stack or its rows.
+int oracle_set_script(uint32_t slot, const uint32_t* words, uint64_t n, uint32_t width, uint32_t prep_width, char* msg, uint64_t msg_cap) {
+    const char* err = "";
+    chips::Script s;
+    if (slot >= (uint32_t)chips::NUM_SCRIPT_SLOTS) err = "no such script slot";
+    else { s.words.assign(words, words + n); s.width = width; s.prep_width = prep_width; err = chips::script_error(s); }
+    if (*err) { if (msg && msg_cap) { strncpy(msg, err, msg_cap - 1); msg[msg_cap - 1] = 0; } return 1; }
+    chips::script_slot((int)slot) = std::move(s);
+    return 0;
+}
+// [log_quotient_degree, max constraint degree, constraints] of the scripted AIR in `slot`, by the reference's degree rules
+void oracle_script_degree(uint32_t slot, uint32_t out[3]) {
+    DegreeBuilder db;
+    chips::eval(chips::TEST_SCRIPT0 + (int)slot, db);
+    out[0] = log_quotient_degree(MachineDesc::of({chips::TEST_SCRIPT0 + (int)slot}).chips[0]); out[1] = (uint32_t)db.max_degree; out[2] = (uint32_t)db.num_constraints;
+}
 uint32_t oracle_log_quotient_degree(uint32_t chip) { return log_quotient_degree(MachineDesc::basic().chips[chip]); }
 uint32_t oracle_num_interactions(uint32_t chip) { return (uint32_t)MachineDesc::basic().chips[chip].interactions.size(); }
 // generate_permutation_trace of BasicMachine chip `chip`; out is height x 5(M+1), row-major (flatten_to_base).
@@ -257,13 +278,16 @@ void* oracle_prove_basic(const uint32_t* const* main, const uint64_t* heights, c
     res->words = serialize_proof(p);
     return res;
 }
-// Any machine made of chips::ChipIndex / test-AIR ids without preprocessed traces (the general log_quotient_degree tests)
+// Any machine made of chips::ChipIndex / test-AIR ids (the general log_quotient_degree tests).  prep (may be null): one pointer per chip,
+// null or the chip's preprocessed trace (heights[i] x preprocessed width) — committed and observed as prove_basic does, in chip order.
 void* oracle_prove_machine(const uint32_t* chip_ids, uint32_t n_chips, const uint32_t* const* main, const uint64_t* heights, const uint32_t* rc480,
-                           uint32_t log_blowup, uint32_t num_queries, uint32_t pow_bits, int debug_check) {
+                           uint32_t log_blowup, uint32_t num_queries, uint32_t pow_bits, int debug_check, const uint32_t* const* prep) {
     std::vector<int> ids(chip_ids, chip_ids + n_chips);
     MachineDesc md = MachineDesc::of(ids);
     MachineInput in;
     for (uint32_t i = 0; i < n_chips; i++) in.main_traces.push_back(to_matrix(main[i], heights[i], md.chips[i].width));
+    for (uint32_t i = 0; prep && i < n_chips; i++)
+        if (prep[i]) in.preprocessed.push_back({(int)i, to_matrix(prep[i], heights[i], md.chips[i].prep_width)});
     auto* res = new ProveResult();
     auto t0 = std::chrono::steady_clock::now();
     MachineProof p = prove(md, in, make_cfg(rc480, log_blowup, num_queries, pow_bits), &res->dbg, debug_check != 0);
@@ -271,12 +295,17 @@ void* oracle_prove_machine(const uint32_t* chip_ids, uint32_t n_chips, const uin
     res->words = serialize_proof(p);
     return res;
 }
+// prep / prep_heights (may be null): as in oracle_prove_machine; the verifier recomputes their commitment
 int oracle_verify_machine(const uint32_t* chip_ids, uint32_t n_chips, const uint32_t* proof, uint64_t n_words, const uint32_t* rc480, uint32_t log_blowup,
-                          uint32_t num_queries, uint32_t pow_bits, char* msg, uint64_t msg_cap) {
+                          uint32_t num_queries, uint32_t pow_bits, char* msg, uint64_t msg_cap, const uint32_t* const* prep, const uint64_t* prep_heights) {
     MachineProof p;
     const char* err = nullptr;
     if (!deserialize_proof(proof, n_words, p)) err = "malformed proof";
-    if (!err) err = verify(MachineDesc::of(std::vector<int>(chip_ids, chip_ids + n_chips)), {}, p, make_cfg(rc480, log_blowup, num_queries, pow_bits));
+    MachineDesc md = MachineDesc::of(std::vector<int>(chip_ids, chip_ids + n_chips));
+    std::vector<std::pair<int, Matrix>> pre;
+    for (uint32_t i = 0; prep && i < n_chips; i++)
+        if (prep[i]) pre.push_back({(int)i, to_matrix(prep[i], prep_heights[i], md.chips[i].prep_width)});
+    if (!err) err = verify(md, pre, p, make_cfg(rc480, log_blowup, num_queries, pow_bits));
     if (err && msg && msg_cap) { strncpy(msg, err, msg_cap - 1); msg[msg_cap - 1] = 0; }
     return err ? 1 : 0;
 }

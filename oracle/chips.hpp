@@ -493,6 +493,58 @@ template <class B> void eval_pow(B& b, int degree, bool pin_first) {
 }
 constexpr int TEST_POW5 = 100, TEST_POW9 = 101;
 
+// ---------------------------------------------------------------- scripted test AIRs (NOT in the reference)
+// An AIR given at run time as a postfix word list (oracle_set_script, capi.cpp): the independent statement of what an AIR captured
+// through the product's vgpu_air_* FFI has to compute.  The walk evaluates DIRECTLY on whichever builder it is instantiated over (the
+// recorder of oracle_eval_constraints, the degree builder, the prover's and the verifier's folders): no simplification, no sharing, no
+// intermediate form.  Words: SW_CONST v | SW_MAIN col is_next | SW_PREP col is_next | SW_FIRST | SW_LAST | SW_TRANS | SW_ADD | SW_SUB |
+// SW_MUL | SW_NEG | SW_ASSERT (binary words pop y then x and push x op y; SW_ASSERT pops one value and asserts it zero).
+constexpr int TEST_SCRIPT0 = 200, NUM_SCRIPT_SLOTS = 16, SCRIPT_MAX_WIDTH = 2048;
+enum ScriptWord : uint32_t { SW_CONST = 0, SW_MAIN, SW_PREP, SW_FIRST, SW_LAST, SW_TRANS, SW_ADD, SW_SUB, SW_MUL, SW_NEG, SW_ASSERT };
+struct Script { std::vector<uint32_t> words; size_t width = 0, prep_width = 0; };
+inline Script& script_slot(int slot) { static Script slots[NUM_SCRIPT_SLOTS]; return slots[slot]; }
+inline bool is_script(int chip) { return chip >= TEST_SCRIPT0 && chip < TEST_SCRIPT0 + NUM_SCRIPT_SLOTS; }
+// "" or what is wrong with the word list (stack discipline, column ranges): a script is checked once, when it is set
+inline const char* script_error(const Script& s) {
+    if (s.width > (size_t)SCRIPT_MAX_WIDTH || s.prep_width > (size_t)SCRIPT_MAX_WIDTH) return "width above SCRIPT_MAX_WIDTH";
+    size_t depth = 0;
+    for (size_t i = 0; i < s.words.size(); i++) {
+        switch (s.words[i]) {
+            case SW_CONST: if (i + 1 >= s.words.size()) return "cut constant"; i += 1; depth++; break;
+            case SW_MAIN: case SW_PREP:
+                if (i + 2 >= s.words.size()) return "cut variable";
+                if (s.words[i + 1] >= (s.words[i] == SW_MAIN ? s.width : s.prep_width) || s.words[i + 2] > 1) return "variable out of range";
+                i += 2; depth++; break;
+            case SW_FIRST: case SW_LAST: case SW_TRANS: depth++; break;
+            case SW_ADD: case SW_SUB: case SW_MUL: if (depth < 2) return "stack underflow"; depth--; break;
+            case SW_NEG: if (depth < 1) return "stack underflow"; break;
+            case SW_ASSERT: if (depth < 1) return "stack underflow"; depth--; break;
+            default: return "unknown word";
+        }
+    }
+    return depth ? "values left on the stack" : "";
+}
+template <class B> void eval_script(B& b, const Script& s) {
+    using T = typename B::Expr;
+    std::vector<T> st;
+    const std::vector<uint32_t>& w = s.words;
+    for (size_t i = 0; i < w.size(); i++) {
+        switch (w[i]) {
+            case SW_CONST: st.push_back(b.from_u32(w[i + 1])); i += 1; break;
+            case SW_MAIN: st.push_back((w[i + 2] ? b.main_next() : b.main_local())[w[i + 1]]); i += 2; break;
+            case SW_PREP: st.push_back((w[i + 2] ? b.prep_next() : b.prep_local())[w[i + 1]]); i += 2; break;
+            case SW_FIRST: st.push_back(b.is_first_row()); break;
+            case SW_LAST: st.push_back(b.is_last_row()); break;
+            case SW_TRANS: st.push_back(b.is_transition()); break;
+            case SW_ADD: { T y = st.back(); st.pop_back(); T x = st.back(); st.back() = x + y; break; }
+            case SW_SUB: { T y = st.back(); st.pop_back(); T x = st.back(); st.back() = x - y; break; }
+            case SW_MUL: { T y = st.back(); st.pop_back(); T x = st.back(); st.back() = x * y; break; }
+            case SW_NEG: { T x = st.back(); st.back() = -x; break; }
+            case SW_ASSERT: { T x = st.back(); st.pop_back(); b.assert_zero(x); break; }
+        }
+    }
+}
+
 // ---------------------------------------------------------------- the machine (basic/src/lib.rs:151-166)
 enum ChipIndex { CPU = 0, PROGRAM, MEM, ADD, SUB, MUL, DIV, SHIFT, LT, COM, BITWISE, OUTPUT, RANGE, STATIC_DATA, NUM_CHIPS };
 struct ChipShape { const char* name; size_t width, preprocessed_width; };
@@ -515,6 +567,7 @@ inline ChipShape chip_shape(int chip) {
         case TEST_POW5: return {"pow5", 2, 0};
         case TEST_POW9: return {"pow9", 2, 0};
     }
+    if (is_script(chip)) return {"script", script_slot(chip - TEST_SCRIPT0).width, script_slot(chip - TEST_SCRIPT0).prep_width};
     return {"?", 0, 0};
 }
 // Air::eval of chip `chip`; program, mem, div and range have empty evals (program/src/stark.rs:14, memory/src/stark.rs:22-78
@@ -533,7 +586,7 @@ template <class B> void eval(int chip, B& b) {
         case STATIC_DATA: eval_static_data(b); break;
         case TEST_POW5: eval_pow(b, 5, false); break;
         case TEST_POW9: eval_pow(b, 9, true); break;
-        default: break;
+        default: if (is_script(chip)) eval_script(b, script_slot(chip - TEST_SCRIPT0)); break;
     }
 }
 

@@ -172,8 +172,9 @@ def perm_trace(chip, main, challenges15):
 def eval_constraints(chip, local, nxt, prep_local=None, prep_next=None, is_first=0, is_last=0, is_transition=1):
     a, ap = _u32(local)
     b, bp = _u32(nxt)
-    c, cp = _u32(prep_local if prep_local is not None else np.zeros(8, dtype=np.uint32))
-    d, dp = _u32(prep_next if prep_next is not None else np.zeros(8, dtype=np.uint32))
+    npre = max(8, chip_shape(chip)[1])
+    c, cp = _u32(prep_local if prep_local is not None else np.zeros(npre, dtype=np.uint32))
+    d, dp = _u32(prep_next if prep_next is not None else np.zeros(npre, dtype=np.uint32))
     L = lib()
     L.oracle_eval_constraints.restype = ctypes.c_uint32
     n = L.oracle_eval_constraints(ctypes.c_uint32(chip), ap, bp, cp, dp, ctypes.c_uint32(is_first), ctypes.c_uint32(is_last), ctypes.c_uint32(is_transition), None,
@@ -320,8 +321,40 @@ def prove_basic(main_traces, prep_program, prep_range, rc, log_blowup=1, num_que
 TEST_POW5, TEST_POW9 = 100, 101  # the oracle's synthetic higher-degree AIRs (chips.hpp)
 
 
-def prove_machine(chip_ids, main_traces, rc, log_blowup=1, num_queries=40, pow_bits=8, debug_check=False):
-    """Proof of a machine made of the given chip ids (no preprocessed traces): the general log_quotient_degree tests."""
+TEST_SCRIPT0, NUM_SCRIPT_SLOTS = 200, 16  # the oracle's scripted AIRs (chips.hpp): chip id TEST_SCRIPT0 + slot
+SW_CONST, SW_MAIN, SW_PREP, SW_FIRST, SW_LAST, SW_TRANS, SW_ADD, SW_SUB, SW_MUL, SW_NEG, SW_ASSERT = range(11)
+
+
+def set_script(slot, words, width, prep_width=0):
+    """Set the scripted AIR of `slot` to the postfix word list `words` (chips.hpp); returns its chip id.  A malformed list raises."""
+    w, wp = _u32(np.asarray(words, dtype=np.uint32).reshape(-1))
+    msg = ctypes.create_string_buffer(128)
+    if lib().oracle_set_script(ctypes.c_uint32(slot), wp, ctypes.c_uint64(w.size), ctypes.c_uint32(width), ctypes.c_uint32(prep_width), msg, ctypes.c_uint64(128)):
+        raise ValueError("oracle_set_script: " + msg.value.decode())
+    return TEST_SCRIPT0 + slot
+
+
+def script_degree(slot):
+    """(log_quotient_degree, max constraint degree, constraints) of the scripted AIR in `slot`, by the reference's degree rules."""
+    out = np.zeros(3, dtype=np.uint32)
+    lib().oracle_script_degree(ctypes.c_uint32(slot), out.ctypes.data_as(c_u32p))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def _prep_args(prep, n):
+    """One pointer per chip (null where the chip has no preprocessed trace) and the heights; (None, None, keep) when there is none at all."""
+    if prep is None or all(p is None for p in prep):
+        return None, None, []
+    assert len(prep) == n
+    keep = [None if p is None else np.ascontiguousarray(p, dtype=np.uint32) for p in prep]
+    ptrs = (c_u32p * n)(*[k.ctypes.data_as(c_u32p) if k is not None else ctypes.cast(None, c_u32p) for k in keep])
+    hs = (ctypes.c_uint64 * n)(*[0 if k is None else k.shape[0] for k in keep])
+    return ptrs, hs, keep
+
+
+def prove_machine(chip_ids, main_traces, rc, log_blowup=1, num_queries=40, pow_bits=8, debug_check=False, prep=None):
+    """Proof of a machine made of the given chip ids: the general log_quotient_degree tests.  prep: None, or per chip None / its
+    preprocessed trace (as many rows as its main trace)."""
     ids = np.array(chip_ids, dtype=np.uint32)
     keep = [np.ascontiguousarray(m, dtype=np.uint32) for m in main_traces]
     ptrs = (c_u32p * len(keep))(*[k.ctypes.data_as(c_u32p) for k in keep])
@@ -329,18 +362,21 @@ def prove_machine(chip_ids, main_traces, rc, log_blowup=1, num_queries=40, pow_b
     r, rp = _u32(rc)
     L = lib()
     L.oracle_prove_machine.restype = ctypes.c_void_p
+    pptrs, _, pkeep = _prep_args(prep, len(keep))
+    assert all(k is None or k.shape[0] == m.shape[0] for k, m in zip(pkeep, keep))
     h = L.oracle_prove_machine(ids.ctypes.data_as(c_u32p), ctypes.c_uint32(ids.size), ptrs, hs, rp, ctypes.c_uint32(log_blowup), ctypes.c_uint32(num_queries),
-                               ctypes.c_uint32(pow_bits), ctypes.c_int(1 if debug_check else 0))
+                               ctypes.c_uint32(pow_bits), ctypes.c_int(1 if debug_check else 0), pptrs)
     return ProveResult(h)
 
 
-def verify_machine(chip_ids, proof_words, rc, log_blowup=1, num_queries=40, pow_bits=8):
+def verify_machine(chip_ids, proof_words, rc, log_blowup=1, num_queries=40, pow_bits=8, prep=None):
     ids = np.array(chip_ids, dtype=np.uint32)
+    pptrs, phs, pkeep = _prep_args(prep, ids.size)
     w, wp = _u32(proof_words)
     r, rp = _u32(rc)
     msg = ctypes.create_string_buffer(256)
     rcode = lib().oracle_verify_machine(ids.ctypes.data_as(c_u32p), ctypes.c_uint32(ids.size), wp, ctypes.c_uint64(w.size), rp, ctypes.c_uint32(log_blowup),
-                                        ctypes.c_uint32(num_queries), ctypes.c_uint32(pow_bits), msg, ctypes.c_uint64(256))
+                                        ctypes.c_uint32(num_queries), ctypes.c_uint32(pow_bits), msg, ctypes.c_uint64(256), pptrs, phs)
     return None if rcode == 0 else msg.value.decode()
 
 

@@ -38,6 +38,8 @@ template <class T> struct Folder {
     T from_u32(uint32_t k) const { return T(Fp(k)); }
     const T* main_local() const { return main_.local; }
     const T* main_next() const { return main_.next; }
+    const T* prep_local() const { return prep_.local; }
+    const T* prep_next() const { return prep_.next; }
     T is_first_row() const { return first; }
     T is_last_row() const { return last; }
     T is_transition() const { return trans; }
@@ -61,6 +63,8 @@ struct FastFolder {
     Fp from_u32(uint32_t k) const { return Fp(k); }
     const Fp* main_local() const { return main_.local; }
     const Fp* main_next() const { return main_.next; }
+    const Fp* prep_local() const { return prep_.local; }
+    const Fp* prep_next() const { return prep_.next; }
     Fp is_first_row() const { return first; }
     Fp is_last_row() const { return last; }
     Fp is_transition() const { return trans; }
@@ -90,6 +94,8 @@ struct DebugBuilder {
     Fp from_u32(uint32_t k) const { return Fp(k); }
     const Fp* main_local() const { return main_.local; }
     const Fp* main_next() const { return main_.next; }
+    const Fp* prep_local() const { return prep_.local; }
+    const Fp* prep_next() const { return prep_.next; }
     Fp is_first_row() const { return first; }
     Fp is_last_row() const { return last; }
     Fp is_transition() const { return trans; }
@@ -109,10 +115,12 @@ struct DegreeBuilder {
     };
     int max_degree = 0;
     size_t num_constraints = 0;
-    std::vector<Expr> row = std::vector<Expr>(128, Expr{1});  // every trace variable has degree 1
+    std::vector<Expr> row = std::vector<Expr>(chips::SCRIPT_MAX_WIDTH, Expr{1});  // every trace variable has degree 1
     Expr from_u32(uint32_t) const { return Expr{0}; }
     const Expr* main_local() const { return row.data(); }
     const Expr* main_next() const { return row.data(); }
+    const Expr* prep_local() const { return row.data(); }
+    const Expr* prep_next() const { return row.data(); }
     Expr is_first_row() const { return Expr{1}; }
     Expr is_last_row() const { return Expr{1}; }
     Expr is_transition() const { return Expr{0}; }

@@ -35,7 +35,26 @@ static int32_t fail(int32_t code, const std::string& msg) { g_err = msg; return 
         return fail(m.find("hip") != std::string::npos ? VGPU_ERR_HIP : VGPU_ERR_INTERNAL, m); \
     }
 
-struct vgpu_air { std::string name; vair::Dag dag; std::vector<vair::Interaction> interactions; };
+// What vgpu_air_* hands out and takes is a HANDLE: an index into `handles`, (DAG node, degree).  The DAG folds and shares (x * 0 is the node of
+// the constant 0); the degree does not: it follows the reference's rules on the expression as the host wrote it (symbolic_expression.rs:36-62:
+// a product adds its operands' degrees whatever they are), so that an AIR captured here gets the log_quotient_degree the same AIR gets in-tree.
+// The expression entry points return no status: the first misuse (a column outside the AIR, a handle that does not exist) is kept in `error`,
+// its result is BAD — never a node — and vgpu_machine_push_air refuses the AIR with that message.
+struct vgpu_air {
+    static constexpr uint32_t BAD = 0xffffffffu;
+    static constexpr int DEGREE_CAP = 1 << 20;  // far above anything accepted; keeps repeated squaring from overflowing
+    std::string name; vair::Dag dag; std::vector<vair::Interaction> interactions;
+    std::vector<std::pair<uint32_t, int>> handles;
+    int max_degree = 0;
+    std::string error;
+    uint32_t hand(uint32_t node, int degree) { handles.push_back({node, std::min(degree, DEGREE_CAP)}); return (uint32_t)handles.size() - 1; }
+    uint32_t bad(const std::string& what) { if (error.empty()) error = "AIR '" + name + "': " + what; return BAD; }
+    bool known(uint32_t h, const char* fn) {
+        if (h < handles.size()) return true;
+        bad(std::string(fn) + ": node " + std::to_string(h) + " does not exist");
+        return false;
+    }
+};
 struct vgpu_machine { MachineDesc desc; };
 struct vgpu_challenger { std::unique_ptr<Poseidon16> perm; std::unique_ptr<Challenger> ch; };
 // Device objects keep their prover (device context, memory pool) alive: a host may free handles in any order — a garbage
@@ -100,16 +119,37 @@ int32_t vgpu_air_new(const char* name, uint32_t width, uint32_t preprocessed_wid
     })
 }
 void vgpu_air_free(vgpu_air_t* air) { delete air; }
-uint32_t vgpu_air_constant(vgpu_air_t* a, uint32_t canonical) { return a->dag.constant(canonical); }
-uint32_t vgpu_air_variable(vgpu_air_t* a, uint32_t is_prep, uint32_t column, uint32_t is_next) { return a->dag.var(is_prep != 0, (int)column, is_next != 0); }
-uint32_t vgpu_air_is_first_row(vgpu_air_t* a) { return a->dag.selector(vair::N_FIRST); }
-uint32_t vgpu_air_is_last_row(vgpu_air_t* a) { return a->dag.selector(vair::N_LAST); }
-uint32_t vgpu_air_is_transition(vgpu_air_t* a) { return a->dag.selector(vair::N_TRANS); }
-uint32_t vgpu_air_add(vgpu_air_t* a, uint32_t x, uint32_t y) { return a->dag.add(x, y); }
-uint32_t vgpu_air_sub(vgpu_air_t* a, uint32_t x, uint32_t y) { return a->dag.sub(x, y); }
-uint32_t vgpu_air_mul(vgpu_air_t* a, uint32_t x, uint32_t y) { return a->dag.mul(x, y); }
-uint32_t vgpu_air_neg(vgpu_air_t* a, uint32_t x) { return a->dag.neg(x); }
-void vgpu_air_assert_zero(vgpu_air_t* a, uint32_t node) { a->dag.constraints.push_back(node); }
+uint32_t vgpu_air_constant(vgpu_air_t* a, uint32_t canonical) { return a->hand(a->dag.constant(canonical), 0); }
+uint32_t vgpu_air_variable(vgpu_air_t* a, uint32_t is_prep, uint32_t column, uint32_t is_next) {
+    const uint32_t w = (uint32_t)(is_prep ? a->dag.prep_width : a->dag.width);
+    if (column >= w) return a->bad(std::string("vgpu_air_variable: ") + (is_prep ? "preprocessed" : "main") + " column " + std::to_string(column) + " of " + std::to_string(w));
+    if (column > 0xffffu) return a->bad("vgpu_air_variable: column " + std::to_string(column) + " does not fit the program's 16-bit column field");
+    return a->hand(a->dag.var(is_prep != 0, (int)column, is_next != 0), 1);
+}
+uint32_t vgpu_air_is_first_row(vgpu_air_t* a) { return a->hand(a->dag.selector(vair::N_FIRST), 1); }
+uint32_t vgpu_air_is_last_row(vgpu_air_t* a) { return a->hand(a->dag.selector(vair::N_LAST), 1); }
+uint32_t vgpu_air_is_transition(vgpu_air_t* a) { return a->hand(a->dag.selector(vair::N_TRANS), 0); }
+uint32_t vgpu_air_add(vgpu_air_t* a, uint32_t x, uint32_t y) {
+    if (!a->known(x, "vgpu_air_add") || !a->known(y, "vgpu_air_add")) return vgpu_air::BAD;
+    return a->hand(a->dag.add(a->handles[x].first, a->handles[y].first), std::max(a->handles[x].second, a->handles[y].second));
+}
+uint32_t vgpu_air_sub(vgpu_air_t* a, uint32_t x, uint32_t y) {
+    if (!a->known(x, "vgpu_air_sub") || !a->known(y, "vgpu_air_sub")) return vgpu_air::BAD;
+    return a->hand(a->dag.sub(a->handles[x].first, a->handles[y].first), std::max(a->handles[x].second, a->handles[y].second));
+}
+uint32_t vgpu_air_mul(vgpu_air_t* a, uint32_t x, uint32_t y) {
+    if (!a->known(x, "vgpu_air_mul") || !a->known(y, "vgpu_air_mul")) return vgpu_air::BAD;
+    return a->hand(a->dag.mul(a->handles[x].first, a->handles[y].first), a->handles[x].second + a->handles[y].second);
+}
+uint32_t vgpu_air_neg(vgpu_air_t* a, uint32_t x) {
+    if (!a->known(x, "vgpu_air_neg")) return vgpu_air::BAD;
+    return a->hand(a->dag.neg(a->handles[x].first), a->handles[x].second);
+}
+void vgpu_air_assert_zero(vgpu_air_t* a, uint32_t node) {
+    if (!a->known(node, "vgpu_air_assert_zero")) return;
+    a->dag.constraints.push_back(a->handles[node].first);
+    a->max_degree = std::max(a->max_degree, a->handles[node].second);
+}
 static vair::VirtualCol to_vcol(const vgpu_vcol_t& v) {
     vair::VirtualCol c;
     c.constant = v.constant;
@@ -135,7 +175,8 @@ int32_t vgpu_machine_new(vgpu_machine_t** out) { VG_TRY({ if (!out) throw std::i
 int32_t vgpu_machine_push_air(vgpu_machine_t* m, const vgpu_air_t* air) {
     VG_TRY({
         if (!m || !air) throw std::invalid_argument("null argument");
-        AirDesc d = MachineDesc::make_air_from_dag(air->name, air->dag, air->interactions);
+        if (!air->error.empty()) throw std::invalid_argument(air->error);
+        AirDesc d = MachineDesc::make_air_from_dag(air->name, air->dag, air->interactions, air->max_degree);
         // log_quotient_degree 1 (constraint degree <= 3 = LOOKUP_DEGREE_BOUND, machine/src/lib.rs:36) is what every chip of the
         // reference has; captured AIRs of degree up to 9 (log_quotient_degree 2, 3) run through the general quotient kernel.  Beyond
         // that the AIR is refused HERE, when it is pushed.
@@ -144,6 +185,10 @@ int32_t vgpu_machine_push_air(vgpu_machine_t* m, const vgpu_air_t* air) {
                     std::to_string(d.log_quotient_degree) + "; the device path implements log_quotient_degree 1..3 (constraint degree <= 9)";
             return VGPU_ERR_UNSUPPORTED;
         }
+        // programs of more than 64 registers run from an LDS register file: what does not fit it is refused here, not at a launch
+        if (d.program.num_regs > vk::interp_lds_max_regs(d.log_quotient_degree))
+            throw std::invalid_argument("AIR '" + air->name + "': the constraint program needs " + std::to_string(d.program.num_regs) + " registers; the interpreters of log_quotient_degree " +
+                                        std::to_string(d.log_quotient_degree) + " hold " + std::to_string(vk::interp_lds_max_regs(d.log_quotient_degree)) + " in a workgroup's LDS");
         m->desc.airs.push_back(std::move(d));
     })
 }

@@ -46,16 +46,23 @@ struct MachineDesc {
         return a;
     }
 
-    // From an externally captured DAG (the vgpu_air_* FFI path).  Degree comes from the DAG itself.
-    static AirDesc make_air_from_dag(const std::string& name, const vair::Dag& dag, std::vector<vair::Interaction> interactions) {
+    // From an externally captured DAG (the vgpu_air_* FFI path).  max_degree is the largest constraint degree of the expressions AS THE HOST
+    // WROTE THEM, by the reference's rules (no folding: 0 * x^4 has degree 4) — the capture tracks it beside the folded DAG, whose own node
+    // degrees can only be lower; the proof shape (log_quotient_degree) must be the one the same chip gets when it is captured in-tree.
+    static AirDesc make_air_from_dag(const std::string& name, const vair::Dag& dag, std::vector<vair::Interaction> interactions, int max_degree) {
         AirDesc a;
         a.name = name; a.width = (uint32_t)dag.width; a.prep_width = (uint32_t)dag.prep_width;
         a.program = vair::compile(dag);
-        a.max_constraint_degree = dag.max_degree();
+        a.max_constraint_degree = max_degree;
         a.log_quotient_degree = vair::log_quotient_degree_from(a.max_constraint_degree);
         a.interactions = std::move(interactions);
         a.interaction_words = vk::encode_interactions(a.interactions);
         return a;
+    }
+
+    // A DAG built directly (no capture beside it): the degree its own nodes carry
+    static AirDesc make_air_from_dag(const std::string& name, const vair::Dag& dag, std::vector<vair::Interaction> interactions) {
+        return make_air_from_dag(name, dag, std::move(interactions), dag.max_degree());
     }
 
     static MachineDesc basic() {

@@ -47,6 +47,23 @@ struct QuotientArgs {
     }
 };
 
+// The interpreters with an LDS register file (programs of more than 64 registers) keep it slot-major, reg[slot][thread], and shrink the
+// workgroup down to INTERP_LDS_MIN_THREADS (one wave) before the file stops fitting: a program may hold as many registers as one wave's
+// file fits the dynamic LDS the kernel may have.  k_quotient<0> (log_quotient_degree 1) shares the CU's 160 KiB with its 10 KiB static
+// transpose tile of the natural-order store; k_quotient_general<0> and k_check_constraints<INTERPRET> have no static LDS.  These figures are
+// the kernels' dynamic-LDS limits (hipFuncSetAttribute), what their launches size by, and what vgpu_machine_push_air refuses above.
+constexpr uint32_t INTERP_LDS_MIN_THREADS = 64;
+constexpr uint32_t INTERP_LDS_BYTES_PAIR = 148 * 1024, INTERP_LDS_BYTES_GENERAL = 160 * 1024;
+constexpr uint32_t INTERP_LDS_MAX_REGS_PAIR = INTERP_LDS_BYTES_PAIR / (4 * INTERP_LDS_MIN_THREADS);        // 592: k_quotient<0>
+constexpr uint32_t INTERP_LDS_MAX_REGS_GENERAL = INTERP_LDS_BYTES_GENERAL / (4 * INTERP_LDS_MIN_THREADS);  // 640: k_quotient_general<0>
+// the largest register file every kernel that runs an AIR of this log_quotient_degree holds
+constexpr uint32_t interp_lds_max_regs(unsigned lqd) { return lqd == 1 ? INTERP_LDS_MAX_REGS_PAIR : INTERP_LDS_MAX_REGS_GENERAL; }
+// threads per workgroup of an LDS-file interpreter launch: 256 while the file fits 64 KiB, halved down to one wave
+inline unsigned interp_lds_threads(uint32_t n_regs) {
+    unsigned threads = 256;
+    while (threads > INTERP_LDS_MIN_THREADS && (size_t)n_regs * threads * 4 > 64 * 1024) threads >>= 1;
+    return threads;
+}
 
 // layout.hip
 void launch_ingest(hipStream_t st, const uint32_t* src_dev, DMatView dst, bool bitrev);

@@ -128,6 +128,8 @@ void launch_ingest(hipStream_t st, const uint32_t* src_dev, DMatView dst, bool b
     int log_h = (int)vg::log2_strict_u64(dst.height);
     unsigned blocks = (unsigned)((dst.height + 63) / 64);
     size_t lds = (size_t)64 * (dst.width | 1) * 4;
+    // the 64-row tile of every column has to fit a workgroup's LDS (160 KiB: 639 columns); said here, not by the launch's "invalid argument"
+    if (lds > 160 * 1024) throw std::invalid_argument("ingest: a matrix of " + std::to_string(dst.width) + " columns is wider than the 639 columns whose 64-row tile fits a workgroup's LDS");
     ProfScope ps("k_ingest", st, 8.0 * dst.height * dst.width);
     VK_LAUNCH(k_ingest, dim3(blocks), dim3(256), lds, st, src_dev, dst, log_h, bitrev ? 1 : 0);
 }

@@ -585,8 +585,10 @@ void launch_check_constraints(hipStream_t st, const QuotientArgs& a_in, unsigned
         VG_CHECK(CHIP_COM) VG_CHECK(CHIP_BITWISE) VG_CHECK(CHIP_OUTPUT) VG_CHECK(CHIP_STATIC_DATA)
 #undef VG_CHECK
         case QuotientArgs::INTERPRET: {
-            unsigned threads = 256;
-            while (threads > 64 && (size_t)a.n_regs * threads * 4 > 64 * 1024) threads >>= 1;
+            static bool attr = false;
+            if (!attr) { (void)hipFuncSetAttribute((const void*)k_check_constraints<QuotientArgs::INTERPRET>, hipFuncAttributeMaxDynamicSharedMemorySize, INTERP_LDS_BYTES_GENERAL); attr = true; }
+            if (a.n_regs > INTERP_LDS_MAX_REGS_GENERAL) throw std::invalid_argument("check_constraints: the constraint program needs more registers than a workgroup's LDS holds");
+            const unsigned threads = interp_lds_threads(a.n_regs);
             VK_LAUNCH((k_check_constraints<QuotientArgs::INTERPRET>), dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), (size_t)a.n_regs * threads * 4, st, a,
                                first_bad_dev);
             break;
@@ -599,10 +601,13 @@ void launch_quotient(hipStream_t st, const QuotientArgs& a_in, const DeviceTable
     const QuotientArgs a = a_in.normalised();  // one GPU: next rows from the same LDEs, 2^lqd further in natural index
     static bool attr = false;
     if (!attr) {
-        (void)hipFuncSetAttribute((const void*)k_quotient<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 148 * 1024);  // 160 KiB minus the 10 KiB static transpose tile of the natural-order store
-        (void)hipFuncSetAttribute((const void*)k_quotient_general<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)k_quotient<0>, hipFuncAttributeMaxDynamicSharedMemorySize, INTERP_LDS_BYTES_PAIR);  // 160 KiB minus the 10 KiB static transpose tile of the natural-order store
+        (void)hipFuncSetAttribute((const void*)k_quotient_general<0>, hipFuncAttributeMaxDynamicSharedMemorySize, INTERP_LDS_BYTES_GENERAL);
         attr = true;
     }
+    // vgpu_machine_push_air refuses such a program; a launch must never ask for more LDS than the limit set above
+    if (a.native_chip == QuotientArgs::INTERPRET && a.n_regs > interp_lds_max_regs((unsigned)a.lqd))
+        throw std::invalid_argument("quotient: the constraint program needs more registers than a workgroup's LDS holds");
     uint64_t n = 1ull << a.log_n;
     if (a.lqd != 1) {  // higher-degree AIRs: the interpreted program over 2^lqd points per thread
         if (a.lqd < 1 || a.lqd > 3 || a.native_chip != QuotientArgs::INTERPRET) throw std::runtime_error("quotient: log_quotient_degree must be 1..3 (and above 1 only for interpreted AIRs)");
@@ -614,7 +619,7 @@ void launch_quotient(hipStream_t st, const QuotientArgs& a_in, const DeviceTable
             else VK_LAUNCH(k_quotient_general<2>, grid, dim3(threads), 0, st, a, tb);
             return;
         }
-        while (threads > 64 && (size_t)a.n_regs * threads * 4 > 64 * 1024) threads >>= 1;
+        threads = interp_lds_threads(a.n_regs);
         VK_LAUNCH(k_quotient_general<0>, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), (size_t)a.n_regs * threads * 4, st, a, tb);
         return;
     }
@@ -657,8 +662,7 @@ void launch_quotient(hipStream_t st, const QuotientArgs& a_in, const DeviceTable
         else VK_LAUNCH(k_quotient<2>, grid, dim3(threads), 0, st, a, tb);
         return;
     }
-    unsigned threads = 256;
-    while (threads > 64 && (size_t)a.n_regs * threads * 4 > 64 * 1024) threads >>= 1;
+    const unsigned threads = interp_lds_threads(a.n_regs);
     size_t lds = (size_t)a.n_regs * threads * 4;
     VK_LAUNCH(k_quotient<0>, dim3((unsigned)((n + threads - 1) / threads)), dim3(threads), lds, st, a, tb);
 }
