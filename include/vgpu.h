@@ -974,6 +974,82 @@ const uint32_t* vgpu_product_report_words(const vgpu_product_report_t* r);
 void vgpu_product_report_timing(const vgpu_product_report_t* r, double out[3]);
 void vgpu_product_report_free(vgpu_product_report_t* r);
 
+/* ---- Domain audit: the audits above judge a witness by local algebra.  A LOOKUP MEMBERSHIP ties a cell to a set ("this cell is a byte because
+ * it is sent to the range bus"), and none of them sees a missing one.  Per chip and main column: which set of values does this witness put
+ * there, and on which rows is a narrow column not a field of a live send to a lookup table.  Inputs: exactly what vgpu_prove and the audits take.
+ *   vcol           (vgpu_vcol_t) constant + sum weight * cell (mod p) at row r, over main or preprocessed cells of row r.  A field or count is
+ *                  BARE(c) iff it has one term, main, column c, weight 1, constant 0.  A record (chip, interaction, row) is LIVE iff its count
+ *                  vcol != 0 at that row.
+ *   column domain  per main column of every audited chip, over all n rows, canonical values: min, max, nonzero_rows, wide_rows (value >= 2^16),
+ *                  distinct_narrow (the exact number of distinct values < 2^16), dense (1 iff wide_rows = 0 and distinct_narrow = max - min +
+ *                  1), bits (the bit length of max), class 0 CONSTANT (min = max), 1 BOOLEAN (max <= 1, not constant), 2 BYTE (max < 2^8), 3
+ *                  HALF (max < 2^16), 4 WIDE.  NARROW iff the class is BYTE or HALF and max < 2^max_bits.
+ *   lookup buses   a TABLE CHIP has zero constraints, zero sends and at least one receive.  Bus (is_global, bus_index) is a LOOKUP BUS iff it
+ *                  has a receive and every receive on it, machine-wide, belongs to a table chip: structural, independent of the witness
+ *                  (lookup_auto = 1).  With lookup_auto = 0 bit bus_index of lookup_global_mask / lookup_local_mask decides; a machine with
+ *                  a bus index >= 64 is refused then.  Buses are numbered in ascending (is_global, bus_index).
+ *   appearances    an (interaction, field position) at which column c is bare; per appearance is_send, the bus, the position, live_rows.
+ *                  Per column: guarded_rows (rows with at least one live bare SEND on a lookup bus), sent_rows (a live bare send on any other
+ *                  bus), received_rows (a live bare receive), unguarded_rows = n - guarded_rows, unguarded_nonzero_rows (unguarded and the cell
+ *                  != 0), mixed_rows (rows with a live send one of whose fields reads c without being bare(c)).
+ *   entries        the narrow columns with unguarded_nonzero_rows > 0, ascending (chip, column), each with its appearances and its first
+ *                  max_rows_per_entry unguarded non-zero rows, ascending, with their values; total_entries stays exact when the list is cut.
+ *   bus positions  per bus, field position and direction, over the live records of the WHOLE machine (chip_mask does not narrow them): min,
+ *                  max, distinct_narrow, wide_records, records and the bus's lookup flag: what a table actually offers.
+ * What it is not: THIS witness only (a short program leaves columns accidentally narrow); only bare fields count as guards (a send of 256 a + b
+ * guards neither column: see mixed_rows); values near p (small negatives) are WIDE; a guard says the cell is looked up, not that the table is
+ * sound (the range chip's counter is an unconstrained main column, which the mutation audit reports); `check`'s exit status never depends on it.
+ * Options: max_entries (default 1024, at most 2^24), max_rows_per_entry (default 4, at most 4096), chip_mask (0: all), max_bits (0: 16; above 16
+ * refused), lookup_auto, the two masks, reserved (must be zero).  A null pointer gives the defaults.  In a struct max_entries, max_rows_per_entry
+ * and lookup_auto are taken AS GIVEN (0 entries / 0 rows list nothing and keep every count exact; lookup_auto = 0 with zero masks names no lookup
+ * bus): start from the defaults, not from a zeroed struct.
+ * vgpu_domain_audit runs on the device (kernels/domain_audit.hip), queued on the prover context, wave64.  (1) k_da_scan: gridDim.y = the chip's
+ * virtual columns (its main columns, then every (interaction, field) gated by its count), gridDim.x = at most 2048 slices of whole 256-row
+ * tiles; a workgroup of 256 threads streams its slice (main columns are column-major: coalesced), reduces min / max / counts by wave shuffles
+ * and LDS to one integer atomic of each kind, and sets values < 2^16 in an 8 KB LDS bitmap (a wave whose live lanes hold one value sets the
+ * bit once), which it ORs into the column's 2048-word bitmap in device memory.  (2) k_da_classify: per bitmap the popcount, dense, bits, class,
+ * narrow.  (3) k_da_guard: one thread per row walks the chip's appearance table (staged in LDS), counts per wave by ballots, per workgroup in
+ * LDS, one add per workgroup; the unguarded non-zero rows of narrow columns are listed by count -> scan -> list, no atomic admits a row.  The
+ * only atomics are integer OR, min, max and add: every word is the same run after run.  Scratch from the pool, zeroed by one memset;
+ * VGPU_ERR_OOM with the arithmetic when the pool cannot give it.  vgpu_domain_audit_host: the same contract on the host, one thread, no limits.
+ * Report image (vgpu_domain_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x314d4456 "VDM1" [1] word count [2] max_bits [3] truncated [4,5] total_entries (exact even when the list is cut) [6] reported
+ *   [7] n_chips [8] lookup_auto [9] n_buses [10] n_positions [11] 0
+ *   per chip, in machine order, 10 words: [0] width [1] constraints [2] interactions [3] audited (0 / 1) [4,5] height (u64) [6] is_table
+ *   [7] narrow columns [8] entries [9] appearances; then `width` column records of 24 words: [0] min [1] max [2] distinct_narrow [3] class
+ *   [4] dense [5] bits [6] narrow [7] appearances [8,9] nonzero_rows [10,11] wide_rows [12,13] guarded_rows [14,15] sent_rows [16,17]
+ *   received_rows [18,19] unguarded_rows [20,21] unguarded_nonzero_rows [22,23] mixed_rows.  A chip that is not audited keeps words 0 .. 6 of
+ *   its block; the rest and its column records are 0.
+ *   per bus, ascending (is_global, bus_index), 4 words: is_global, bus_index, lookup, width (the most fields of an interaction on it)
+ *   per bus, position and direction (sends, then receives), 12 words: [0] bus (its number in the list above) [1] position [2] is_send
+ *   [3] lookup [4] min [5] max [6] distinct_narrow [7] 0 [8,9] wide_records [10,11] records; without a live record [4 .. 11] are 0.
+ *   per entry, 8 + 8 A + 2 L words: chip, column, class, max, A = appearances, L = listed rows = min(unguarded_nonzero_rows,
+ *   max_rows_per_entry), unguarded_nonzero_rows (u64); then per appearance 8 words: interaction, position, is_send, is_global, bus_index, lookup
+ *   (a send on a lookup bus), live_rows (u64); then L (row, value) pairs. */
+typedef struct vgpu_domain_audit_opts {
+    uint64_t max_entries;
+    uint32_t max_rows_per_entry;
+    uint32_t chip_mask;
+    uint32_t max_bits;
+    uint32_t lookup_auto;
+    uint64_t lookup_global_mask;
+    uint64_t lookup_local_mask;
+    uint32_t reserved[2];
+} vgpu_domain_audit_opts_t;
+typedef struct vgpu_domain_report vgpu_domain_report_t;
+int32_t vgpu_domain_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                          uint32_t n_prep, const vgpu_domain_audit_opts_t* opts, vgpu_domain_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_domain_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                               const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                               const vgpu_domain_audit_opts_t* opts, vgpu_domain_report_t** out);
+uint64_t vgpu_domain_report_len(const vgpu_domain_report_t* r);
+const uint32_t* vgpu_domain_report_words(const vgpu_domain_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: cells scanned (main cells of the
+ * audited chips plus one per evaluated count or field vcol and row) */
+void vgpu_domain_report_timing(const vgpu_domain_report_t* r, double out[3]);
+void vgpu_domain_report_free(vgpu_domain_report_t* r);
+
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
  *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct

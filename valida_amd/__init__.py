@@ -1618,6 +1618,118 @@ def product_audit_host(machine, main_matrices, preprocessed, max_entries=1024, m
     return _audit_host("product", machine, main_matrices, preprocessed, opts)
 
 
+class DomainAuditOpts(ctypes.Structure):  # vgpu_domain_audit_opts_t
+    _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("max_bits", ctypes.c_uint32),
+                ("lookup_auto", ctypes.c_uint32), ("lookup_global_mask", ctypes.c_uint64), ("lookup_local_mask", ctypes.c_uint64), ("reserved", ctypes.c_uint32 * 2)]
+
+
+DOMAIN_CLASSES = ("constant", "boolean", "byte", "half", "wide")
+
+
+class DomainReport(_AuditReport):
+    """The domain audit of a witness (vgpu_domain_audit / vgpu_domain_audit_host; the contract is stated in include/vgpu.h), as plain Python
+    values: max_bits, lookup_auto, truncated, total_entries (the narrow columns with an unguarded non-zero row), reported,
+    chips = [dict(chip, width, constraints, interactions, audited, height, is_table, narrow, entries, appearances)],
+    columns(chip) = [dict(column, min, max, distinct_narrow, cls ("constant" / "boolean" / "byte" / "half" / "wide"), dense, bits, narrow,
+    appearances, nonzero_rows, wide_rows, guarded_rows, sent_rows, received_rows, unguarded_rows, unguarded_nonzero_rows, mixed_rows)] ([] for a
+    chip that is not audited),
+    buses = [dict(bus, is_global, bus_index, lookup, width, positions=[dict(position, is_send, lookup, min, max, distinct_narrow, wide_records,
+    records)])] ascending by (is_global, bus_index), per position the sends, then the receives,
+    entries = [dict(chip, column, cls, max, unguarded_nonzero_rows, appearances=[dict(interaction, position, is_send, is_global, bus_index, lookup,
+    live_rows)], rows=[(row, value)])] ascending by (chip, column),
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (cells scanned).
+    THIS witness only, bare fields only: candidates for a missing range check, not findings."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 12 or w[0] != 0x314d4456 or w[1] != len(w):
+            raise ValueError("not a domain report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.max_bits, self.truncated = w[2], bool(w[3])
+        self.total_entries, self.reported = w[4] | (w[5] << 32), w[6]
+        self.lookup_auto = bool(w[8])
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        pos = 12
+        self.chips, self._columns = [], []
+        for c in range(w[7]):
+            self.chips.append(dict(chip=c, width=w[pos], constraints=w[pos + 1], interactions=w[pos + 2], audited=bool(w[pos + 3]), height=u64(pos + 4), is_table=bool(w[pos + 6]),
+                                   narrow=w[pos + 7], entries=w[pos + 8], appearances=w[pos + 9]))
+            audited, width = bool(w[pos + 3]), w[pos]
+            pos += 10
+            cols = []
+            for k in range(width):
+                if audited:
+                    cols.append(dict(column=k, min=w[pos], max=w[pos + 1], distinct_narrow=w[pos + 2], cls=DOMAIN_CLASSES[w[pos + 3]], dense=bool(w[pos + 4]), bits=w[pos + 5],
+                                     narrow=bool(w[pos + 6]), appearances=w[pos + 7], nonzero_rows=u64(pos + 8), wide_rows=u64(pos + 10), guarded_rows=u64(pos + 12),
+                                     sent_rows=u64(pos + 14), received_rows=u64(pos + 16), unguarded_rows=u64(pos + 18), unguarded_nonzero_rows=u64(pos + 20), mixed_rows=u64(pos + 22)))
+                pos += 24
+            self._columns.append(cols)
+        self.buses = []
+        for b in range(w[9]):
+            self.buses.append(dict(bus=b, is_global=bool(w[pos]), bus_index=w[pos + 1], lookup=bool(w[pos + 2]), width=w[pos + 3], positions=[]))
+            pos += 4
+        for _ in range(w[10]):
+            self.buses[w[pos]]["positions"].append(dict(position=w[pos + 1], is_send=bool(w[pos + 2]), lookup=bool(w[pos + 3]), min=w[pos + 4], max=w[pos + 5], distinct_narrow=w[pos + 6],
+                                                        wide_records=u64(pos + 8), records=u64(pos + 10)))
+            pos += 12
+        self.entries = []
+        for _ in range(self.reported):
+            A, L = w[pos + 4], w[pos + 5]
+            at = pos + 8
+            apps = [dict(interaction=w[at + 8 * k], position=w[at + 8 * k + 1], is_send=bool(w[at + 8 * k + 2]), is_global=bool(w[at + 8 * k + 3]), bus_index=w[at + 8 * k + 4],
+                         lookup=bool(w[at + 8 * k + 5]), live_rows=u64(at + 8 * k + 6)) for k in range(A)]
+            at += 8 * A
+            self.entries.append(dict(chip=w[pos], column=w[pos + 1], cls=DOMAIN_CLASSES[w[pos + 2]], max=w[pos + 3], unguarded_nonzero_rows=u64(pos + 6), appearances=apps,
+                                     rows=[(w[at + 2 * k], w[at + 2 * k + 1]) for k in range(L)]))
+            pos = at + 2 * L
+        assert pos == len(w)
+
+    def columns(self, chip):
+        """The column records of `chip` ([] when it was not audited)."""
+        return self._columns[chip]
+
+    def unguarded(self, chip):
+        """The listed columns of `chip` that are narrow and hold a non-zero cell on a row with no live bare send to a lookup bus."""
+        return [e["column"] for e in self.entries if e["chip"] == chip]
+
+    def lookup_buses(self):
+        """[(is_global, bus_index)] of the buses counted as lookup tables."""
+        return [(b["is_global"], b["bus_index"]) for b in self.buses if b["lookup"]]
+
+    def to_dict(self):
+        return dict(max_bits=self.max_bits, lookup_auto=self.lookup_auto, truncated=self.truncated, total_entries=self.total_entries, reported=self.reported, device_ms=self.device_ms,
+                    host_ms=self.host_ms, evaluations=self.evaluations, chips=self.chips, columns=self._columns, buses=self.buses, entries=self.entries)
+
+
+def _domain_opts(max_entries, max_rows_per_entry, chips, max_bits, lookup_buses):
+    """lookup_buses: None (the structural rule) or a list of (is_global, bus_index) pairs / bare global bus indices that count as lookup tables."""
+    if int(max_entries) < 0 or int(max_rows_per_entry) < 0 or int(max_bits) < 1:
+        raise VgpuError(-1, "domain_audit: max_entries and max_rows_per_entry must not be negative, max_bits at least 1")
+    gmask = lmask = 0
+    if lookup_buses is not None:
+        for b in lookup_buses:
+            is_global, index = (True, int(b)) if isinstance(b, (int, np.integer)) else (bool(b[0]), int(b[1]))
+            if index < 0 or index > 63:
+                raise VgpuError(-1, "domain_audit: lookup_buses names bus indices below 64")
+            if is_global:
+                gmask |= 1 << index
+            else:
+                lmask |= 1 << index
+    return DomainAuditOpts(int(max_entries), int(max_rows_per_entry), _chip_mask("domain", chips), int(max_bits), 1 if lookup_buses is None else 0, gmask, lmask, (ctypes.c_uint32 * 2)(0, 0))
+
+
+def domain_audit_host(machine, main_matrices, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None, max_bits=16, lookup_buses=None):
+    """The domain audit on the HOST (vgpu_domain_audit_host: no device, one thread): main_matrices = one canonical matrix per chip,
+    preprocessed = [(chip index, matrix)], chips = the chip indices to audit (default: all), max_bits = a column is narrow below 2^max_bits,
+    lookup_buses = None (the structural rule) or the buses that count as lookup tables; a DomainReport back."""
+    opts = _domain_opts(max_entries, max_rows_per_entry, chips, max_bits, lookup_buses)
+    return _audit_host("domain", machine, main_matrices, preprocessed, opts)
+
+
 class TransitionAuditOpts(ctypes.Structure):  # vgpu_transition_audit_opts_t
     _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("max_terms", ctypes.c_uint32),
                 ("min_gate_windows", ctypes.c_uint32), ("max_gates", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
@@ -2040,7 +2152,7 @@ def coverage_audit_host(machine, main_matrices, preprocessed, deltas=None, max_c
     return _audit_host("coverage", machine, main_matrices, preprocessed, opts)
 
 
-_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, product=ProductReport, field=FieldReport,
+_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, product=ProductReport, domain=DomainReport, field=FieldReport,
                       link=LinkReport, coverage=CoverageReport)
 
 
@@ -2275,6 +2387,14 @@ class Prover:
         terms listed per relation, chips = the chip indices to audit (default: all); a ProductReport back."""
         opts = _product_opts(max_entries, max_rows_per_entry, max_terms, chips)
         return self._audit("product", main, preprocessed, opts)
+
+    def domain_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, chips=None, max_bits=16, lookup_buses=None):
+        """Which set of values this witness puts into every main column, and on which rows a narrow (byte or half-word valued) column is not a
+        field of a live send to a lookup table (vgpu_domain_audit); the arguments of prove, chips = the chip indices to audit (default: all),
+        max_bits = a column is narrow below 2^max_bits, lookup_buses = None (the structural rule) or the buses that count as lookup tables; a
+        DomainReport back."""
+        opts = _domain_opts(max_entries, max_rows_per_entry, chips, max_bits, lookup_buses)
+        return self._audit("domain", main, preprocessed, opts)
 
     def transition_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, min_gate_windows=64, max_gates=256, chips=None):
         """Which affine-linear relations between a row and its successor this witness keeps, on every window or under a boolean gate, and at

@@ -35,6 +35,7 @@ SOURCES = [
     "kernels/invariant_audit.hip",
     "kernels/transition_audit.hip",
     "kernels/product_audit.hip",
+    "kernels/domain_audit.hip",
     "kernels/field_probe.hip",
     "host/prover.cpp",
     "host/prover_audits.cpp",

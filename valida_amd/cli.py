@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--products] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--products] [--domains] [--max-bits N] [--lookup-buses B[,B..]] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -106,6 +106,15 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         missing constraint (a forgotten b^2 = b, s t = 0, s x = y) or a column this program never exercises.  Single products only (s a - s b
         = 0 is found only when s a and s b are each affine), within one row, on THIS witness (a short program has accidental relations), first
         order with the rank audit's caveats: the exit status does not depend on this flag.
+        --domains adds the domain audit of the same witness (vgpu_domain_audit: per chip and main column the set of values the witness puts
+        there — min, max, the exact number of distinct values below 2^16, a class from constant to wide — and the rows on which a narrow
+        column, byte or half-word valued below 2^N for --max-bits N (default 16), is not a bare field of a live send to a lookup table), on
+        the same path (device or --host), restricted by the same --chips.  A lookup table is a bus all of whose receivers are chips without
+        constraints and sends (on the BasicMachine the memory and the range bus); --lookup-buses=3 or =g3,l0 names them instead (g: global,
+        l: local).  The JSON report gets one more key, "domains" (DomainReport.to_json's object); stdout gets one line per chip that has an
+        entry, `add: 4 narrow columns unguarded (columns 2-3,6-7: byte-valued on up to 103 rows, on no lookup send)`.  A candidate missing
+        range check, on THIS witness (a short program leaves columns accidentally narrow) and for bare fields only (a send of 256 a + b guards
+        neither column): never changes the exit status.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
 Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
@@ -374,6 +383,49 @@ def product_lines(report):
     return lines
 
 
+def _column_ranges(cols):
+    """[2, 3, 6, 7] as "2-3,6-7"."""
+    out, k = [], 0
+    while k < len(cols):
+        j = k
+        while j + 1 < len(cols) and cols[j + 1] == cols[j] + 1:
+            j += 1
+        out.append("%d" % cols[k] if j == k else "%d-%d" % (cols[k], cols[j]))
+        k = j + 1
+    return ",".join(out)
+
+
+def domain_lines(report):
+    """One line per chip of a domain report that has an entry: its narrow columns with a non-zero cell on a row that no lookup send guards."""
+    import valida_amd as va
+
+    lines = []
+    for c in report.chips:
+        mine = [e for e in report.entries if e["chip"] == c["chip"]]
+        if not mine:
+            continue
+        name = va.CHIP_NAMES[c["chip"]] if c["chip"] < len(va.CHIP_NAMES) else "chip %d" % c["chip"]
+        cols = report.columns(c["chip"])
+        never = all(cols[e["column"]]["guarded_rows"] == 0 for e in mine)
+        lines.append("%s: %d narrow column%s unguarded (column%s %s: %s-valued on up to %d rows, %s)" % (
+            name, c["entries"], "" if c["entries"] == 1 else "s", "" if c["entries"] == 1 else "s", _column_ranges([e["column"] for e in mine]) + (",.." if len(mine) < c["entries"] else ""),
+            "half" if any(e["cls"] == "half" for e in mine) else "byte", max(e["unguarded_nonzero_rows"] for e in mine),
+            "on no lookup send" if never else "lookup sends miss these rows"))
+    return lines
+
+
+def parse_lookup_buses(text):
+    """--lookup-buses: None (the structural rule) or [(is_global, bus_index)] from 3 / g3 / l0, comma-separated."""
+    if not text:
+        return None
+    out = []
+    for t in text.split(","):
+        t = t.strip()
+        is_global = not t.startswith("l")
+        out.append((is_global, int(t.lstrip("gl"))))
+    return out
+
+
 def field_lines(report):
     """One line per (chip, interaction) of a field report with a floating field: the bus, the fields, the most rows one of them floats on."""
     import valida_amd as va
@@ -485,10 +537,15 @@ def main(argv=None):
     ap.add_argument("--products", action="store_true", help="check: also the product audit (the products of two independent columns that are an affine function of the row "
                     "on every row of this witness — b^2 = b, s t = 0, s t = s, s x = y, a b = c — and on how many rows the chip's own constraints and bus records enforce each: "
                     "never enforced = a candidate missing constraint; single products, one row, this witness, first order; never changes the exit status)")
+    ap.add_argument("--domains", action="store_true", help="check: also the domain audit (per main column the set of values this witness puts there, and the narrow — byte or "
+                    "half-word valued — columns with a non-zero cell on a row where no live bare send to a lookup table guards them: a candidate missing range check; this witness, bare "
+                    "fields only; never changes the exit status)")
+    ap.add_argument("--max-bits", type=int, default=16, help="check --domains: a column is narrow when its largest value is below 2^N (1 to 16, default 16)")
+    ap.add_argument("--lookup-buses", default="", help="check --domains: the buses that count as lookup tables instead of the structural rule, comma-separated (3 or g3: global bus 3, l0: local bus 0)")
     ap.add_argument("--min-gate-windows", type=int, default=64, help="check --transitions: a gate that holds on fewer windows is counted but not audited (default 64)")
     ap.add_argument("--max-gates", type=int, default=256, help="check --transitions: the gates listed per chip, the ungated one included (default 256)")
     ap.add_argument("--step-sizes", default="1,-1,2", help="check --steps: 1 to 4 distinct step sizes, comma-separated integers mod p (as --step-sizes=1,-1,2)")
-    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields / --steps / --invariants / --transitions / --products: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
+    ap.add_argument("--chips", default="", help="check --pairs / --rank / --fields / --steps / --invariants / --transitions / --products / --domains: audit only these chips, comma-separated names or indices (as --chips=cpu,add)")
     _config_flags(ap)
     args = ap.parse_args(argv)
 
@@ -527,6 +584,8 @@ def main(argv=None):
                 treport = va.transition_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_terms=256, min_gate_windows=args.min_gate_windows, max_gates=args.max_gates,
                                                    chips=parse_chips(args.chips)) if args.transitions else None
                 qreport = va.product_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.products else None
+                dreport = va.domain_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips), max_bits=args.max_bits,
+                                               lookup_buses=parse_lookup_buses(args.lookup_buses)) if args.domains else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -544,6 +603,7 @@ def main(argv=None):
                 ireport = prover.invariant_audit(main, prep, max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.invariants else None
                 treport = prover.transition_audit(main, prep, max_terms=256, min_gate_windows=args.min_gate_windows, max_gates=args.max_gates, chips=parse_chips(args.chips)) if args.transitions else None
                 qreport = prover.product_audit(main, prep, max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.products else None
+                dreport = prover.domain_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips), max_bits=args.max_bits, lookup_buses=parse_lookup_buses(args.lookup_buses)) if args.domains else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -567,6 +627,8 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), transitions=treport.to_dict()))
             if qreport is not None:
                 text = json.dumps(dict(json.loads(text), products=qreport.to_dict()))
+            if dreport is not None:
+                text = json.dumps(dict(json.loads(text), domains=dreport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
@@ -574,7 +636,7 @@ def main(argv=None):
                     rank_lines(rreport) if rreport is not None else []) + (field_lines(freport) if freport is not None else []) + (
                     link_lines(lreport) if lreport is not None else []) + (step_lines(sreport) if sreport is not None else []) + (
                     invariant_lines(ireport) if ireport is not None else []) + (transition_lines(treport) if treport is not None else []) + (
-                    product_lines(qreport) if qreport is not None else []):
+                    product_lines(qreport) if qreport is not None else []) + (domain_lines(dreport) if dreport is not None else []):
                 print(line)
             return 0 if report.balanced and (creport is None or creport.satisfied) else 1
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256

@@ -80,6 +80,7 @@ struct vgpu_step_report : audit_report {};
 struct vgpu_invariant_report : audit_report {};
 struct vgpu_transition_report : audit_report {};
 struct vgpu_product_report : audit_report {};
+struct vgpu_domain_report : audit_report {};
 struct vgpu_comm { std::shared_ptr<Prover> owner; std::unique_ptr<Comm> comm; };  // owner first: the communicator dies before its context
 static_assert(sizeof(vgpu_cpu_op_t) == sizeof(vk::TgCpuOp) && sizeof(vgpu_mem_op_t) == sizeof(vk::TgMemOp) && sizeof(vgpu_alu_op_t) == sizeof(vk::TgAluOp),
               "C ABI log records and their device images must match");
@@ -1233,6 +1234,32 @@ uint64_t vgpu_product_report_len(const vgpu_product_report_t* r) { return report
 const uint32_t* vgpu_product_report_words(const vgpu_product_report_t* r) { return report_words(r); }
 void vgpu_product_report_timing(const vgpu_product_report_t* r, double out[3]) { report_timing(r, out, 3); }
 void vgpu_product_report_free(vgpu_product_report_t* r) { delete r; }
+
+// ---- domain audit (host/domain_audit.hpp) ----
+static_assert(sizeof(vgpu_domain_audit_opts_t) == 48, "vgpu_domain_audit_opts_t has no padding");
+static DomainAuditOpts domain_opts(const vgpu_domain_audit_opts_t* o) {
+    DomainAuditOpts r;  // a null pointer: the defaults; a struct is taken as given (max_bits 0: 16)
+    if (o) {
+        r.max_entries = o->max_entries; r.max_rows_per_entry = o->max_rows_per_entry; r.chip_mask = o->chip_mask; r.max_bits = o->max_bits;
+        r.lookup_auto = o->lookup_auto; r.lookup_global_mask = o->lookup_global_mask; r.lookup_local_mask = o->lookup_local_mask;
+        for (uint32_t i = 0; i < 2; i++) r.reserved[i] = o->reserved[i];
+    }
+    return r;
+}
+int32_t vgpu_domain_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                          uint32_t n_prep, const vgpu_domain_audit_opts_t* opts, vgpu_domain_report_t** out) {
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->domain_audit(m, pr, domain_opts(opts)); });
+}
+int32_t vgpu_domain_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                               const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                               const vgpu_domain_audit_opts_t* opts, vgpu_domain_report_t** out) {
+    return audit_on_host<ConstraintHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                               [&](auto&... a) { return domain_audit_host(a..., domain_opts(opts)); });
+}
+uint64_t vgpu_domain_report_len(const vgpu_domain_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_domain_report_words(const vgpu_domain_report_t* r) { return report_words(r); }
+void vgpu_domain_report_timing(const vgpu_domain_report_t* r, double out[3]) { report_timing(r, out, 3); }
+void vgpu_domain_report_free(vgpu_domain_report_t* r) { delete r; }
 
 // ---- coverage audit (host/coverage_audit.hpp) ----
 static_assert(sizeof(vgpu_coverage_audit_opts_t) == 40, "vgpu_coverage_audit_opts_t has no padding");

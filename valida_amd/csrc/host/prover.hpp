@@ -19,6 +19,7 @@
 #include "invariant_audit.hpp"
 #include "transition_audit.hpp"
 #include "product_audit.hpp"
+#include "domain_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -174,6 +175,10 @@ class Prover {
     // function of the row on every row (the invariant audit's pivots, the first-independent rows, an inverse, a pruned sweep over rows x pairs) and,
     // per relation, the rows on which the rank audit's Jacobian enforces it; queued on the context like the other audits, scratch from the pool.
     ProductReport product_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const ProductAuditOpts& opts);
+    // Domain audit of a witness (host/domain_audit.hpp, kernels/domain_audit.hip): per main column the set of values the witness puts there (one
+    // streaming scan per virtual column into an LDS bitmap) and the rows on which a narrow column is not a field of a live send to a lookup table;
+    // queued on the context like the other audits, scratch from the pool.
+    DomainReport domain_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const DomainAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

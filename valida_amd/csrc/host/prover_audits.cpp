@@ -1041,6 +1041,146 @@ ProductReport Prover::product_audit(const std::vector<const DeviceTrace*>& main,
     return rep;
 }
 
+// ---- domain audit (host/domain_audit.hpp; kernels/domain_audit.hip) ------------------------------------------------------------------------
+DomainReport Prover::domain_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const DomainAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const DomainAuditOpts o = domain_audit_checked_opts(opts_in, machine_.airs.size());
+    const auto tr = audit_traces<ConstraintShape>("domain_audit", main, preprocessed);
+    const DomainPlan plan = domain_audit_plan(machine_, tr.ms, tr.prep_chips, tr.ps, o);
+    const size_t NC = machine_.airs.size();
+    const uint32_t R = o.max_rows_per_entry;
+    DomainReport rep;
+    domain_audit_blocks(rep, machine_, plan, tr.ms, o);
+    std::vector<uint32_t> slot0;
+    const uint32_t n_slots = domain_audit_slots(machine_, plan, o, slot0);
+    // per chip its launch shape and tables: a chip whose guard table does not fit the LDS is refused before anything is queued
+    std::vector<vk::DaArgs> args(NC);
+    std::vector<uint32_t> desc_words;
+    std::vector<uint64_t> vt_at(NC, 0), gt_at(NC, 0);
+    for (size_t i = 0; i < NC; i++) {
+        const AirDesc& air = machine_.airs[i];
+        vk::DaArgs& a = args[i];
+        a = vk::DaArgs{};
+        a.n = main[i]->height; a.width = air.width; a.prep_width = air.prep_width;
+        vk::da_shape(a);
+        const bool audited = rep.chips[i].audited && air.width;
+        const std::vector<uint32_t> vt = domain_audit_vt(air, plan.chips[i], audited, slot0[i]);
+        a.NV = (uint32_t)(vt.size() / 4);
+        vt_at[i] = desc_words.size();
+        desc_words.insert(desc_words.end(), vt.begin(), vt.end());
+        rep.evaluations += (double)a.n * a.NV;
+        rep.evaluations += (double)a.n * air.interactions.size();  // the counts
+        if (!audited) { a.width = 0; continue; }
+        const std::vector<uint32_t> gt = domain_audit_gt(air, plan.chips[i]);
+        a.GW = (uint32_t)gt.size(); a.A = (uint32_t)plan.chips[i].apps.size(); a.slot0 = slot0[i];
+        gt_at[i] = desc_words.size();
+        desc_words.insert(desc_words.end(), gt.begin(), gt.end());
+        if (vk::da_guard_lds_words(a) + 4 * 66 > vk::DA_GUARD_LDS_WORDS)
+            throw std::invalid_argument("domain_audit: the guard table of chip " + air.name + " (" + std::to_string(a.GW) + " words for " + std::to_string(plan.chips[i].items.size()) +
+                                        " items, " + std::to_string(5 * (size_t)air.width + a.A) + " counters) does not fit 64 KB of LDS [the host audit has no limit]");
+    }
+
+    DeviceCtx& c = *ctx_;
+    AuditPass pass(c, main.size() + preprocessed.size());
+    const hipStream_t st = pass.stream;
+
+    uint64_t scratch_words = 0, rows_words = 0;
+    audit_or_no_memory(st, [&] {
+        for (size_t i = 0; i < NC; i++) {
+            vk::DaArgs& a = args[i];
+            if (!a.NV && !a.width) continue;  // neither a column nor a field: the chip is not read
+            const vk::DMatView v = pass.working(main[i]);
+            a.main = v.data; a.mstride = v.stride;
+            if (const DeviceTrace* p = audit_prep(preprocessed, plan.prep_slot, i)) { const vk::DMatView pv = pass.working(p); a.prep = pv.data; a.pstride = pv.stride; }
+            a.iw = iw_dev_[i].data;
+        }
+        if (desc_words.empty()) desc_words.push_back(0);
+        DBuf desc(&c, desc_words);
+        for (size_t i = 0; i < NC; i++) { args[i].vt = desc.data + vt_at[i]; args[i].gt = desc.data + gt_at[i]; }
+        c.check_launch("domain_audit ingest");
+        // the scratch (u32 words), all of it zeroed by one memset: tot [slots][5] u64, cls [slots][8], bitmaps [slots][2048], per audited chip
+        // gtot [5 w + A] u64 and table [w][NB]; behind them the prefix tables, which the scan writes whole
+        const uint64_t tot_at = 0, cls_at = tot_at + 2ull * vk::DA_TOT * n_slots, bm_at = cls_at + (uint64_t)vk::DA_CLS * n_slots;
+        AuditScratch sc(NC);
+        sc.zeroed = bm_at + (uint64_t)vk::DA_BITMAP_WORDS * n_slots;
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].width) sc.add(i, 2 * (5ull * args[i].width + args[i].A), (uint64_t)args[i].width * args[i].NB);
+        scratch_words = sc.place_prefixes();
+        DBuf scratch(&c, (size_t)(scratch_words ? scratch_words : 1));
+        unsigned long long* tot = reinterpret_cast<unsigned long long*>(scratch.data + tot_at);
+        uint32_t* cls = scratch.data + cls_at;
+        pass.begin();
+        if (sc.zeroed) VG_HIP_CHECK(hipMemsetAsync(scratch.data, 0, (size_t)sc.zeroed * 4, st));
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].NV) vk::launch_da_scan(st, args[i], tot, scratch.data + bm_at);
+        vk::launch_da_classify(st, tot, scratch.data + bm_at, cls, n_slots, o.max_bits);
+        for (size_t i = 0; i < NC; i++)
+            if (args[i].width) vk::launch_da_guard(st, args[i], vk::MA_COUNT, cls, reinterpret_cast<unsigned long long*>(scratch.data + sc.tot_at[i]), scratch.data + sc.tab_at[i], nullptr, 0, 0, nullptr);
+        c.check_launch("domain_audit count");
+        // tot and cls lie in front: one download; then the guard totals of each audited chip
+        std::vector<uint32_t> tw((size_t)bm_at ? (size_t)bm_at : 1);
+        if (bm_at) c.download_small(tw.data(), scratch.data, (size_t)bm_at * 4);
+        auto total = [&](uint32_t s, uint32_t k) { return audit_u64(tw, (size_t)s * vk::DA_TOT + k); };
+        for (uint32_t p = 0; p < plan.n_positions; p++) {
+            if (!total(p, 4)) continue;
+            const uint32_t* k = tw.data() + cls_at + (size_t)p * vk::DA_CLS;
+            DomainPosition& dp = rep.positions[p];
+            dp.min = k[5]; dp.max = k[6]; dp.distinct = k[0]; dp.wide = total(p, 3); dp.records = total(p, 4);
+        }
+        std::vector<uint32_t> gw;
+        for (size_t i = 0; i < NC; i++) {
+            if (!args[i].width) continue;
+            DomainChipStat& cs = rep.chips[i];
+            const uint32_t W = args[i].width;
+            gw.resize(2 * (5 * (size_t)W + args[i].A));
+            c.download_small(gw.data(), scratch.data + sc.tot_at[i], gw.size() * 4);
+            for (uint32_t col = 0; col < W; col++) {
+                const uint32_t s = slot0[i] + col;
+                const uint32_t* k = tw.data() + cls_at + (size_t)s * vk::DA_CLS;
+                DomainColumn& dc = cs.cols[col];
+                dc.distinct = k[0]; dc.cls = k[1]; dc.dense = k[2]; dc.bits = k[3]; dc.narrow = k[4]; dc.min = k[5]; dc.max = k[6];
+                dc.nonzero = total(s, 2); dc.wide = total(s, 3);
+                dc.guarded = audit_u64(gw, 5 * (size_t)col); dc.sent = audit_u64(gw, 5 * (size_t)col + 1); dc.received = audit_u64(gw, 5 * (size_t)col + 2);
+                dc.mixed = audit_u64(gw, 5 * (size_t)col + 3);
+                dc.unguarded = args[i].n - dc.guarded;
+                // a column without items that is not narrow is not walked by the guard pass: none of its rows is guarded
+                const bool walked = dc.narrow || plan.chips[i].item_at[col] != plan.chips[i].item_at[col + 1];
+                dc.unguarded_nonzero = walked ? audit_u64(gw, 5 * (size_t)col + 4) : dc.nonzero;
+            }
+            for (uint32_t k = 0; k < args[i].A; k++) cs.app_live[k] = audit_u64(gw, 5 * (size_t)W + k);
+        }
+        domain_audit_entries(rep, plan, o);
+        if (R) {
+            audit_chip_runs(rep.entries, [&](uint32_t, size_t, size_t e1) { rows_words = std::max<uint64_t>(rows_words, ((uint64_t)rep.entries[e1 - 1].column + 1) * R * 2); });
+            DBuf out(&c, (size_t)(rows_words ? rows_words : 1));
+            audit_chip_runs(rep.entries, [&](uint32_t chip, size_t e0, size_t e1) {
+                // the listed columns of one chip: scan, list, one download
+                const vk::DaArgs& a = args[chip];
+                const uint32_t c_cut = rep.entries[e1 - 1].column + 1;  // entries ascend: the listed columns of a chip are below it
+                const size_t words = (size_t)c_cut * R * 2;
+                vk::launch_ra_scan(st, vk::da_scan_args(a), scratch.data + sc.tab_at[chip], scratch.data + sc.pre_at[chip], c_cut);
+                vk::launch_da_guard(st, a, vk::MA_LIST, cls, nullptr, scratch.data + sc.tab_at[chip], scratch.data + sc.pre_at[chip], c_cut, R, out.data);
+                c.check_launch("domain_audit list");
+                std::vector<uint32_t> w(words);
+                c.download_small(w.data(), out.data, w.size() * 4);
+                for (size_t e = e0; e < e1; e++) {
+                    DomainEntry& en = rep.entries[e];
+                    const uint64_t listed = std::min<uint64_t>(en.unguarded_nonzero, R);
+                    en.rows.assign(w.begin() + (size_t)en.column * R * 2, w.begin() + (size_t)en.column * R * 2 + (size_t)listed * 2);
+                }
+            });
+        }
+        pass.end(rep);
+    }, [&] {
+        return std::string("domain_audit: the device pool cannot give the pass its scratch: per slot (" + std::to_string(n_slots) + ": the main columns of the audited chips and " +
+                           std::to_string(plan.n_positions) + " bus positions) 8192 bytes of bitmap, 40 of totals and 32 of classes, per audited chip 40 bytes per column, 8 per appearance and 8 per "
+                           "(column, workgroup of 256 rows) (" + std::to_string(scratch_words * 4) + " bytes for this witness), " + std::to_string(rows_words * 4) +
+                           " bytes of listed rows (8 per (listed column, row slot)), plus the working-layout copies of uploaded traces; chip_mask audits fewer chips at a time");
+    });
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 // ---- transition audit (host/transition_audit.hpp; kernels/transition_audit.hip) --------------------------------------------------------------
 TransitionReport Prover::transition_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const TransitionAuditOpts& opts_in) {
     const auto t_host = Clock::now();

@@ -409,6 +409,39 @@ void pq_shape(PqArgs& a);  // ra_shape for this audit's LDS with a.E relations i
 size_t pq_lds_bytes(const PqArgs& a, uint32_t NW, uint32_t T);
 void launch_pq_count(hipStream_t st, const PqArgs& a, unsigned long long* totals, uint32_t* table);
 void launch_pq_list(hipStream_t st, const PqArgs& a, const uint32_t* table, const uint32_t* prefix, uint32_t i_cut, uint32_t R, uint32_t* rows);
+// domain_audit.hip — the passes of the domain audit (host/domain_audit.hpp: contract; Prover::domain_audit drives them), per chip.  A SLOT is a
+// main column of an audited chip or a bus position record; a VIRTUAL COLUMN of a chip is a main column or an (interaction, field) gated by the
+// interaction's count.  vt [NV][4]: kind (0 main column, 1 field), the main column or the word offset of the field vcol in iw, the word offset of
+// the count vcol in iw, the slot.  tot [slots][5] u64: ~min, max, non-zero, wide, live (zeroed); bitmaps [slots][2048] u32 (zeroed); cls
+// [slots][8] u32: distinct, class, dense, bits, narrow, min, max, 0.  Guard: gt = [0] items I, [1] W, item_at [W + 1], then per item (ascending
+// column) the word offset of its interaction's count vcol in iw, its kind (host/domain_audit.hpp: DM_*), its appearance or ~0; gtot [5 W + A] u64:
+// per column guarded, sent, received, mixed, unguarded non-zero rows, then per appearance its live rows (zeroed); table / prefix [W][NB] u32 the
+// unguarded non-zero rows of a narrow column per workgroup and their exclusive prefix (table zeroed; the scan is launch_ra_scan over
+// da_scan_args); rows [c_cut][R][2] u32 (row, canonical value).
+constexpr uint32_t DA_TILE = 256, DA_MAX_SLICES = 2048, DA_BITMAP_WORDS = 2048, DA_TOT = 5, DA_CLS = 8, DA_GUARD_LDS_WORDS = 16 * 1024;
+struct DaArgs {
+    const uint32_t* main;  // column-major working layout (Montgomery), natural row order
+    uint64_t mstride;
+    const uint32_t* prep;  // null for a chip without preprocessed columns
+    uint64_t pstride;
+    uint64_t n;            // height, a power of two
+    uint32_t width, prep_width;
+    const uint32_t* iw;    // the chip's interactions (interactions.hpp: encode_interactions)
+    const uint32_t* vt;
+    uint32_t NV;           // virtual columns scanned = gridDim.y
+    uint32_t TPS, S;       // da_shape: tiles of DA_TILE rows per slice, slices = gridDim.x
+    const uint32_t* gt;
+    uint32_t GW, A;        // words of gt; appearances
+    uint32_t slot0;        // the slot of main column 0 (an audited chip's main columns have consecutive slots)
+    uint32_t NB;           // workgroups of the guard pass = ceil(n / DA_TILE)
+};
+void da_shape(DaArgs& a, uint32_t max_slices = DA_MAX_SLICES);  // TPS, S, NB from the height
+inline uint64_t da_guard_lds_words(const DaArgs& a) { return (uint64_t)a.GW + 5ull * a.width + a.A + 16; }
+RaArgs da_scan_args(const DaArgs& a);  // what launch_ra_scan takes for table rows of NB words
+void launch_da_scan(hipStream_t st, const DaArgs& a, unsigned long long* tot, uint32_t* bitmaps);
+void launch_da_classify(hipStream_t st, const unsigned long long* tot, const uint32_t* bitmaps, uint32_t* cls, uint32_t n_slots, uint32_t max_bits);
+void launch_da_guard(hipStream_t st, const DaArgs& a, uint32_t mode, const uint32_t* cls, unsigned long long* gtot, uint32_t* table, const uint32_t* prefix, uint32_t c_cut, uint32_t R,
+                     uint32_t* rows);
 // field_audit.hip — the passes of the field audit (host/field_audit.hpp: contract; Prover::field_audit drives them), per chip.  One wave per
 // trace row, one wave per workgroup, T rows per workgroup one after the other, NB workgroups.  A SLOT of a chip is (interaction, field) in
 // order, NS of them.  totals: u64 [0] live records, [1] floating fields, [2] rows with a floating field, [3 + m] live rows of interaction m,
