@@ -1050,6 +1050,76 @@ const uint32_t* vgpu_domain_report_words(const vgpu_domain_report_t* r);
 void vgpu_domain_report_timing(const vgpu_domain_report_t* r, double out[3]);
 void vgpu_domain_report_free(vgpu_domain_report_t* r);
 
+/* ---- Memory audit: the audits above judge a witness by bus balance and by local algebra.  None asks whether the memory table IS a memory: the
+ * reference's memory AIR is commented out (memory/src/stark.rs:22-78), so nothing requires a read to return the last value written to its
+ * address, and a wrong value planted consistently in the sender's channel and the table's row passes every one of them.  This audit replays
+ * the receives of one bus as a memory and names the records that break it.  Inputs: exactly what vgpu_prove and the audits take.
+ *   bus       global bus 2 (the BasicMachine's memory bus) by default; bus_is_global / bus_index name another.  Every RECEIVE on it is read
+ *             through its vcols and must have exactly 8 fields (is_read, clk, addr, is_static_initial, v0, v1, v2, v3), the shape of
+ *             memory/src/lib.rs:216-233.  Another field count, a bus without a receive, more than 2^32 - 2 slots: VGPU_ERR_INVALID_ARG, the
+ *             message names the reason.
+ *   records   a SLOT is (chip, receive, row), LIVE iff its count vcol != 0 at the row; values canonical.  A live record is a READ iff
+ *             is_read == 1, otherwise a WRITE; STATIC iff is_static_initial == 1.
+ *   order     live records by (addr, clk, static before non-static, seq), seq = lexicographic (chip, row, interaction): the key
+ *             addr << 32 | clk << 1 | !static and a stable sort of the slots enumerated in seq order.  Inside one (addr, clk) the bus record
+ *             carries no ordinal: the trace's own order decides, as the reference's stable sort of the clk-ordered log leaves it;
+ *             same_cycle_pairs counts the verdicts that rest on that.
+ *   state     per address the last WRITE before a record in that order, or none; a read leaves it unchanged; an address nobody has written
+ *             reads as 0 (read_or_init, memory/src/lib.rs:107-120).
+ *   findings  at most one kind per live record, the lowest applicable: 1 MALFORMED with a reason mask (bit 0 count != 1, bit 1 is_read not in
+ *             {0, 1}, bit 2 is_static not in {0, 1}, bit 3 static with is_read == 1 or clk != 0, bit 4 a value field >= 256; the record still
+ *             takes its place in the order and acts as a write or read by the rule above), 2 DUPLICATE_STATIC (a static record whose
+ *             predecessor in the order is a static record of the same address), 3 STALE_READ (a read with a last write whose four value
+ *             fields differ from the read's, compared as field elements), 4 UNINIT_READ (a read with no write before it and a non-zero
+ *             value).  A tampered read is one finding; a tampered write one per read that follows it before the next write.
+ *   counters  exact: live, reads, writes, statics, addresses (distinct), min_addr, max_addr, max_clk, uninit_zero_reads (a read with no write
+ *             before it and value 0: counted, never a finding), same_cycle_pairs (positions whose predecessor has the same (addr, clk), both
+ *             non-static, at least one a write), max_clk_gap (between successive records of one address), dummy_reads_clk (over successive
+ *             same-address pairs with gap > L the sum of gap / L), dummy_reads_addr (over successive different addresses with difference > L
+ *             the sum of diff / L), L = live: what insert_dummy_reads (memory/src/lib.rs:286-362) would add, static records counted as
+ *             operations at clk 0; layout_descents (rows r with rows r and r + 1 of one chip and receive both live and key(r) > key(r + 1))
+ *             and the first such (chip, row): whether an adjacent-row AIR could hold on the trace as laid out; one count per kind.
+ *   list      the first max_findings findings in ascending order position (default 64, at most 2^20; in a struct taken as given: 0 lists
+ *             nothing and every count stays exact).  reserved must be zero.  A null options pointer gives the defaults.
+ * What it is not: it judges the table's receives only (whether the senders agree is the bus audit's question) and THIS witness only; same-cycle
+ * order is the trace's, not proven; addresses are field elements, so two u32 addresses p apart are one address here, as in the proof; it says
+ * nothing about a continuation's initial memory.
+ * vgpu_memory_audit runs on the device (kernels/memory_audit.hip), queued on the prover context, wave64, workgroups of 256: k_mm_keys (a
+ * thread per row, one descriptor walk per receive; key and id per slot, per workgroup the live count, the OR of the live keys and of their
+ * complements and the layout descents from an LDS tile with one halo row), the bus audit's radix sort over the key bytes in which some live
+ * key differs, k_mm_gather (order position -> packed record and a mark: position + 1 for a write or the first record of an address), an
+ * exclusive max-scan of the marks (the last write), k_mm_judge (kind, reason, counters by ballots, LDS, one atomic per counter and workgroup;
+ * findings by count -> scan -> list).  The only atomics are integer add, or and max: every word is the same run after run.  Scratch from the
+ * pool, its totals zeroed by one memset; VGPU_ERR_OOM with the arithmetic when the pool cannot give it.  vgpu_memory_audit_host: the same
+ * contract on the host, one thread, std::stable_sort, no limits.
+ * Report image (vgpu_memory_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x314d4d56 "VMM1" [1] word count [2] bus_is_global [3] bus_index [4] receives [5] truncated [6] listed [7] max_findings [8,9] slots
+ *   [10,11] live [12,13] reads [14,15] writes [16,17] statics [18,19] addresses [20] min_addr [21] max_addr [22] max_clk [23] max_clk_gap
+ *   [24,25] uninit_zero_reads [26,27] same_cycle_pairs [28,29] dummy_reads_clk [30,31] dummy_reads_addr [32,33] layout_descents [34] chip and
+ *   [35] row of the first descent (all ones: none) [36,37] findings [38,39] malformed [40,41] duplicate_static [42,43] stale_read [44,45]
+ *   uninit_read [46,47] 0; without a live record [20 .. 23] are 0
+ *   per receive, seq order, 2 words: chip, interaction
+ *   per listed finding 20 words: [0] kind [1] reason [2] chip [3] interaction [4] row [5] addr [6] clk [7..10] value [11..14] expected (the
+ *   last write's value, 0 when there is none) [15] chip [16] interaction [17] row of the last write (all ones: none) [18] order position [19] 0 */
+typedef struct vgpu_memory_audit_opts {
+    uint32_t max_findings;
+    uint32_t bus_is_global;
+    uint32_t bus_index;
+    uint32_t reserved;
+} vgpu_memory_audit_opts_t;
+typedef struct vgpu_memory_report vgpu_memory_report_t;
+int32_t vgpu_memory_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                          uint32_t n_prep, const vgpu_memory_audit_opts_t* opts, vgpu_memory_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_memory_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                               const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                               const vgpu_memory_audit_opts_t* opts, vgpu_memory_report_t** out);
+uint64_t vgpu_memory_report_len(const vgpu_memory_report_t* r);
+const uint32_t* vgpu_memory_report_words(const vgpu_memory_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: slots evaluated */
+void vgpu_memory_report_timing(const vgpu_memory_report_t* r, double out[3]);
+void vgpu_memory_report_free(vgpu_memory_report_t* r);
+
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
  *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct

@@ -1730,6 +1730,85 @@ def domain_audit_host(machine, main_matrices, preprocessed, max_entries=1024, ma
     return _audit_host("domain", machine, main_matrices, preprocessed, opts)
 
 
+class MemoryAuditOpts(ctypes.Structure):  # vgpu_memory_audit_opts_t
+    _fields_ = [("max_findings", ctypes.c_uint32), ("bus_is_global", ctypes.c_uint32), ("bus_index", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+MEMORY_KINDS = ("malformed", "duplicate_static", "stale_read", "uninit_read")
+MEMORY_COUNTERS = ("slots", "live", "reads", "writes", "statics", "addresses", "min_addr", "max_addr", "max_clk", "max_clk_gap", "uninit_zero_reads", "same_cycle_pairs", "dummy_reads_clk",
+                   "dummy_reads_addr", "layout_descents", "findings") + MEMORY_KINDS
+
+
+class MemoryReport(_AuditReport):
+    """The memory audit of a witness (vgpu_memory_audit / vgpu_memory_audit_host; the contract is stated in include/vgpu.h), as plain Python
+    values: words (the image), bus = (is_global, bus_index), max_findings, truncated, receives = [(chip, interaction)],
+    counters = dict(slots, live, reads, writes, statics, addresses, min_addr, max_addr, max_clk, max_clk_gap, uninit_zero_reads, same_cycle_pairs,
+    dummy_reads_clk, dummy_reads_addr, layout_descents, findings, malformed, duplicate_static, stale_read, uninit_read),
+    first_descent = (chip, row) of the first layout descent or None,
+    findings = [dict(kind ("malformed" / "duplicate_static" / "stale_read" / "uninit_read"), reason, chip, interaction, row, addr, clk, value,
+    expected, last_write = (chip, interaction, row) or None, position)] in ascending order position,
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (slots evaluated).
+    It judges the table's receives of THIS witness; whether the senders agree is the bus audit's question."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 48 or w[0] != 0x314d4d56 or w[1] != len(w):
+            raise ValueError("not a memory report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        self.bus = (bool(w[2]), w[3])
+        self.truncated, self.max_findings = bool(w[5]), w[7]
+        self.counters = dict(slots=u64(8), live=u64(10), reads=u64(12), writes=u64(14), statics=u64(16), addresses=u64(18), min_addr=w[20], max_addr=w[21], max_clk=w[22], max_clk_gap=w[23],
+                             uninit_zero_reads=u64(24), same_cycle_pairs=u64(26), dummy_reads_clk=u64(28), dummy_reads_addr=u64(30), layout_descents=u64(32), findings=u64(36),
+                             malformed=u64(38), duplicate_static=u64(40), stale_read=u64(42), uninit_read=u64(44))
+        self.first_descent = None if w[34] == 0xFFFFFFFF else (w[34], w[35])
+        pos = 48
+        self.receives = [(w[pos + 2 * k], w[pos + 2 * k + 1]) for k in range(w[4])]
+        pos += 2 * w[4]
+        self.findings = []
+        for _ in range(w[6]):
+            f = w[pos:pos + 20]
+            self.findings.append(dict(kind=MEMORY_KINDS[f[0] - 1], reason=f[1], chip=f[2], interaction=f[3], row=f[4], addr=f[5], clk=f[6], value=f[7:11], expected=f[11:15],
+                                      last_write=None if f[15] == 0xFFFFFFFF else (f[15], f[16], f[17]), position=f[18]))
+            pos += 20
+        assert pos == len(w)
+
+    @property
+    def total_findings(self):
+        return self.counters["findings"]
+
+    def to_dict(self):
+        return dict(words=[int(x) for x in self.words], bus=list(self.bus), max_findings=self.max_findings, truncated=self.truncated, receives=[list(r) for r in self.receives],
+                    counters=self.counters, first_descent=None if self.first_descent is None else list(self.first_descent),
+                    findings=[dict(f, last_write=None if f["last_write"] is None else list(f["last_write"])) for f in self.findings], device_ms=self.device_ms, host_ms=self.host_ms,
+                    evaluations=self.evaluations)
+
+    @classmethod
+    def from_dict(cls, d):
+        """The report of to_dict()'s object (a `check --memory` JSON report's "memory" key)."""
+        return cls(d["words"], d.get("device_ms", 0.0), d.get("host_ms", 0.0), d.get("evaluations", 0.0))
+
+
+def _memory_opts(max_findings, bus):
+    """bus: None (global bus 2, the BasicMachine's memory bus), a global bus index, or (is_global, bus_index)."""
+    if int(max_findings) < 0 or int(max_findings) >= 1 << 32:
+        raise VgpuError(-1, "memory_audit: max_findings must not be negative")
+    is_global, index = (True, 2) if bus is None else ((True, int(bus)) if isinstance(bus, (int, np.integer)) else (bool(bus[0]), int(bus[1])))
+    if index < 0 or index >= 1 << 32:
+        raise VgpuError(-1, "memory_audit: bus names a bus index")
+    return MemoryAuditOpts(int(max_findings), 1 if is_global else 0, index, 0)
+
+
+def memory_audit_host(machine, main_matrices, preprocessed, max_findings=64, bus=None):
+    """The memory audit on the HOST (vgpu_memory_audit_host: no device, one thread): main_matrices = one canonical matrix per chip,
+    preprocessed = [(chip index, matrix)], bus = None (global bus 2), a global bus index or (is_global, bus_index); a MemoryReport back."""
+    return _audit_host("memory", machine, main_matrices, preprocessed, _memory_opts(max_findings, bus))
+
+
 class TransitionAuditOpts(ctypes.Structure):  # vgpu_transition_audit_opts_t
     _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("max_terms", ctypes.c_uint32),
                 ("min_gate_windows", ctypes.c_uint32), ("max_gates", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
@@ -2152,7 +2231,7 @@ def coverage_audit_host(machine, main_matrices, preprocessed, deltas=None, max_c
     return _audit_host("coverage", machine, main_matrices, preprocessed, opts)
 
 
-_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, product=ProductReport, domain=DomainReport, field=FieldReport,
+_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, product=ProductReport, domain=DomainReport, memory=MemoryReport, field=FieldReport,
                       link=LinkReport, coverage=CoverageReport)
 
 
@@ -2395,6 +2474,12 @@ class Prover:
         DomainReport back."""
         opts = _domain_opts(max_entries, max_rows_per_entry, chips, max_bits, lookup_buses)
         return self._audit("domain", main, preprocessed, opts)
+
+    def memory_audit(self, main, preprocessed, max_findings=64, bus=None):
+        """Whether the receives of the memory bus of this witness are a memory: every read returns the last value written to its address
+        (vgpu_memory_audit); the arguments of prove, bus = None (global bus 2), a global bus index or (is_global, bus_index); a MemoryReport
+        back with the records that break it and the exact counters."""
+        return self._audit("memory", main, preprocessed, _memory_opts(max_findings, bus))
 
     def transition_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, min_gate_windows=64, max_gates=256, chips=None):
         """Which affine-linear relations between a row and its successor this witness keeps, on every window or under a boolean gate, and at

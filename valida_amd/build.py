@@ -36,6 +36,7 @@ SOURCES = [
     "kernels/transition_audit.hip",
     "kernels/product_audit.hip",
     "kernels/domain_audit.hip",
+    "kernels/memory_audit.hip",
     "kernels/field_probe.hip",
     "host/prover.cpp",
     "host/prover_audits.cpp",

@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--products] [--domains] [--max-bits N] [--lookup-buses B[,B..]] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--products] [--domains] [--max-bits N] [--lookup-buses B[,B..]] [--memory] [--max-findings N] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -115,9 +115,18 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         entry, `add: 4 narrow columns unguarded (columns 2-3,6-7: byte-valued on up to 103 rows, on no lookup send)`.  A candidate missing
         range check, on THIS witness (a short program leaves columns accidentally narrow) and for bare fields only (a send of 256 a + b guards
         neither column): never changes the exit status.
+        --memory adds the memory audit of the same witness (vgpu_memory_audit: the receives of the memory bus replayed as a memory — the live
+        records ordered by (addr, clk, static first, trace order), per address the last write — and the records that break it: a malformed
+        record, a duplicate static record, a read that does not return the last write to its address, a read of a non-zero value from an address
+        nobody wrote), on the same path (device or --host); --max-findings N lists the first N (default 64).  The JSON report gets one more
+        key, "memory" (MemoryReport.to_dict's object); stdout gets one line per finding kind present, `mem: 1 stale read (row 812, addr 4076,
+        clk 55: read 5, last write 3 at row 811)`, and one summary line with the counters: live records, addresses, same-cycle pairs (verdicts
+        that rest on the trace's own order), the largest clk gap, the dummy reads the reference's unfinished memory argument would need, and
+        whether the trace as laid out is sorted.  It judges the table's receives (whether the senders agree is the bus audit's question).
+        Findings are definite faults: with --memory, check exits 1 when there is one.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
-Exit status: 0 on success (run / prove done, proof accepted, witness balanced and, with --constraints, every constraint satisfied), 1 otherwise (the reference always exits 0)."""
+Exit status: 0 on success (run / prove done, proof accepted, witness balanced, with --constraints every constraint satisfied and with --memory no memory finding), 1 otherwise (the reference always exits 0)."""
 import argparse
 import json
 import sys
@@ -426,6 +435,53 @@ def parse_lookup_buses(text):
     return out
 
 
+def memory_value(v):
+    """The four value fields of a memory record as the number they spell when they are bytes (big-endian, as the VM's Word), else their list."""
+    return (v[0] << 24) | (v[1] << 16) | (v[2] << 8) | v[3] if all(x < 256 for x in v) else list(v)
+
+
+MEMORY_KIND_TEXT = {"malformed": "malformed record", "duplicate_static": "duplicate static record", "stale_read": "stale read", "uninit_read": "uninitialised read"}
+MEMORY_REASONS = ("count is not 1", "is_read is not 0 or 1", "is_static is not 0 or 1", "static with is_read or clk", "a value field is no byte")
+
+
+def memory_lines(report):
+    """One line per finding kind of a memory report (the count and the first listed record of the kind), then one summary line with the counters."""
+    import valida_amd as va
+
+    c, lines = report.counters, []
+    name = va.CHIP_NAMES[2] if report.receives == [(2, 0)] else "memory"  # the BasicMachine's table is its mem chip
+    for kind in va.MEMORY_KINDS:
+        if not c[kind]:
+            continue
+        head = "%s: %d %s%s" % (name, c[kind], MEMORY_KIND_TEXT[kind], "" if c[kind] == 1 else "s")
+        first = [f for f in report.findings if f["kind"] == kind]
+        if not first:
+            lines.append(head)
+            continue
+        f = first[0]
+        at = "row %d, addr %d, clk %d: " % (f["row"], f["addr"], f["clk"])
+        if kind == "malformed":
+            what = ", ".join(MEMORY_REASONS[b] for b in range(5) if f["reason"] >> b & 1)
+        elif kind == "duplicate_static":
+            what = "the record before it is a static record of this address"
+        elif kind == "stale_read":
+            what = "read %s, last write %s at row %d" % (memory_value(f["value"]), memory_value(f["expected"]), f["last_write"][2])
+        else:
+            what = "read %s, nothing written" % (memory_value(f["value"]),)
+        lines.append("%s (%s%s)" % (head, at, what))
+    lines.append("%s: %d live records (%d reads, %d writes, %d static) of %d addresses, %d same-cycle pair%s, largest clk gap %d, %d uninitialised zero read%s, dummy reads %d clk + %d addr, %s, %s" % (
+        name, c["live"], c["reads"], c["writes"], c["statics"], c["addresses"], c["same_cycle_pairs"], "" if c["same_cycle_pairs"] == 1 else "s", c["max_clk_gap"], c["uninit_zero_reads"],
+        "" if c["uninit_zero_reads"] == 1 else "s", c["dummy_reads_clk"], c["dummy_reads_addr"],
+        "laid out sorted" if not c["layout_descents"] else "%d layout descent%s (the first at row %d)" % (c["layout_descents"], "" if c["layout_descents"] == 1 else "s", report.first_descent[1]),
+        "no finding" if not c["findings"] else "%d finding%s" % (c["findings"], "" if c["findings"] == 1 else "s")))
+    return lines
+
+
+def check_status(balanced, creport, mreport):
+    """The exit status of `check`: 1 for an unbalanced bus, a failing constraint (with --constraints) or a memory finding (with --memory)."""
+    return 0 if balanced and (creport is None or creport.satisfied) and (mreport is None or mreport.total_findings == 0) else 1
+
+
 def field_lines(report):
     """One line per (chip, interaction) of a field report with a floating field: the bus, the fields, the most rows one of them floats on."""
     import valida_amd as va
@@ -542,6 +598,9 @@ def main(argv=None):
                     "fields only; never changes the exit status)")
     ap.add_argument("--max-bits", type=int, default=16, help="check --domains: a column is narrow when its largest value is below 2^N (1 to 16, default 16)")
     ap.add_argument("--lookup-buses", default="", help="check --domains: the buses that count as lookup tables instead of the structural rule, comma-separated (3 or g3: global bus 3, l0: local bus 0)")
+    ap.add_argument("--memory", action="store_true", help="check: also the memory audit (the receives of the memory bus replayed as a memory: malformed records, duplicate static "
+                    "records, reads that do not return the last write to their address, reads of a non-zero value from an address nobody wrote; definite faults: check exits 1 on a finding)")
+    ap.add_argument("--max-findings", type=int, default=64, help="check --memory: the findings listed (default 64, at most 2^20; the counts stay exact)")
     ap.add_argument("--min-gate-windows", type=int, default=64, help="check --transitions: a gate that holds on fewer windows is counted but not audited (default 64)")
     ap.add_argument("--max-gates", type=int, default=256, help="check --transitions: the gates listed per chip, the ungated one included (default 256)")
     ap.add_argument("--step-sizes", default="1,-1,2", help="check --steps: 1 to 4 distinct step sizes, comma-separated integers mod p (as --step-sizes=1,-1,2)")
@@ -586,6 +645,7 @@ def main(argv=None):
                 qreport = va.product_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.products else None
                 dreport = va.domain_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips), max_bits=args.max_bits,
                                                lookup_buses=parse_lookup_buses(args.lookup_buses)) if args.domains else None
+                memreport = va.memory_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_findings=args.max_findings) if args.memory else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -604,6 +664,7 @@ def main(argv=None):
                 treport = prover.transition_audit(main, prep, max_terms=256, min_gate_windows=args.min_gate_windows, max_gates=args.max_gates, chips=parse_chips(args.chips)) if args.transitions else None
                 qreport = prover.product_audit(main, prep, max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.products else None
                 dreport = prover.domain_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips), max_bits=args.max_bits, lookup_buses=parse_lookup_buses(args.lookup_buses)) if args.domains else None
+                memreport = prover.memory_audit(main, prep, max_findings=args.max_findings) if args.memory else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -629,6 +690,8 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), products=qreport.to_dict()))
             if dreport is not None:
                 text = json.dumps(dict(json.loads(text), domains=dreport.to_dict()))
+            if memreport is not None:
+                text = json.dumps(dict(json.loads(text), memory=memreport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
@@ -636,9 +699,9 @@ def main(argv=None):
                     rank_lines(rreport) if rreport is not None else []) + (field_lines(freport) if freport is not None else []) + (
                     link_lines(lreport) if lreport is not None else []) + (step_lines(sreport) if sreport is not None else []) + (
                     invariant_lines(ireport) if ireport is not None else []) + (transition_lines(treport) if treport is not None else []) + (
-                    product_lines(qreport) if qreport is not None else []) + (domain_lines(dreport) if dreport is not None else []):
+                    product_lines(qreport) if qreport is not None else []) + (domain_lines(dreport) if dreport is not None else []) + (memory_lines(memreport) if memreport is not None else []):
                 print(line)
-            return 0 if report.balanced and (creport is None or creport.satisfied) else 1
+            return check_status(report.balanced, creport, memreport)
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256
         rc = va.poseidon_round_constants(source=args.constants)
         prover = va.Prover(va.Machine.basic(), rc, device=args.device or 0, log_blowup=args.log_blowup, num_queries=args.queries, pow_bits=args.pow_bits,

@@ -20,6 +20,7 @@
 #include "transition_audit.hpp"
 #include "product_audit.hpp"
 #include "domain_audit.hpp"
+#include "memory_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -179,6 +180,10 @@ class Prover {
     // streaming scan per virtual column into an LDS bitmap) and the rows on which a narrow column is not a field of a live send to a lookup table;
     // queued on the context like the other audits, scratch from the pool.
     DomainReport domain_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const DomainAuditOpts& opts);
+    // Memory audit of a witness (host/memory_audit.hpp, kernels/memory_audit.hip): the receives of one bus replayed as a memory (a 64-bit key sort
+    // of the slots, a max-scan for the last write, one judged sweep) and the records that break it; queued on the context like the other audits,
+    // scratch from the pool.
+    MemoryReport memory_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const MemoryAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

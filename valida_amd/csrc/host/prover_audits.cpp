@@ -1784,4 +1784,88 @@ CoverageReport Prover::coverage_audit(const std::vector<const DeviceTrace*>& mai
     return rep;
 }
 
+// ---- memory audit (host/memory_audit.hpp; kernels/memory_audit.hip) -------------------------------------------------------------------------
+MemoryReport Prover::memory_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const MemoryAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const MemoryAuditOpts o = memory_audit_checked_opts(opts_in);
+    const auto tr = audit_traces<BusShape>("memory_audit", main, preprocessed);
+    std::vector<int> prep_slot;
+    BusPlan bus_plan;
+    const MemoryPlan plan = memory_audit_plan(machine_, tr.ms, tr.prep_chips, tr.ps, prep_slot, o, &bus_plan);
+    const uint64_t n = plan.n_slots;
+    std::vector<uint32_t> entries;
+    const std::vector<uint32_t> mt_words = memory_audit_mt(plan, entries);
+    MemoryReport rep;
+    memory_audit_header(rep, plan, o);
+
+    DeviceCtx& c = *ctx_;
+    AuditPass pass(c, main.size() + preprocessed.size());
+    const size_t NC = machine_.airs.size();
+    const hipStream_t st = pass.stream;
+    uint64_t n_live = 0;
+    audit_or_no_memory(st, [&] {
+        // only the chips that receive on the audited bus are read
+        std::vector<const uint32_t*> mptr(NC, nullptr), pptr(NC, nullptr);
+        std::vector<uint64_t> mstride(NC, 0), pstride(NC, 0);
+        for (uint32_t i : entries) {
+            const vk::DMatView v = pass.working(main[i]);
+            mptr[i] = v.data; mstride[i] = v.stride;
+            if (const DeviceTrace* p = audit_prep(preprocessed, prep_slot, i)) { const vk::DMatView pv = pass.working(p); pptr[i] = pv.data; pstride[i] = pv.stride; }
+        }
+        c.check_launch("memory_audit ingest");
+        DBuf desc(&c, bus_audit_descriptor(machine_, bus_plan, mptr, mstride, pptr, pstride)), mt(&c, mt_words);
+        const uint64_t na = n ? n : 1;
+        // the totals of the keys pass and of the judge, u64 each, zeroed by one memset
+        constexpr size_t TOT_WORDS = 2 * (vk::MM_KEY_TOT + vk::MM_JUDGE_TOT);
+        DBuf keys2(&c, (size_t)(4 * na)), ids2(&c, (size_t)(2 * na)), sort_tmp(&c, vk::bus_audit_sort_scratch_words(na)), totals(&c, TOT_WORDS);
+        unsigned long long* keys = (unsigned long long*)keys2.data;
+        unsigned long long* tot = (unsigned long long*)totals.data;
+        unsigned long long* cnt = tot + vk::MM_KEY_TOT;
+        pass.begin();
+        VG_HIP_CHECK(hipMemsetAsync(totals.data, 0, TOT_WORDS * 4, st));
+        for (size_t e = 0; e < entries.size(); e++)
+            vk::launch_mm_keys(st, desc.data, mt.data, (uint32_t)e, plan.chips[entries[e]].height, (uint32_t)plan.chips[entries[e]].receives.size(), keys, ids2.data, tot);
+        c.check_launch("memory_audit keys");
+        std::vector<uint32_t> tw(TOT_WORDS, 0);
+        c.download_small(tw.data(), totals.data, 2 * vk::MM_KEY_TOT * 4);
+        unsigned long long th[vk::MM_KEY_TOT], ch[vk::MM_JUDGE_TOT];
+        for (uint32_t k = 0; k < vk::MM_KEY_TOT; k++) th[k] = audit_u64(tw, k);
+        n_live = th[0];
+        if (!n_live) {
+            memory_audit_from_device(rep, plan, th, nullptr, nullptr, 0);
+        } else {
+            int shifts[8];
+            const int n_shifts = memory_audit_shifts(th[1], th[2], n_live < n, shifts);
+            const int half = vk::launch_ba_sort(st, keys, ids2.data, n, sort_tmp.data, shifts, n_shifts, 0);
+            const uint32_t* ids = ids2.data + (uint64_t)half * n;
+            const uint64_t nb = (n_live + 255) / 256;
+            DBuf rec(&c, (size_t)(vk::MM_REC * n_live)), mark(&c, (size_t)n_live), block_before(&c, vk::memory_audit_scan_blocks(n_live)), table(&c, (size_t)nb);
+            vk::launch_mm_gather(st, desc.data, mt.data, keys + (uint64_t)half * n, ids, n_live, n_live, rec.data, mark.data);
+            vk::launch_mm_scan(st, mark.data, n_live, block_before.data);
+            vk::launch_mm_judge(st, vk::MM_COUNT, rec.data, ids, mark.data, block_before.data, n_live, n_live, cnt, table.data, 0, nullptr);
+            c.check_launch("memory_audit judge");
+            c.download_small(tw.data(), totals.data, TOT_WORDS * 4);
+            for (uint32_t k = 0; k < vk::MM_JUDGE_TOT; k++) ch[k] = audit_u64(tw, vk::MM_KEY_TOT + k);
+            const uint64_t total = ch[6] + ch[7] + ch[8] + ch[9];
+            const size_t listed = (size_t)std::min<uint64_t>(total, o.max_findings);
+            std::vector<uint32_t> ow(listed * vk::MM_OUT);
+            if (listed) {
+                DBuf out(&c, ow.size());
+                vk::launch_mm_judge(st, vk::MM_LIST, rec.data, ids, mark.data, block_before.data, n_live, n_live, nullptr, table.data, (uint32_t)listed, out.data);
+                c.check_launch("memory_audit list");
+                c.download_small(ow.data(), out.data, ow.size() * 4);
+            }
+            memory_audit_from_device(rep, plan, th, ch, ow.data(), listed);
+        }
+        pass.end(rep);
+    }, [&] {
+        return std::string("memory_audit: the device pool cannot give the pass its scratch: 24 bytes per slot (two halves of 8-byte keys and 4-byte ids) for each of the " +
+                           std::to_string(n) + " (chip, receive, row) slots = " + std::to_string(24 * n) + " bytes, " + std::to_string(vk::bus_audit_sort_scratch_words(n ? n : 1) * 4) +
+                           " bytes of digit tables, 32 bytes for each of the " + std::to_string(n_live) + " live records (7 words of record, 1 of mark) = " + std::to_string(32 * n_live) +
+                           " bytes, 64 per listed finding, plus the working-layout copies of uploaded traces");
+    });
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 }  // namespace vhost

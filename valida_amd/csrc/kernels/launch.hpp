@@ -442,6 +442,22 @@ void launch_da_scan(hipStream_t st, const DaArgs& a, unsigned long long* tot, ui
 void launch_da_classify(hipStream_t st, const unsigned long long* tot, const uint32_t* bitmaps, uint32_t* cls, uint32_t n_slots, uint32_t max_bits);
 void launch_da_guard(hipStream_t st, const DaArgs& a, uint32_t mode, const uint32_t* cls, unsigned long long* gtot, uint32_t* table, const uint32_t* prefix, uint32_t c_cut, uint32_t R,
                      uint32_t* rows);
+// memory_audit.hip — the passes of the memory audit (host/memory_audit.hpp: contract; Prover::memory_audit drives them).  desc: the bus audit's
+// descriptor (host/bus_audit.hpp).  mt: [0] entries, per entry (a chip with receives on the audited bus) 4 words: chip, first slot, receives R,
+// the word offset in mt of its R interaction indices.  A slot is first_slot + row * R + k; n slots in all.  keys2 / ids2: [2 n] ping-pong halves
+// for launch_ba_sort; tot: [MM_KEY_TOT] u64 (zeroed); rec: [MM_REC][n_live] u32; mark: [n_live]; block_before: [memory_audit_scan_blocks(n_live)];
+// cnt: [MM_JUDGE_TOT] u64 (zeroed); table: [ceil(n_live / 256)] u32; out: [max_findings][MM_OUT] u32.
+constexpr uint32_t MM_TILE = 256, MM_KEY_TOT = 5, MM_SCAN_ITEMS = 8, MM_SCAN_BLOCK = MM_SCAN_ITEMS * 256, MM_JUDGE_TOT = 16, MM_REC = 7, MM_NFIELDS = 8, MM_OUT = 16;
+enum : uint32_t { MM_COUNT = 0, MM_LIST = 1 };
+size_t memory_audit_scan_blocks(uint64_t n);
+void launch_mm_keys(hipStream_t st, const uint32_t* desc, const uint32_t* mt, uint32_t entry, uint64_t height, uint32_t R, unsigned long long* keys, uint32_t* ids,
+                    unsigned long long* tot);
+void launch_mm_gather(hipStream_t st, const uint32_t* desc, const uint32_t* mt, const unsigned long long* keys, const uint32_t* ids, uint64_t n_live, uint64_t n, uint32_t* rec,
+                      uint32_t* mark);
+void launch_mm_scan(hipStream_t st, uint32_t* mark, uint64_t n_live, uint32_t* block_before);
+// MM_COUNT: the counters and the findings per workgroup; MM_LIST (after it): scans the table in place and lists the first max_findings
+void launch_mm_judge(hipStream_t st, uint32_t mode, const uint32_t* rec, const uint32_t* ids, const uint32_t* incl, const uint32_t* block_before, uint64_t n_live, uint64_t n,
+                     unsigned long long* cnt, uint32_t* table, uint32_t max_findings, uint32_t* out);
 // field_audit.hip — the passes of the field audit (host/field_audit.hpp: contract; Prover::field_audit drives them), per chip.  One wave per
 // trace row, one wave per workgroup, T rows per workgroup one after the other, NB workgroups.  A SLOT of a chip is (interaction, field) in
 // order, NS of them.  totals: u64 [0] live records, [1] floating fields, [2] rows with a floating field, [3 + m] live rows of interaction m,
