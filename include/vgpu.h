@@ -1120,6 +1120,80 @@ const uint32_t* vgpu_memory_report_words(const vgpu_memory_report_t* r);
 void vgpu_memory_report_timing(const vgpu_memory_report_t* r, double out[3]);
 void vgpu_memory_report_free(vgpu_memory_report_t* r);
 
+/* ---- Program audit: the memory audit asks whether the memory table is a memory; the same hole exists for instruction fetch.  The reference comments
+ * out both halves of the program bus (the cpu's send of (pc, opcode, a..e) with count one, cpu/src/lib.rs:138-157; the program chip's receive of
+ * the preprocessed ROM row with count `multiplicity`, program/src/lib.rs:50-68) and the program chip's AIR is empty: nothing ties a cpu row's
+ * instruction to ROM[pc] or the multiplicity column to how often a word ran.  This audit replays the would-be bus exactly.  Inputs: exactly what
+ * vgpu_prove and the audits take.
+ *   options   fetch_chip (default 0, the cpu), pc_col (1), n_fields (6; 1 to 8), field_cols (3..8: opcode, a..e; main columns of the fetching
+ *             chip), table_chip (1, program), key_col (0) and table_cols (1..6), preprocessed columns of the table chip, mult_col (0), a main
+ *             column of the table chip, rom_len (0: the table's height; the table's rows from rom_len on are padding and not fetchable),
+ *             max_findings and max_ranges (64, at most 2^20; in a struct taken as given: 0 lists nothing and every count stays exact), reserved
+ *             (0).  A null pointer gives these defaults, the BasicMachine's.  VGPU_ERR_INVALID_ARG before anything is queued, the message naming
+ *             the reason: a column outside its trace, a table chip without a preprocessed trace, a table whose main and preprocessed heights
+ *             differ, rom_len above the table's height, a fetch or table height above 2^30, n_fields outside 1..8, a non-zero reserved.
+ *   records   a FETCH is every row r of the fetching chip, padding rows included, count one: pc(r) = the cell at pc_col, f(r)[j] = the cell at
+ *             field_cols[j].  A table row i has key K[i], word W[i][j], multiplicity m[i].  c[i] = the fetches with pc(r) == i, for i below the
+ *             table's height.  Lookups are by row index; values canonical.
+ *   findings  1 TABLE_KEY (a table row with K[i] != i), 2 PC_OUT_OF_ROM (a fetch with pc >= rom_len), 3 WRONG_INSTRUCTION (pc < rom_len and some
+ *             field differs from W[pc] by something other than 2^32 mod p = 268435454), 4 WRAPPED_OPERAND (pc < rom_len, at least one field
+ *             differs and every differing field has f - W = 2^32 mod p: the reference's set_imm_value / set_left_imm_value, cpu/src/lib.rs:
+ *             356-372, put the u32 value of a negative immediate mod p into the cpu row where the ROM holds from_i32 of it; counted and listed
+ *             apart, never a fault), 5 MULTIPLICITY (m[i] != c[i] mod p).  mask: bit j for every differing field, wrapped or not.  A fetch gets at
+ *             most one of 2, 3, 4; a table row may get 1 and 5.  Kinds 1, 2, 3, 5 are the HARD findings.  With rom_len = the table's height
+ *             there is no hard and no wrapped finding exactly when the reference's program bus, uncommented, balances on this witness.
+ *   counters  exact: fetches, table rows, rom_len, fetched_words (i < rom_len with c[i] > 0), unfetched_words, unfetched_ranges (maximal runs of
+ *             unfetched words below rom_len), hottest_pc and hottest_count (the largest c[i] over the table's rows, the lowest i on a tie; 0 and 0
+ *             when no fetch hits the table), first_pc, last_pc, over the windows (r, r + 1) sequential (pc' = pc + 1 in the field), stay
+ *             (pc' = pc) and jumps (the rest); one count per kind.
+ *   lists     findings: the first max_findings hard findings, TABLE_KEY by i, then the fetch findings by row, then MULTIPLICITY by i; wrapped:
+ *             the first max_findings WRAPPED_OPERAND rows in row order; unfetched: the first max_ranges ranges [lo, hi), ascending.
+ * What it is not: it judges the fetches against the table of THIS witness only.  It does not ask whether the opcode flags fit the opcode,
+ * whether the step did what the opcode says, or whether the preprocessed commitment is the verifier's.
+ * vgpu_program_audit runs on the device (kernels/program_audit.hip), queued on the prover context, wave64, workgroups of 256: k_pg_hist (the
+ * fetch counts in an LDS histogram of min(table height, 32768) bins per workgroup, taller tables in slices; a wave whose live lanes hold one pc
+ * adds once), k_pg_judge (a thread per fetch: kind, mask, the window to the next row through an LDS tile with one halo row; counters by ballots,
+ * LDS, one atomic per counter and workgroup), k_pg_table (a thread per table row: key, multiplicity, fetched flag, range starts and ends through
+ * a halo, the hottest word as a maximum of count << 32 | ~pc); every list by count -> scan -> list.  The only atomics are integer add and max:
+ * every word is the same run after run.  Scratch from the pool, its totals and counts zeroed by one memset; VGPU_ERR_OOM with the arithmetic when
+ * the pool cannot give it.  vgpu_program_audit_host: the same contract on the host, one thread, no limits beyond the refusals.
+ * Report image (vgpu_program_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x31475056 "VPG1" [1] word count [2] fetch_chip [3] table_chip [4] n_fields [5] truncated (bit 0 findings, bit 1 wrapped, bit 2
+ *   unfetched) [6] listed findings [7] listed wrapped [8] listed ranges [9] max_findings [10] max_ranges [11] rom_len [12,13] fetches [14,15]
+ *   table rows [16,17] fetched_words [18,19] unfetched_words [20,21] unfetched_ranges [22] hottest_pc [23] 0 [24,25] hottest_count [26]
+ *   first_pc [27] last_pc [28,29] sequential [30,31] stay [32,33] jumps [34,35] hard findings [36,37] table_key [38,39] pc_out_of_rom [40,41]
+ *   wrong_instruction [42,43] wrapped_operand [44,45] multiplicity [46,47] 0
+ *   per listed finding, then per listed wrapped row, 24 words: [0] kind [1] mask [2] the fetch row (kinds 2, 3, 4) or the table row (1, 5)
+ *   [3] pc (the table row for kinds 1, 5) [4..11] found: f(r)[j] (kinds 2, 3, 4), K[i] in [4] (kind 1), m[i] in [4] (kind 5) [12..19]
+ *   expected: W[pc][j] (kinds 3, 4), 0 (kind 2), i in [12] (kind 1), c[i] mod p in [12] and c[i] in [13] (kind 5) [20..23] 0
+ *   per listed range 2 words: lo, hi */
+typedef struct vgpu_program_audit_opts {
+    uint32_t fetch_chip;
+    uint32_t pc_col;
+    uint32_t n_fields;
+    uint32_t field_cols[8];
+    uint32_t table_chip;
+    uint32_t key_col;
+    uint32_t table_cols[8];
+    uint32_t mult_col;
+    uint32_t rom_len;
+    uint32_t max_findings;
+    uint32_t max_ranges;
+    uint32_t reserved;
+} vgpu_program_audit_opts_t;
+typedef struct vgpu_program_report vgpu_program_report_t;
+int32_t vgpu_program_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                           uint32_t n_prep, const vgpu_program_audit_opts_t* opts, vgpu_program_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_program_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                                const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                                const vgpu_program_audit_opts_t* opts, vgpu_program_report_t** out);
+uint64_t vgpu_program_report_len(const vgpu_program_report_t* r);
+const uint32_t* vgpu_program_report_words(const vgpu_program_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: fetches + table rows */
+void vgpu_program_report_timing(const vgpu_program_report_t* r, double out[3]);
+void vgpu_program_report_free(vgpu_program_report_t* r);
+
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.
  *   mutations     exactly those of the mutation audit above: (chip, row r, main column c, delta index j), the same trace domain, 1 to 4 distinct

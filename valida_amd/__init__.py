@@ -249,6 +249,10 @@ class Workload:
             out.append((chip.value, np.ctypeslib.as_array(data, shape=(h.value, w.value)).copy()))
         return out
 
+    def program_audit_host(self, max_findings=64, max_ranges=64):
+        """The host program audit of this workload's own witness with rom_len = program_len: the table's zero padding rows are not fetchable."""
+        return program_audit_host(Machine.basic(), self.main_traces(), self.preprocessed(), rom_len=self.program_len, max_findings=max_findings, max_ranges=max_ranges)
+
     def __del__(self):
         if getattr(self, "_h", None):
             try:
@@ -1809,6 +1813,96 @@ def memory_audit_host(machine, main_matrices, preprocessed, max_findings=64, bus
     return _audit_host("memory", machine, main_matrices, preprocessed, _memory_opts(max_findings, bus))
 
 
+class ProgramAuditOpts(ctypes.Structure):  # vgpu_program_audit_opts_t
+    _fields_ = [("fetch_chip", ctypes.c_uint32), ("pc_col", ctypes.c_uint32), ("n_fields", ctypes.c_uint32), ("field_cols", ctypes.c_uint32 * 8), ("table_chip", ctypes.c_uint32),
+                ("key_col", ctypes.c_uint32), ("table_cols", ctypes.c_uint32 * 8), ("mult_col", ctypes.c_uint32), ("rom_len", ctypes.c_uint32), ("max_findings", ctypes.c_uint32),
+                ("max_ranges", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+PROGRAM_KINDS = ("table_key", "pc_out_of_rom", "wrong_instruction", "wrapped_operand", "multiplicity")
+PROGRAM_HARD_KINDS = ("table_key", "pc_out_of_rom", "wrong_instruction", "multiplicity")
+PROGRAM_COUNTERS = ("fetches", "table_rows", "rom_len", "fetched_words", "unfetched_words", "unfetched_ranges", "hottest_pc", "hottest_count", "first_pc", "last_pc", "sequential", "stay",
+                    "jumps", "hard") + PROGRAM_KINDS
+PROGRAM_TWO32 = (1 << 32) % P  # what the unsigned and the signed embedding of one negative i32 differ by
+
+
+class ProgramReport(_AuditReport):
+    """The program audit of a witness (vgpu_program_audit / vgpu_program_audit_host; the contract is stated in include/vgpu.h), as plain
+    Python values: words (the image), fetch_chip, table_chip, n_fields, max_findings, max_ranges, truncated = (findings, wrapped, unfetched),
+    counters = dict(fetches, table_rows, rom_len, fetched_words, unfetched_words, unfetched_ranges, hottest_pc, hottest_count, first_pc,
+    last_pc, sequential, stay, jumps, hard, table_key, pc_out_of_rom, wrong_instruction, wrapped_operand, multiplicity),
+    hard = the listed hard findings and wrapped = the listed wrapped-operand rows, each [dict(kind, mask, fields = the field indices of mask,
+    row, pc, found, expected)] (for table_key and multiplicity row = pc = the table row, found[0] = the key or the multiplicity,
+    expected[0] = the row or the fetch count mod p, expected[1] = the fetch count), unfetched = [(lo, hi)],
+    device_ms (the device pass; 0.0 for the host audit), host_ms (the whole call), evaluations (fetches + table rows).
+    It judges the fetches against the table of THIS witness; wrapped operands are never a fault."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 48 or w[0] != 0x31475056 or w[1] != len(w) or len(w) != 48 + 24 * (w[6] + w[7]) + 2 * w[8]:
+            raise ValueError("not a program report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        self.fetch_chip, self.table_chip, self.n_fields, self.max_findings, self.max_ranges = w[2], w[3], w[4], w[9], w[10]
+        self.truncated = (bool(w[5] & 1), bool(w[5] & 2), bool(w[5] & 4))
+        self.counters = dict(fetches=u64(12), table_rows=u64(14), rom_len=w[11], fetched_words=u64(16), unfetched_words=u64(18), unfetched_ranges=u64(20), hottest_pc=w[22],
+                             hottest_count=u64(24), first_pc=w[26], last_pc=w[27], sequential=u64(28), stay=u64(30), jumps=u64(32), hard=u64(34), table_key=u64(36), pc_out_of_rom=u64(38),
+                             wrong_instruction=u64(40), wrapped_operand=u64(42), multiplicity=u64(44))
+        pos = 48
+        self.hard, self.wrapped = [], []
+        for n, into in ((w[6], self.hard), (w[7], self.wrapped)):
+            for _ in range(n):
+                f = w[pos:pos + 24]
+                into.append(dict(kind=PROGRAM_KINDS[f[0] - 1], mask=f[1], fields=[j for j in range(8) if f[1] >> j & 1], row=f[2], pc=f[3], found=f[4:12], expected=f[12:20]))
+                pos += 24
+        self.unfetched = [(w[pos + 2 * k], w[pos + 2 * k + 1]) for k in range(w[8])]
+
+    @property
+    def total_hard(self):
+        return self.counters["hard"]
+
+    @property
+    def total_wrapped(self):
+        return self.counters["wrapped_operand"]
+
+    def to_dict(self):
+        return dict(words=[int(x) for x in self.words], fetch_chip=self.fetch_chip, table_chip=self.table_chip, n_fields=self.n_fields, max_findings=self.max_findings,
+                    max_ranges=self.max_ranges, truncated=list(self.truncated), counters=self.counters, hard=self.hard, wrapped=self.wrapped, unfetched=[list(r) for r in self.unfetched],
+                    device_ms=self.device_ms, host_ms=self.host_ms, evaluations=self.evaluations)
+
+    @classmethod
+    def from_dict(cls, d):
+        """The report of to_dict()'s object (a `check --program` JSON report's "program" key)."""
+        return cls(d["words"], d.get("device_ms", 0.0), d.get("host_ms", 0.0), d.get("evaluations", 0.0))
+
+
+def _program_opts(rom_len, max_findings, max_ranges, fetch, table):
+    """fetch: None (the BasicMachine's cpu: chip 0, pc column 1, field columns 3..8) or (chip, pc_col, [field columns]); table: None (its
+    program chip: chip 1, key column 0, word columns 1..6, multiplicity column 0) or (chip, key_col, [word columns], mult_col)."""
+    fchip, pc_col, fcols = (0, 1, [3, 4, 5, 6, 7, 8]) if fetch is None else (int(fetch[0]), int(fetch[1]), [int(c) for c in fetch[2]])
+    tchip, key_col, tcols, mult_col = (1, 0, [1, 2, 3, 4, 5, 6], 0) if table is None else (int(table[0]), int(table[1]), [int(c) for c in table[2]], int(table[3]))
+    if len(fcols) != len(tcols):
+        raise VgpuError(-1, "program_audit: the fetching chip and the table name as many field columns (%d, %d)" % (len(fcols), len(tcols)))
+    if not 1 <= len(fcols) <= 8:
+        raise VgpuError(-1, "program_audit: n_fields is 1 to 8 (got %d)" % len(fcols))
+    values = [fchip, pc_col, tchip, key_col, mult_col, int(rom_len), int(max_findings), int(max_ranges)] + fcols + tcols
+    if any(v < 0 or v >= 1 << 32 for v in values):
+        raise VgpuError(-1, "program_audit: chips, columns, rom_len and the limits are not negative")
+    u8 = ctypes.c_uint32 * 8
+    return ProgramAuditOpts(fchip, pc_col, len(fcols), u8(*fcols), tchip, key_col, u8(*tcols), mult_col, int(rom_len), int(max_findings), int(max_ranges), 0)
+
+
+def program_audit_host(machine, main_matrices, preprocessed, rom_len=0, max_findings=64, max_ranges=64, fetch=None, table=None):
+    """The program audit on the HOST (vgpu_program_audit_host: no device, one thread): main_matrices = one canonical matrix per chip,
+    preprocessed = [(chip index, matrix)], rom_len = the ROM's length (0: the table's height; Workload.program_len is a VM witness's),
+    fetch = None or (chip, pc_col, [field columns]), table = None or (chip, key_col, [word columns], mult_col); a ProgramReport back."""
+    return _audit_host("program", machine, main_matrices, preprocessed, _program_opts(rom_len, max_findings, max_ranges, fetch, table))
+
+
 class TransitionAuditOpts(ctypes.Structure):  # vgpu_transition_audit_opts_t
     _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("max_terms", ctypes.c_uint32),
                 ("min_gate_windows", ctypes.c_uint32), ("max_gates", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
@@ -2231,7 +2325,7 @@ def coverage_audit_host(machine, main_matrices, preprocessed, deltas=None, max_c
     return _audit_host("coverage", machine, main_matrices, preprocessed, opts)
 
 
-_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, product=ProductReport, domain=DomainReport, memory=MemoryReport, field=FieldReport,
+_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, product=ProductReport, domain=DomainReport, memory=MemoryReport, program=ProgramReport, field=FieldReport,
                       link=LinkReport, coverage=CoverageReport)
 
 
@@ -2480,6 +2574,13 @@ class Prover:
         (vgpu_memory_audit); the arguments of prove, bus = None (global bus 2), a global bus index or (is_global, bus_index); a MemoryReport
         back with the records that break it and the exact counters."""
         return self._audit("memory", main, preprocessed, _memory_opts(max_findings, bus))
+
+    def program_audit(self, main, preprocessed, rom_len=0, max_findings=64, max_ranges=64, fetch=None, table=None):
+        """Whether the instruction fetches of this witness match its program ROM and the ROM's multiplicities match the fetch counts
+        (vgpu_program_audit); the arguments of prove, rom_len = the ROM's length (0: the table's height; Workload.program_len is a VM
+        witness's), fetch = None (the cpu) or (chip, pc_col, [field columns]), table = None (the program chip) or (chip, key_col, [word
+        columns], mult_col); a ProgramReport back with the fetches and table rows that break the would-be program bus and the exact counters."""
+        return self._audit("program", main, preprocessed, _program_opts(rom_len, max_findings, max_ranges, fetch, table))
 
     def transition_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, min_gate_windows=64, max_gates=256, chips=None):
         """Which affine-linear relations between a row and its successor this witness keeps, on every window or under a boolean gate, and at

@@ -37,6 +37,7 @@ SOURCES = [
     "kernels/product_audit.hip",
     "kernels/domain_audit.hip",
     "kernels/memory_audit.hip",
+    "kernels/program_audit.hip",
     "kernels/field_probe.hip",
     "host/prover.cpp",
     "host/prover_audits.cpp",

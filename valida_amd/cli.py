@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--products] [--domains] [--max-bits N] [--lookup-buses B[,B..]] [--memory] [--max-findings N] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--products] [--domains] [--max-bits N] [--lookup-buses B[,B..]] [--memory] [--program] [--max-findings N] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -124,9 +124,18 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         that rest on the trace's own order), the largest clk gap, the dummy reads the reference's unfinished memory argument would need, and
         whether the trace as laid out is sorted.  It judges the table's receives (whether the senders agree is the bus audit's question).
         Findings are definite faults: with --memory, check exits 1 when there is one.
+        --program adds the program audit of the same witness (vgpu_program_audit: every cpu row's (pc, opcode, a..e) held against the program
+        chip's preprocessed ROM row, and the ROM's multiplicity column against the fetch counts: the reference's commented-out program bus
+        replayed), on the same path (device or --host), with the ROM's real length so that the table's padding rows are not fetchable;
+        --max-findings N lists the first N (default 64).  The JSON report gets one more key, "program" (ProgramReport.to_dict's object); stdout
+        gets one line per hard kind present, `cpu: 1 wrong instruction (row 100, pc 12: operand a 7, ROM 0)`, one line for wrapped operands,
+        `cpu: 8 fetches differ from the ROM only by 2^32 in an immediate (first row 5, pc 5, fields c)` (the reference writes the u32 value of a
+        negative immediate mod p into the cpu row where the ROM holds p - |x|: counted apart, never a fault), and one summary line with the
+        counters and the first ranges of words that never ran.  It judges the fetches against the table of THIS witness, not what the step did.
+        Hard findings are definite faults: with --program, check exits 1 when there is one; wrapped operands never change the status.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
-Exit status: 0 on success (run / prove done, proof accepted, witness balanced, with --constraints every constraint satisfied and with --memory no memory finding), 1 otherwise (the reference always exits 0)."""
+Exit status: 0 on success (run / prove done, proof accepted, witness balanced, with --constraints every constraint satisfied, with --memory no memory finding and with --program no hard program finding), 1 otherwise (the reference always exits 0)."""
 import argparse
 import json
 import sys
@@ -477,9 +486,64 @@ def memory_lines(report):
     return lines
 
 
-def check_status(balanced, creport, mreport):
-    """The exit status of `check`: 1 for an unbalanced bus, a failing constraint (with --constraints) or a memory finding (with --memory)."""
-    return 0 if balanced and (creport is None or creport.satisfied) and (mreport is None or mreport.total_findings == 0) else 1
+def check_status(balanced, creport, mreport, preport=None):
+    """The exit status of `check`: 1 for an unbalanced bus, a failing constraint (with --constraints), a memory finding (with --memory) or a
+    hard program finding (with --program; wrapped operands never count)."""
+    return 0 if balanced and (creport is None or creport.satisfied) and (mreport is None or mreport.total_findings == 0) and (preport is None or preport.total_hard == 0) else 1
+
+
+PROGRAM_FIELD_NAMES = ("opcode", "operand a", "operand b", "operand c", "operand d", "operand e")
+
+
+def program_field(j, short=False):
+    """Field j of a fetch as the BasicMachine names it (opcode, a..e); beyond those its index."""
+    name = PROGRAM_FIELD_NAMES[j] if j < len(PROGRAM_FIELD_NAMES) else "field %d" % j
+    return name.split(" ")[-1] if short else name
+
+
+def program_lines(report):
+    """One line per hard kind of a program report (the count and the first listed finding of the kind), one for the wrapped operands, then one
+    summary line with the counters and the first unfetched ranges."""
+    import valida_amd as va
+
+    c, lines = report.counters, []
+    fetcher = va.CHIP_NAMES[report.fetch_chip] if (report.fetch_chip, report.table_chip) == (0, 1) else "chip %d" % report.fetch_chip
+    table = va.CHIP_NAMES[report.table_chip] if (report.fetch_chip, report.table_chip) == (0, 1) else "chip %d" % report.table_chip
+    text = {"table_key": ("wrong table key", "wrong table keys"), "pc_out_of_rom": ("pc outside the ROM", "pcs outside the ROM"), "wrong_instruction": ("wrong instruction", "wrong instructions"),
+            "multiplicity": ("wrong multiplicity", "wrong multiplicities")}
+    for kind in va.PROGRAM_HARD_KINDS:
+        if not c[kind]:
+            continue
+        head = "%s: %d %s" % (table if kind in ("table_key", "multiplicity") else fetcher, c[kind], text[kind][c[kind] != 1])
+        first = [f for f in report.hard if f["kind"] == kind]
+        if not first:
+            lines.append(head)
+            continue
+        f = first[0]
+        if kind == "table_key":
+            what = "row %d: key %d" % (f["row"], f["found"][0])
+        elif kind == "pc_out_of_rom":
+            what = "row %d, pc %d, ROM length %d" % (f["row"], f["pc"], c["rom_len"])
+        elif kind == "wrong_instruction":
+            what = "row %d, pc %d: %s" % (f["row"], f["pc"], ", ".join("%s %d, ROM %d" % (program_field(j), f["found"][j], f["expected"][j]) for j in f["fields"]))
+        else:
+            what = "word %d: multiplicity %d, fetched %d times" % (f["row"], f["found"][0], f["expected"][1])
+        lines.append("%s (%s)" % (head, what))
+    if c["wrapped_operand"]:
+        head = "%s: %d fetch%s from the ROM only by 2^32 in an immediate" % (fetcher, c["wrapped_operand"], " differs" if c["wrapped_operand"] == 1 else "es differ")
+        if report.wrapped:
+            f = report.wrapped[0]
+            head += " (first row %d, pc %d, fields %s)" % (f["row"], f["pc"], ", ".join(program_field(j, short=True) for j in f["fields"]))
+        lines.append(head)
+    if c["unfetched_words"]:
+        shown = ", ".join("[%d, %d)" % r for r in report.unfetched[:4])
+        words = "%d of %d words never fetched%s" % (c["unfetched_words"], c["rom_len"], " (%s%s)" % (shown, ", .." if c["unfetched_ranges"] > min(4, len(report.unfetched)) else "") if shown else "")
+    else:
+        words = "all words fetched"
+    lines.append("%s: %d fetches of a %d-word ROM (%d table rows): %s, hottest pc %d (%d fetches), %d sequential, %d stay, %d jumps, pc %d to %d, %s" % (
+        fetcher, c["fetches"], c["rom_len"], c["table_rows"], words, c["hottest_pc"], c["hottest_count"], c["sequential"], c["stay"], c["jumps"], c["first_pc"], c["last_pc"],
+        "no finding" if not c["hard"] else "%d finding%s" % (c["hard"], "" if c["hard"] == 1 else "s")))
+    return lines
 
 
 def field_lines(report):
@@ -600,7 +664,9 @@ def main(argv=None):
     ap.add_argument("--lookup-buses", default="", help="check --domains: the buses that count as lookup tables instead of the structural rule, comma-separated (3 or g3: global bus 3, l0: local bus 0)")
     ap.add_argument("--memory", action="store_true", help="check: also the memory audit (the receives of the memory bus replayed as a memory: malformed records, duplicate static "
                     "records, reads that do not return the last write to their address, reads of a non-zero value from an address nobody wrote; definite faults: check exits 1 on a finding)")
-    ap.add_argument("--max-findings", type=int, default=64, help="check --memory: the findings listed (default 64, at most 2^20; the counts stay exact)")
+    ap.add_argument("--program", dest="program_audit", action="store_true", help="check: also the program audit (every cpu row's instruction held against the program ROM at its pc, the ROM's multiplicities against "
+                    "the fetch counts: the reference's commented-out program bus replayed; check exits 1 on a hard finding, fetches that differ only by 2^32 in an immediate are listed apart)")
+    ap.add_argument("--max-findings", type=int, default=64, help="check --memory, --program: the findings listed (default 64, at most 2^20; the counts stay exact)")
     ap.add_argument("--min-gate-windows", type=int, default=64, help="check --transitions: a gate that holds on fewer windows is counted but not audited (default 64)")
     ap.add_argument("--max-gates", type=int, default=256, help="check --transitions: the gates listed per chip, the ungated one included (default 256)")
     ap.add_argument("--step-sizes", default="1,-1,2", help="check --steps: 1 to 4 distinct step sizes, comma-separated integers mod p (as --step-sizes=1,-1,2)")
@@ -646,6 +712,7 @@ def main(argv=None):
                 dreport = va.domain_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_entries=1 << 20, chips=parse_chips(args.chips), max_bits=args.max_bits,
                                                lookup_buses=parse_lookup_buses(args.lookup_buses)) if args.domains else None
                 memreport = va.memory_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_findings=args.max_findings) if args.memory else None
+                progreport = va.program_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), rom_len=w.program_len, max_findings=args.max_findings) if args.program_audit else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -665,6 +732,7 @@ def main(argv=None):
                 qreport = prover.product_audit(main, prep, max_entries=1 << 20, max_terms=256, chips=parse_chips(args.chips)) if args.products else None
                 dreport = prover.domain_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips), max_bits=args.max_bits, lookup_buses=parse_lookup_buses(args.lookup_buses)) if args.domains else None
                 memreport = prover.memory_audit(main, prep, max_findings=args.max_findings) if args.memory else None
+                progreport = prover.program_audit(main, prep, rom_len=w.program_len, max_findings=args.max_findings) if args.program_audit else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -692,6 +760,8 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), domains=dreport.to_dict()))
             if memreport is not None:
                 text = json.dumps(dict(json.loads(text), memory=memreport.to_dict()))
+            if progreport is not None:
+                text = json.dumps(dict(json.loads(text), program=progreport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
@@ -699,9 +769,10 @@ def main(argv=None):
                     rank_lines(rreport) if rreport is not None else []) + (field_lines(freport) if freport is not None else []) + (
                     link_lines(lreport) if lreport is not None else []) + (step_lines(sreport) if sreport is not None else []) + (
                     invariant_lines(ireport) if ireport is not None else []) + (transition_lines(treport) if treport is not None else []) + (
-                    product_lines(qreport) if qreport is not None else []) + (domain_lines(dreport) if dreport is not None else []) + (memory_lines(memreport) if memreport is not None else []):
+                    product_lines(qreport) if qreport is not None else []) + (domain_lines(dreport) if dreport is not None else []) + (memory_lines(memreport) if memreport is not None else []) + (
+                    program_lines(progreport) if progreport is not None else []):
                 print(line)
-            return check_status(report.balanced, creport, memreport)
+            return check_status(report.balanced, creport, memreport, progreport)
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256
         rc = va.poseidon_round_constants(source=args.constants)
         prover = va.Prover(va.Machine.basic(), rc, device=args.device or 0, log_blowup=args.log_blowup, num_queries=args.queries, pow_bits=args.pow_bits,

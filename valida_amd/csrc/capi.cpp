@@ -82,6 +82,7 @@ struct vgpu_transition_report : audit_report {};
 struct vgpu_product_report : audit_report {};
 struct vgpu_domain_report : audit_report {};
 struct vgpu_memory_report : audit_report {};
+struct vgpu_program_report : audit_report {};
 struct vgpu_comm { std::shared_ptr<Prover> owner; std::unique_ptr<Comm> comm; };  // owner first: the communicator dies before its context
 static_assert(sizeof(vgpu_cpu_op_t) == sizeof(vk::TgCpuOp) && sizeof(vgpu_mem_op_t) == sizeof(vk::TgMemOp) && sizeof(vgpu_alu_op_t) == sizeof(vk::TgAluOp),
               "C ABI log records and their device images must match");
@@ -1283,6 +1284,32 @@ uint64_t vgpu_memory_report_len(const vgpu_memory_report_t* r) { return report_l
 const uint32_t* vgpu_memory_report_words(const vgpu_memory_report_t* r) { return report_words(r); }
 void vgpu_memory_report_timing(const vgpu_memory_report_t* r, double out[3]) { report_timing(r, out, 3); }
 void vgpu_memory_report_free(vgpu_memory_report_t* r) { delete r; }
+
+// ---- program audit (host/program_audit.hpp) ----
+static_assert(sizeof(vgpu_program_audit_opts_t) == 104, "vgpu_program_audit_opts_t has no padding");
+static ProgramAuditOpts program_opts(const vgpu_program_audit_opts_t* o) {
+    ProgramAuditOpts r;  // a null pointer: the defaults (the BasicMachine's cpu and program chips, the table's height, 64 and 64); a struct is taken as given
+    if (o) {
+        r.fetch_chip = o->fetch_chip; r.pc_col = o->pc_col; r.n_fields = o->n_fields; r.table_chip = o->table_chip; r.key_col = o->key_col;
+        for (int j = 0; j < 8; j++) { r.field_cols[j] = o->field_cols[j]; r.table_cols[j] = o->table_cols[j]; }
+        r.mult_col = o->mult_col; r.rom_len = o->rom_len; r.max_findings = o->max_findings; r.max_ranges = o->max_ranges; r.reserved = o->reserved;
+    }
+    return r;
+}
+int32_t vgpu_program_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                           uint32_t n_prep, const vgpu_program_audit_opts_t* opts, vgpu_program_report_t** out) {
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->program_audit(m, pr, program_opts(opts)); });
+}
+int32_t vgpu_program_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                                const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                                const vgpu_program_audit_opts_t* opts, vgpu_program_report_t** out) {
+    return audit_on_host<BusHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                        [&](auto&... a) { return program_audit_host(a..., program_opts(opts)); });
+}
+uint64_t vgpu_program_report_len(const vgpu_program_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_program_report_words(const vgpu_program_report_t* r) { return report_words(r); }
+void vgpu_program_report_timing(const vgpu_program_report_t* r, double out[3]) { report_timing(r, out, 3); }
+void vgpu_program_report_free(vgpu_program_report_t* r) { delete r; }
 
 // ---- coverage audit (host/coverage_audit.hpp) ----
 static_assert(sizeof(vgpu_coverage_audit_opts_t) == 40, "vgpu_coverage_audit_opts_t has no padding");

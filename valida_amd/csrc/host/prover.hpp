@@ -21,6 +21,7 @@
 #include "product_audit.hpp"
 #include "domain_audit.hpp"
 #include "memory_audit.hpp"
+#include "program_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -184,6 +185,10 @@ class Prover {
     // of the slots, a max-scan for the last write, one judged sweep) and the records that break it; queued on the context like the other audits,
     // scratch from the pool.
     MemoryReport memory_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const MemoryAuditOpts& opts);
+    // Program audit of a witness (host/program_audit.hpp, kernels/program_audit.hip): the fetching chip's rows held against the table chip's
+    // preprocessed ROM (an LDS histogram of the pcs, one judged sweep over the fetches, one over the table) and the fetches and multiplicities
+    // that break the would-be program bus; queued on the context like the other audits, scratch from the pool.
+    ProgramReport program_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const ProgramAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

@@ -1868,4 +1868,77 @@ MemoryReport Prover::memory_audit(const std::vector<const DeviceTrace*>& main, c
     return rep;
 }
 
+// ---- program audit (host/program_audit.hpp; kernels/program_audit.hip) ----------------------------------------------------------------------
+ProgramReport Prover::program_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const ProgramAuditOpts& o) {
+    const auto t_host = Clock::now();
+    const auto tr = audit_traces<BusShape>("program_audit", main, preprocessed);
+    const ProgramPlan plan = program_audit_plan(machine_, tr.ms, tr.prep_chips, tr.ps, o);
+    ProgramReport rep;
+    program_audit_header(rep, plan, o);
+    const uint64_t H = plan.fetches, T = plan.table_rows, nbj = (H + 255) / 256, nbt = (T + 255) / 256;
+
+    DeviceCtx& c = *ctx_;
+    AuditPass pass(c, 3);
+    const hipStream_t st = pass.stream;
+    size_t listed_hard = 0, listed_wrapped = 0, listed_ranges = 0;
+    audit_or_no_memory(st, [&] {
+        // only the fetching chip's main trace and the table chip's two traces are read
+        vk::PgArgs a{};
+        const vk::DMatView fv = pass.working(main[o.fetch_chip]);
+        const vk::DMatView tv = o.table_chip == o.fetch_chip ? fv : pass.working(main[o.table_chip]);
+        const vk::DMatView pv = pass.working(preprocessed[(size_t)plan.table_prep].second);
+        c.check_launch("program_audit ingest");
+        a.fmain = fv.data; a.fstride = fv.stride; a.H = H;
+        a.tmain = tv.data; a.tmstride = tv.stride; a.tprep = pv.data; a.tpstride = pv.stride;
+        a.T = (uint32_t)T; a.rom_len = plan.rom_len; a.n_fields = o.n_fields; a.pc_col = o.pc_col; a.key_col = o.key_col; a.mult_col = o.mult_col;
+        a.lds_table = vk::program_audit_lds_table(o.n_fields, T) ? 1u : 0u;
+        for (int j = 0; j < 8; j++) { a.field_cols[j] = o.field_cols[j]; a.table_cols[j] = o.table_cols[j]; }
+        // the totals (u64) and the fetch counts behind them, zeroed by one memset; the workgroup tables are written whole by the counting passes
+        constexpr size_t TOT_WORDS = 2 * vk::PG_TOT;
+        DBuf zeroed(&c, TOT_WORDS + (size_t)T), tabs(&c, (size_t)(2 * nbj + 4 * nbt));
+        unsigned long long* tot = (unsigned long long*)zeroed.data;
+        uint32_t* counts = zeroed.data + TOT_WORDS;
+        uint32_t* hard_tab = tabs.data;
+        uint32_t* wrap_tab = tabs.data + nbj;
+        uint32_t* ttabs = tabs.data + 2 * nbj;
+        pass.begin();
+        VG_HIP_CHECK(hipMemsetAsync(zeroed.data, 0, zeroed.words * 4, st));
+        vk::launch_pg_hist(st, a.fmain + (uint64_t)a.pc_col * a.fstride, H, a.T, counts);
+        vk::launch_pg_judge(st, a, vk::PG_COUNT, tot, hard_tab, wrap_tab, 0, 0, 0, nullptr, nullptr);
+        vk::launch_pg_table(st, a, vk::PG_COUNT, counts, tot, ttabs, 0, 0, 0, nullptr, nullptr);
+        c.check_launch("program_audit count");
+        std::vector<uint32_t> tw(TOT_WORDS, 0);
+        c.download_small(tw.data(), zeroed.data, TOT_WORDS * 4);
+        unsigned long long th[vk::PG_TOT];
+        for (uint32_t k = 0; k < vk::PG_TOT; k++) th[k] = audit_u64(tw, k);
+        const uint64_t n_key = th[8], n_fetch = th[3] + th[4], n_mult = th[9];
+        listed_hard = (size_t)std::min<uint64_t>(n_key + n_fetch + n_mult, o.max_findings);
+        listed_wrapped = (size_t)std::min<uint64_t>(th[5], o.max_findings);
+        listed_ranges = (size_t)std::min<uint64_t>(th[11], o.max_ranges);
+        std::vector<uint32_t> ow((listed_hard + listed_wrapped) * vk::PG_OUT + 2 * listed_ranges);
+        if (!ow.empty()) {
+            DBuf out(&c, ow.size());
+            uint32_t* out_wrap = out.data + listed_hard * vk::PG_OUT;
+            uint32_t* ranges = out_wrap + listed_wrapped * vk::PG_OUT;
+            // a section that starts at or past the limit lists nothing: its base is clamped to the limit
+            const uint32_t hard_base = (uint32_t)std::min<uint64_t>(n_key, listed_hard), mult_base = (uint32_t)std::min<uint64_t>(n_key + n_fetch, listed_hard);
+            if (listed_wrapped || hard_base < listed_hard)
+                vk::launch_pg_judge(st, a, vk::PG_LIST, tot, hard_tab, wrap_tab, hard_base, (uint32_t)listed_hard, (uint32_t)listed_wrapped, out.data, out_wrap);
+            if (listed_ranges || (listed_hard && (n_key || mult_base < listed_hard)))
+                vk::launch_pg_table(st, a, vk::PG_LIST, counts, tot, ttabs, mult_base, (uint32_t)listed_hard, (uint32_t)listed_ranges, out.data, ranges);
+            c.check_launch("program_audit list");
+            c.download_small(ow.data(), out.data, ow.size() * 4);
+        }
+        program_audit_from_device(rep, th, ow.data(), listed_hard, listed_wrapped, ow.data() + (listed_hard + listed_wrapped) * vk::PG_OUT, listed_ranges);
+        pass.end(rep);
+    }, [&] {
+        return std::string("program_audit: the device pool cannot give the pass its scratch: 4 bytes for each of the " + std::to_string(T) + " table rows (the fetch counts) = " +
+                           std::to_string(4 * T) + " bytes, " + std::to_string(8 * vk::PG_TOT) + " bytes of totals, 4 bytes for each of the " + std::to_string(2 * nbj + 4 * nbt) +
+                           " workgroup table entries (2 per 256 fetches, 4 per 256 table rows) = " + std::to_string(4 * (2 * nbj + 4 * nbt)) + " bytes, 80 per listed finding (" +
+                           std::to_string(listed_hard + listed_wrapped) + "), 8 per listed range (" + std::to_string(listed_ranges) + "), plus the working-layout copies of uploaded traces");
+    });
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 }  // namespace vhost

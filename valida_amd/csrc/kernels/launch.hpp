@@ -458,6 +458,30 @@ void launch_mm_scan(hipStream_t st, uint32_t* mark, uint64_t n_live, uint32_t* b
 // MM_COUNT: the counters and the findings per workgroup; MM_LIST (after it): scans the table in place and lists the first max_findings
 void launch_mm_judge(hipStream_t st, uint32_t mode, const uint32_t* rec, const uint32_t* ids, const uint32_t* incl, const uint32_t* block_before, uint64_t n_live, uint64_t n,
                      unsigned long long* cnt, uint32_t* table, uint32_t max_findings, uint32_t* out);
+// the memory audit's one-workgroup scan on its own: `a` [total] becomes its exclusive maximum (is_max) or sum, in place
+void launch_mm_scan_words(hipStream_t st, uint32_t* a, uint64_t total, int is_max);
+// program_audit.hip — the passes of the program audit (host/program_audit.hpp: contract; Prover::program_audit drives them).  The traces are
+// working-layout views (column-major Montgomery): fmain the fetching chip's main trace [H rows], tmain / tprep the table chip's main and
+// preprocessed traces [T rows].  counts: [T] u32 (zeroed); tot: [PG_TOT] u64 (zeroed); hard_tab, wrap_tab: [ceil(H / 256)]; tabs:
+// [4][ceil(T / 256)]; out: [listed][PG_OUT] u32; ranges: [listed][2].
+constexpr uint32_t PG_SLICE = 32768, PG_HIST_RUN = 4096, PG_TOT = 16, PG_OUT = 20, PG_LDS_TABLE_WORDS = 2048;
+enum : uint32_t { PG_COUNT = 0, PG_LIST = 1 };
+struct PgArgs {
+    const uint32_t* fmain; uint64_t fstride, H;
+    const uint32_t* tmain; uint64_t tmstride;
+    const uint32_t* tprep; uint64_t tpstride;
+    uint32_t T, rom_len, n_fields, pc_col, key_col, mult_col, lds_table, pad;
+    uint32_t field_cols[8], table_cols[8];
+};
+// whether the judge stages the table's word columns in LDS: (n_fields + 1) * T words within PG_LDS_TABLE_WORDS.  A workgroup gathers at most
+// 256 * n_fields words, so a copy much larger than that costs more than the gathers it saves.
+bool program_audit_lds_table(uint32_t n_fields, uint64_t T);
+void launch_pg_hist(hipStream_t st, const uint32_t* pc_col, uint64_t H, uint32_t T, uint32_t* counts);
+// PG_COUNT: the counters and the two tables; PG_LIST (after it): scans the tables in place and lists
+void launch_pg_judge(hipStream_t st, const PgArgs& a, uint32_t mode, unsigned long long* tot, uint32_t* hard_tab, uint32_t* wrap_tab, uint32_t hard_base, uint32_t max_hard,
+                     uint32_t max_wrapped, uint32_t* out_hard, uint32_t* out_wrap);
+void launch_pg_table(hipStream_t st, const PgArgs& a, uint32_t mode, const uint32_t* counts, unsigned long long* tot, uint32_t* tabs, uint32_t mult_base, uint32_t max_hard,
+                     uint32_t max_ranges, uint32_t* out_hard, uint32_t* ranges);
 // field_audit.hip — the passes of the field audit (host/field_audit.hpp: contract; Prover::field_audit drives them), per chip.  One wave per
 // trace row, one wave per workgroup, T rows per workgroup one after the other, NB workgroups.  A SLOT of a chip is (interaction, field) in
 // order, NS of them.  totals: u64 [0] live records, [1] floating fields, [2] rows with a floating field, [3 + m] live rows of interaction m,

@@ -278,6 +278,10 @@ void launch_mm_scan(hipStream_t st, uint32_t* mark, uint64_t n_live, uint32_t* b
     VK_LAUNCH(k_mm_scan_local, dim3(nb), dim3(256), 0, st, mark, n_live, block_before);
     VK_LAUNCH(k_mm_scan_blocks, dim3(1), dim3(256), 0, st, block_before, (uint64_t)nb, 1);
 }
+void launch_mm_scan_words(hipStream_t st, uint32_t* a, uint64_t total, int is_max) {
+    if (!total) return;
+    VK_LAUNCH(k_mm_scan_blocks, dim3(1), dim3(256), 0, st, a, total, is_max);
+}
 void launch_mm_judge(hipStream_t st, uint32_t mode, const uint32_t* rec, const uint32_t* ids, const uint32_t* incl, const uint32_t* block_before, uint64_t n_live, uint64_t n,
                      unsigned long long* cnt, uint32_t* table, uint32_t max_findings, uint32_t* out) {
     if (!n_live) return;
