@@ -290,6 +290,25 @@ int32_t vgpu_fri_fold(vgpu_prover_t* p, const uint32_t* f, uint64_t n, const uin
  * unspecified words; a butterfly item whose low / lowbits would index past the twiddle tables is refused. */
 int32_t vgpu_field_probe(vgpu_prover_t* p, uint32_t op, const uint32_t* operands, uint64_t operand_words, uint64_t n_items, uint32_t* results, uint64_t result_words);
 
+/* Test hook: poison the prover's HBM pool (vgpu_prover_trim's cache).  The pool clears nothing, so a recycled block holds the last contents of a
+ * buffer of the same size — usually the previous identical call's correct answer, which hides a stage that reads what it has not written.
+ * mode bit 0: every block the pool hands out, fresh or recycled, is filled with `word` first; bit 1: every block is filled at the moment it
+ * returns to the cache (a block released inside a fork/join section: at the join); 0 switches the hook off (the default; the only cost is
+ * then one branch per pool operation).  Each fill covers the whole rounded block and is synchronous: the device drains, hipMemsetD32, the device
+ * drains again — for tests, not for timed runs.  Takes effect with the next pool operation; VGPU_ERR_INVALID_ARG while a proof or an audit
+ * owns the context.  The library reads no environment variable for it (the Python binding reads VGPU_POOL_POISON when a Prover is created). */
+int32_t vgpu_prover_set_pool_poison(vgpu_prover_t* p, uint32_t mode, uint32_t word);
+/* Test hook: out = {blocks, bytes filled on allocation, blocks, bytes filled on release} since the context was created. */
+void vgpu_prover_pool_poison_stats(const vgpu_prover_t* p, uint64_t out[4]);
+/* Test hook, the positive control of the one above: takes a block of `bytes` bytes from the pool exactly as a stage would, downloads its first
+ * n_words words to out[0 .. n_words) and the LAST word of the rounded block to out[n_words], and releases it — a "stage" that reads before it
+ * writes, so under poison it must see the word.  out has room for n_words + 1 words; bytes >= 1 and 4 * n_words <= bytes (else
+ * VGPU_ERR_INVALID_ARG). */
+int32_t vgpu_prover_pool_peek(vgpu_prover_t* p, uint64_t bytes, uint32_t* out, uint64_t n_words);
+/* Test hook: with on != 0 every chunk of vgpu_verify_batch first fills the verifier's whole device buffer (which it keeps and reuses across
+ * chunks and batches) with `word`, by a memset on the verifier's stream in front of the chunk's copies. */
+int32_t vgpu_verifier_set_poison(vgpu_verifier_t* v, uint32_t on, uint32_t word);
+
 /* Machine::prove (basic/src/lib.rs:147-675).  main[i] = trace of chip i; preprocessed traces are given
  * with their chip indices in chip order (BasicMachine: program, range).
  * debug_flags: 1 = keep the per-chip intermediate matrices (vgpu_proof_debug_*); 2 = run check_constraints and

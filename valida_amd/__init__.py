@@ -698,6 +698,10 @@ class Verifier:
         """Proof words per device chunk (default 2^25): a batch is checked in chunks of at most this many words."""
         _check(lib().vgpu_verifier_set_chunk_words(self._h, ctypes.c_uint64(int(words))))
 
+    def set_poison(self, word=None):
+        """Test hook (vgpu_verifier_set_poison): with a word, every chunk first fills the verifier's whole reused device buffer with it; None = off."""
+        _check(lib().vgpu_verifier_set_poison(self._h, ctypes.c_uint32(0 if word is None else 1), ctypes.c_uint32(0 if word is None else int(word))))
+
     def verify_batch(self, proofs, preprocessed_commits=None):
         """proofs: list of word arrays; preprocessed_commits: one 8-word array per proof, or None for a machine without preprocessed traces.
         Returns one entry per proof: None if accepted, else the rejection message (as verify())."""
@@ -2336,6 +2340,21 @@ def _report_of(name):
 # a raw vgpu_X_audit(_host) call's handle as the audit's report (the tests of the options structs call the C entry points themselves)
 _rank_report, _step_report, _field_report, _link_report = _report_of("rank"), _report_of("step"), _report_of("field"), _report_of("link")
 
+def _pool_poison_from_env(environ):
+    """The pool-poison word of VGPU_POOL_POISON (decimal or 0x hex, 0 .. 2^32 - 1), or None when the variable is unset or empty (off)."""
+    text = environ.get("VGPU_POOL_POISON", "").strip()
+    if not text:
+        return None
+    hexa = text[:2] in ("0x", "0X")
+    digits = text[2:] if hexa else text
+    if not digits or any(ch not in ("0123456789abcdefABCDEF" if hexa else "0123456789") for ch in digits):  # no sign, no underscores, no spaces
+        raise ValueError("VGPU_POOL_POISON must be a 32-bit word in decimal or 0x hex, not %r" % text)
+    word = int(digits, 16 if hexa else 10)
+    if word > 0xFFFFFFFF:
+        raise ValueError("VGPU_POOL_POISON must be a 32-bit word (at most 0xFFFFFFFF), not %r" % text)
+    return word
+
+
 class Ticket:
     """An outstanding asynchronous proof (vgpu_prove_async); keeps its inputs alive until waited for."""
 
@@ -2374,9 +2393,12 @@ class Prover:
         lane_off, lane_min = os.environ.get("VGPU_DENSE_LANE", "1") == "0", os.environ.get("VGPU_DENSE_LANE_MIN_NODES", "").strip()
         if lane_min and not lane_min.isdigit():
             raise ValueError("VGPU_DENSE_LANE_MIN_NODES must be a number of leaf rows, not %r" % lane_min)
+        poison = _pool_poison_from_env(os.environ)  # a test switch (set_pool_poison), read once, here
         _check(lib().vgpu_prover_create(ctypes.byref(cfg), machine._h, ctypes.byref(self._h)))
         if lane_off or int(lane_min or 0) > 0:
             self.set_dense_lane(not lane_off, int(lane_min or 0))
+        if poison is not None:
+            self.set_pool_poison(poison)
 
     def set_dense_lane(self, on, min_nodes=0):
         """vgpu_prover_set_dense_lane: the device's dense lane on / off for this context; min_nodes > 0 = the smallest tree that takes it."""
@@ -2654,6 +2676,25 @@ class Prover:
         live, peak = ctypes.c_uint64(), ctypes.c_uint64()
         lib().vgpu_prover_memory(self._h, ctypes.byref(live), ctypes.byref(peak))
         return live.value, peak.value
+
+    def set_pool_poison(self, word=None, on_alloc=True, on_release=True):
+        """Test hook (vgpu_prover_set_pool_poison): fill every block the HBM pool hands out (on_alloc) and every block that returns to its cache
+        (on_release) with `word`, synchronously; word None = off.  Refused (VgpuError, code -1) while a proof or an audit owns the context."""
+        mode = 0 if word is None else (1 if on_alloc else 0) | (2 if on_release else 0)
+        _check(lib().vgpu_prover_set_pool_poison(self._h, ctypes.c_uint32(mode), ctypes.c_uint32(0 if word is None else int(word))))
+
+    def pool_poison_stats(self):
+        """(blocks, bytes filled on allocation, blocks, bytes filled on release) since this context was created."""
+        out = (ctypes.c_uint64 * 4)()
+        lib().vgpu_prover_pool_poison_stats(self._h, out)
+        return tuple(int(x) for x in out)
+
+    def pool_peek(self, nbytes, n_words):
+        """Test hook (vgpu_prover_pool_peek): take a block of nbytes from the pool as a stage would, read it before writing it, release it.
+        Returns (its first n_words words, the last word of the rounded block)."""
+        out = np.zeros(int(n_words) + 1, dtype=np.uint32)
+        _check(lib().vgpu_prover_pool_peek(self._h, ctypes.c_uint64(int(nbytes)), out.ctypes.data_as(c_u32p), ctypes.c_uint64(int(n_words))))
+        return out[:-1].copy(), int(out[-1])
 
     def lane_stats(self):
         """(trees of this context that entered the device's dense lane, those that waited for another context's event)."""

@@ -732,6 +732,8 @@ struct vgpu_verifier {
     uint32_t* buf_dev = nullptr;  // grown to the largest chunk
     uint64_t buf_words = 0;
     uint64_t chunk_words = VERIFY_CHUNK_WORDS_DEFAULT;
+    bool poison = false;  // test hook (vgpu_verifier_set_poison): the whole buffer is filled before every chunk's copies
+    uint32_t poison_word = 0;
     std::vector<std::string> messages;
     double host_ms = 0, device_ms = 0;
     ~vgpu_verifier() {
@@ -750,6 +752,7 @@ struct vgpu_verifier {
             buf_words = need;
         }
         uint32_t* flags_dev = buf_dev + c.total_words();
+        if (poison) VG_HIP_CHECK(hipMemsetD32Async((hipDeviceptr_t)buf_dev, (int)poison_word, buf_words, stream));
         for (const VerifyChunk::Span& sp : c.spans) VG_HIP_CHECK(hipMemcpyAsync(buf_dev + sp.at, sp.words, sp.n * 4, hipMemcpyHostToDevice, stream));
         VG_HIP_CHECK(hipMemcpyAsync(buf_dev + c.proof_words, c.buf.data(), c.buf.size() * 4, hipMemcpyHostToDevice, stream));
         vk::launch_verify_chunk(stream, c.args(buf_dev, flags_dev, fri.hash_kind, pos_dev, pos_sparse));
@@ -783,6 +786,13 @@ int32_t vgpu_verifier_set_chunk_words(vgpu_verifier_t* v, uint64_t chunk_words) 
     VG_TRY({
         if (!v || !chunk_words) throw std::invalid_argument("null verifier or zero chunk size");
         v->chunk_words = chunk_words;
+    })
+}
+int32_t vgpu_verifier_set_poison(vgpu_verifier_t* v, uint32_t on, uint32_t word) {
+    VG_TRY({
+        if (!v) throw std::invalid_argument("null verifier");
+        v->poison = on != 0;
+        v->poison_word = word;
     })
 }
 int32_t vgpu_verify_batch(vgpu_verifier_t* v, const uint32_t* const* proofs, const uint64_t* n_words, const uint32_t* preprocessed_commits, uint32_t n_proofs,
@@ -897,6 +907,40 @@ int32_t vgpu_field_probe(vgpu_prover_t* p, uint32_t op, const uint32_t* operands
         vk::launch_field_probe(c.stream, op, din.data, n_items, c.tables, c.poseidon_tab, c.poseidon_sparse, dout.data);
         c.check_launch("field probe");
         c.download(results, dout.data, result_words * 4);
+    })
+}
+
+// test hooks: the pool's poison (host/runtime.hpp: DeviceCtx::poison_mode)
+int32_t vgpu_prover_set_pool_poison(vgpu_prover_t* p, uint32_t mode, uint32_t word) {
+    VG_TRY({
+        if (!p) throw std::invalid_argument("null argument");
+        if (mode > 3) throw std::invalid_argument("pool poison: mode is bit 0 (on alloc) | bit 1 (on release)");
+        DeviceCtx& c = p->p->ctx();
+        std::unique_lock<std::mutex> owner(c.prove_mu, std::try_to_lock);  // a proof or an audit holds it for as long as it owns the context
+        if (!owner.owns_lock() || c.async_pending.load() > 0) throw std::invalid_argument("pool poison: a proof or an audit is running on this context");
+        std::lock_guard<std::mutex> lk(c.pool_mu);
+        c.poison_mode = mode;
+        c.poison_word = word;
+    })
+}
+void vgpu_prover_pool_poison_stats(const vgpu_prover_t* p, uint64_t out[4]) {
+    if (!p || !out) return;
+    DeviceCtx& c = const_cast<vgpu_prover_t*>(p)->p->ctx();
+    std::lock_guard<std::mutex> lk(c.pool_mu);
+    for (int i = 0; i < 4; i++) out[i] = c.poison_stats[i];
+}
+int32_t vgpu_prover_pool_peek(vgpu_prover_t* p, uint64_t bytes, uint32_t* out, uint64_t n_words) {
+    VG_TRY({
+        if (!p || !out) throw std::invalid_argument("null argument");
+        if (!bytes || n_words > bytes / 4) throw std::invalid_argument("pool peek: bytes >= 1 and 4 * n_words <= bytes");
+        DeviceCtx& c = p->p->ctx();
+        c.activate();
+        const size_t rounded = ((size_t)bytes + 255) & ~(size_t)255;  // DeviceCtx::alloc's rounding
+        DBuf b(&c, (size_t)((bytes + 3) / 4));
+        std::vector<uint32_t> w(n_words + 1);
+        if (n_words) c.download(w.data(), b.data, n_words * 4);
+        c.download(w.data() + n_words, b.data + rounded / 4 - 1, 4);
+        memcpy(out, w.data(), w.size() * 4);
     })
 }
 
@@ -1359,7 +1403,16 @@ int32_t vgpu_prove_async(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint
         for (uint32_t i = 0; i < n_prep; i++) { check_trace(p, prep[i], &job->foreign); job->prep.push_back(prep[i]->t); job->chips.push_back((int)prep_chips[i]); }
         drain(job->foreign);
         std::unique_ptr<vgpu_ticket> t(new vgpu_ticket());
-        t->result = std::async(std::launch::async, [job]() {
+        // counted from here, not from the worker's first instruction: the context is spoken for as soon as the ticket exists (vgpu_prover_set_pool_poison)
+        struct Pending {
+            DeviceCtx& c;
+            explicit Pending(DeviceCtx& x) : c(x) { c.async_pending.fetch_add(1); }
+            ~Pending() { c.async_pending.fetch_sub(1); }
+            Pending(const Pending&) = delete;
+        };
+        auto pending = std::make_shared<Pending>(job->prover->ctx());
+        t->result = std::async(std::launch::async, [job, pending]() mutable {
+            std::shared_ptr<Pending> done = std::move(pending);  // released when the worker returns, whatever becomes of the proof
             std::pair<int32_t, std::string> status{VGPU_OK, ""};
             vgpu_proof_t* proof = nullptr;
             try {

@@ -91,9 +91,15 @@ struct DeviceCtx {
     // The pool is shared by the thread that drives a proof (vgpu_prove_async's worker) and by whichever host thread frees a
     // handle meanwhile (vgpu_trace_free / vgpu_oplog_free / a garbage collector): every pool operation takes this lock.
     std::mutex pool_mu;
+    // Test hook (vgpu_prover_set_pool_poison), off by default: bit 0 fills every block alloc hands out, fresh or recycled,
+    // bit 1 every block at the moment it returns to free_blocks (a release deferred to a join: at the join), with poison_word.  A stage may
+    // assume nothing about a block it has not written; tests/test_pool_poison_gpu.py runs every stage with the pool made adversarial.
+    uint32_t poison_mode = 0, poison_word = 0;
+    uint64_t poison_stats[4] = {0, 0, 0, 0};  // blocks, bytes filled on alloc; blocks, bytes filled on release
     // Uploads handed in by a caller thread WHILE a proof owns the main stream (a host that prepares segment i+1 during proof i):
     // a stream of their own, created on first use, so the copy neither queues behind the proof's kernels nor shares its waits.
     std::atomic<int> proofs_running{0};
+    std::atomic<int> async_pending{0};  // tickets of vgpu_prove_async whose worker has not returned yet (it may not have reached prove_mu)
     // One proof at a time per context (its streams, pool sections and pinned buffers are not shared): callers QUEUE on this mutex — the
     // reference's `Machine: Sync` (machine/src/machine.rs:13) lets several threads call prove on one machine, and so may a host here.
     std::mutex prove_mu;
@@ -163,7 +169,25 @@ struct DeviceCtx {
         live_blocks[p] = bytes;
         live += bytes;
         if (live > peak_live) peak_live = live;
+        if (poison_mode & 1) {
+            if (!poison_fill_locked(p, bytes)) throw std::runtime_error("hip: the pool's poison fill failed");
+            poison_stats[0]++; poison_stats[1] += bytes;
+        }
         return p;
+    }
+    // Fill a whole (rounded) block with poison_word, synchronously, pool_mu held (as trim_locked holds it over its synchronisation): kernels
+    // enqueued before a release may still read the block, so the device drains first, and the fill has landed before anybody gets the block.
+    // Called from release(), hence from destructors on any thread: binds this context's device for the fill only and never throws.
+    bool poison_fill_locked(void* p, size_t bytes) noexcept {
+        int cur = -1;
+        if (hipGetDevice(&cur) != hipSuccess) { (void)hipGetLastError(); cur = -1; }
+        if (cur != device && hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return false; }
+        bool ok = hipDeviceSynchronize() == hipSuccess;
+        ok = ok && hipMemsetD32((hipDeviceptr_t)p, (int)poison_word, bytes / 4) == hipSuccess;
+        ok = ok && hipDeviceSynchronize() == hipSuccess;
+        if (!ok) (void)hipGetLastError();
+        if (cur >= 0 && cur != device) (void)hipSetDevice(cur);
+        return ok;
     }
     // Return every cached (free) block to the driver; live blocks are untouched.  Synchronises the device first: a cached
     // block may still be read by work in flight.
@@ -215,6 +239,7 @@ struct DeviceCtx {
             fprintf(stderr, "vgpu: release of unknown device block %p ignored\n", p);
             return;
         }
+        if ((poison_mode & 2) && poison_fill_locked(p, it->second)) { poison_stats[2]++; poison_stats[3] += it->second; }
         free_blocks.insert({it->second, p});
         live -= it->second;
         live_blocks.erase(it);
