@@ -150,6 +150,12 @@ void vgpu_prover_memory_reset_peak(vgpu_prover_t* p);
  * rows; `on` = 0 switches it off for this context, `min_nodes` > 0 sets the smallest tree that takes it (0 keeps the current value).  Takes
  * effect with the next proof.  (The Python binding calls this at context creation from VGPU_DENSE_LANE and VGPU_DENSE_LANE_MIN_NODES.) */
 void vgpu_prover_set_dense_lane(vgpu_prover_t* p, uint32_t on, uint64_t min_nodes);
+/* Constant columns: while vgpu_prove / vgpu_prove_async brings an uploaded main or preprocessed trace of more than 2^12 rows into the device layout it
+ * compares every row of every column with row 0, on the device and inside the proof, and the low-degree extension fills the columns found constant
+ * with that value instead of transforming them (the extension of a constant polynomial is the constant).  No proof word depends on it; proving TIME
+ * depends on which columns of the traces are constant.  On by default; `on` = 0 transforms every column.  Takes effect with the next proof.
+ * (The Python binding calls this at context creation from VGPU_CONST_COLS.) */
+void vgpu_prover_set_const_columns(vgpu_prover_t* p, uint32_t on);
 /* how many trees of this context entered the lane, and how many of those had to wait for ANOTHER context's event; both stay 0 with the lane off */
 void vgpu_prover_lane_stats(const vgpu_prover_t* p, uint64_t* entered, uint64_t* waited);
 
@@ -185,6 +191,12 @@ void vgpu_trace_free(vgpu_trace_t* t);
 /* pcs.commit_batches / commit_shifted_batches (basic/src/lib.rs:199,223,258,599): coset_shifts may be NULL */
 int32_t vgpu_commit_batches(vgpu_prover_t* p, const vgpu_trace_t* const* mats, uint32_t n_mats, const uint32_t* coset_shifts,
                             uint32_t root[8], vgpu_pdata_t** out);
+/* The main commitment round as vgpu_prove runs it, on its own (a test hook): uploaded row-major matrices only, no coset shifts; the ingest flags the
+ * columns in which some row differs from row 0 and — with vgpu_prover_set_const_columns on — the LDE of a matrix of more than 2^12 rows fills the
+ * unflagged columns instead of transforming them.  Root and LDEs are those of vgpu_commit_batches either way.  varies_out (may be NULL): the flags,
+ * one word per column, matrix after matrix (0 = constant column). */
+int32_t vgpu_commit_batches_flagged(vgpu_prover_t* p, const vgpu_trace_t* const* mats, uint32_t n_mats, uint32_t root[8], vgpu_pdata_t** out,
+                                    uint32_t* varies_out);
 /* pcs.get_ldes (basic/src/lib.rs:201,225,261): copy LDE `idx` back as row-major canonical, rows in
  * COMMITTED (bit-reversed) order; out must hold (height << log_blowup) * width words */
 int32_t vgpu_pdata_lde(vgpu_prover_t* p, const vgpu_pdata_t* pd, uint32_t idx, uint32_t* out, uint64_t cap_words);

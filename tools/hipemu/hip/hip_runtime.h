@@ -51,7 +51,10 @@ struct State {
     dim3 threadIdx, blockIdx, blockDim, gridDim;
 };
 inline State& st() { static State s; return s; }
-constexpr size_t STACK = 256 * 1024;
+#ifndef HIPEMU_STACK_BYTES  // a program built with AddressSanitizer pays for every switch in proportion to the fiber's stack (its shadow is cleared): it may ask for less
+#define HIPEMU_STACK_BYTES (256 * 1024)
+#endif
+constexpr size_t STACK = HIPEMU_STACK_BYTES;
 struct Fiber { ucontext_t ctx; char* stack = nullptr; bool done = false; };
 struct Sched {
     ucontext_t main;

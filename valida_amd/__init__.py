@@ -2397,8 +2397,14 @@ class Prover:
         _check(lib().vgpu_prover_create(ctypes.byref(cfg), machine._h, ctypes.byref(self._h)))
         if lane_off or int(lane_min or 0) > 0:
             self.set_dense_lane(not lane_off, int(lane_min or 0))
+        if os.environ.get("VGPU_CONST_COLS", "1") == "0":  # the constant-column switch (on in the library), read once, here: A/B runs, parity tests
+            self.set_const_columns(False)
         if poison is not None:
             self.set_pool_poison(poison)
+
+    def set_const_columns(self, on):
+        """vgpu_prover_set_const_columns: fill the constant columns of uploaded main / preprocessed traces in the LDE instead of transforming them."""
+        lib().vgpu_prover_set_const_columns(self._h, ctypes.c_uint32(1 if on else 0))
 
     def set_dense_lane(self, on, min_nodes=0):
         """vgpu_prover_set_dense_lane: the device's dense lane on / off for this context; min_nodes > 0 = the smallest tree that takes it."""
@@ -2436,6 +2442,16 @@ class Prover:
         h = ctypes.c_void_p()
         _check(lib().vgpu_commit_batches(self._h, arr, ctypes.c_uint32(len(traces)), sh, root.ctypes.data_as(c_u32p), ctypes.byref(h)))
         return ProverData(self, h, root, [t.shape for t in traces])
+
+    def commit_batches_flagged(self, traces):
+        """vgpu_commit_batches_flagged (a test hook): the main round's commitment as prove() runs it — constant columns found by the ingest and, with
+        the switch on, filled by the LDE.  Returns (ProverData, flags): flags[i][j] != 0 iff column j of matrix i is not constant."""
+        arr = (ctypes.c_void_p * len(traces))(*[t._h for t in traces])
+        root = np.zeros(8, dtype=np.uint32)
+        varies = np.zeros(sum(t.shape[1] for t in traces), dtype=np.uint32)
+        h = ctypes.c_void_p()
+        _check(lib().vgpu_commit_batches_flagged(self._h, arr, ctypes.c_uint32(len(traces)), root.ctypes.data_as(c_u32p), ctypes.byref(h), varies.ctypes.data_as(c_u32p)))
+        return ProverData(self, h, root, [t.shape for t in traces]), np.split(varies, np.cumsum([t.shape[1] for t in traces])[:-1])
 
     def generate_permutation_trace(self, chip, main, challenges, preprocessed=None):
         info = self.machine.chip_info(chip)

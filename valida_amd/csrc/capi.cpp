@@ -365,6 +365,12 @@ void vgpu_prover_memory(const vgpu_prover_t* p, uint64_t* live, uint64_t* peak) 
     if (live) *live = c.live;
     if (peak) *peak = c.peak_live;
 }
+void vgpu_prover_set_const_columns(vgpu_prover_t* p, uint32_t on) {
+    if (!p) return;
+    DeviceCtx& c = p->p->ctx();
+    std::lock_guard<std::mutex> lk(c.prove_mu);  // between proofs: a running proof keeps the setting it started with
+    c.const_cols_on = on != 0;
+}
 void vgpu_prover_set_dense_lane(vgpu_prover_t* p, uint32_t on, uint64_t min_nodes) {
     if (!p) return;
     DeviceCtx& c = p->p->ctx();
@@ -576,6 +582,41 @@ int32_t vgpu_commit_batches(vgpu_prover_t* p, const vgpu_trace_t* const* mats, u
         pd->owner = p->p;
         pd->pd = commit_batches(&c, in, coset_shifts ? &shifts : nullptr, p->p->fri());
         memcpy(root, pd->pd->tree.root, 32);
+        *out = pd.release();
+    })
+}
+int32_t vgpu_commit_batches_flagged(vgpu_prover_t* p, const vgpu_trace_t* const* mats, uint32_t n_mats, uint32_t root[8], vgpu_pdata_t** out, uint32_t* varies_out) {
+    VG_TRY({
+        if (!p || !mats || !n_mats || !root || !out) throw std::invalid_argument("null argument");
+        DeviceCtx& c = p->p->ctx();
+        c.activate();
+        size_t words = 0;
+        for (uint32_t i = 0; i < n_mats; i++) {
+            if (!mats[i] || mats[i]->owner != p->p) throw std::invalid_argument("null trace or trace of another prover");
+            const DeviceTrace& t = *mats[i]->t;
+            if (!t.nat.empty()) throw std::invalid_argument("commit_batches_flagged: uploaded (row-major) matrices only");
+            if (t.height == 0 || (t.height & (t.height - 1))) throw std::invalid_argument("matrix height must be a power of two");
+            words += t.width;
+        }
+        // as Prover::prove: one pool block of flags, zeroed on the stream in front of the ingests, handed to the LDE when the switch is on
+        DBuf flags(&c, words);
+        VG_HIP_CHECK(hipMemsetAsync(flags.data, 0, words * 4, c.stream));
+        std::vector<DMat> nat;
+        std::vector<CommitInput> in;
+        size_t off = 0;
+        for (uint32_t i = 0; i < n_mats; i++) {
+            const DeviceTrace& t = *mats[i]->t;
+            nat.emplace_back(&c, t.height, t.width);
+            vk::launch_ingest(c.stream, t.raw.data, nat.back().view(), false, flags.data + off);
+            off += t.width;
+        }
+        off = 0;
+        for (uint32_t i = 0; i < n_mats; i++) { in.push_back({&nat[i], false, false, c.const_cols_on ? flags.data + off : nullptr}); off += nat[i].width; }
+        std::unique_ptr<vgpu_pdata> pd(new vgpu_pdata());
+        pd->owner = p->p;
+        pd->pd = commit_batches(&c, in, nullptr, p->p->fri());
+        memcpy(root, pd->pd->tree.root, 32);
+        if (varies_out) c.download(varies_out, flags.data, words * 4);
         *out = pd.release();
     })
 }

@@ -226,10 +226,14 @@ struct ProverData {
 // One matrix handed to commit: column-major evaluations over H_n with rows in natural order, or already
 // at bit-reversed positions (`rows_bitrev`).  `consume`: the buffer may be used as the coefficient
 // scratch and released (only meaningful with rows_bitrev); otherwise it is left untouched.
+// `varies` (optional, natural-order input only): the device flags vk::launch_ingest left for this matrix on the stream its LDE runs on (or on one that
+// stream waits for) — columns whose flag is 0 are constant and are filled, not transformed (heights above 2^12; ignored below).  nullptr = every
+// column is transformed.
 struct CommitInput {
     DMat* mat;
     bool rows_bitrev;
     bool consume;
+    const uint32_t* varies = nullptr;
 };
 
 // Returns the bit-reversed LDE on lde_shift * H_{n << log_blowup}.
@@ -249,10 +253,16 @@ inline DMat coset_lde(DeviceCtx* c, hipStream_t st, const CommitInput& in, unsig
         // measured in round 5 and sped up no pass at any size: profiles/r05_ab_session1_standin_groups_quotient.txt.)
         DMat s1, s2;
         if (k > 12) { s1 = DMat(c, n, in.mat->width); s2 = DMat(c, n * b, in.mat->width); }
+        // constant columns (flags from the ingest): the column map is built on the device, on this stream — the host never learns the counts
+        DBuf colmap;
+        if (in.varies && k > 12) {
+            colmap = DBuf(c, vk::lde_colmap_words(in.mat->width));
+            vk::launch_lde_colmap(st, in.varies, in.mat->width, colmap.data);
+        }
         vk::launch_lde_natural(st, in.mat->view(), lde.view(), (int)log_blowup, c->tables, lt, s1.empty() ? vk::DMatView{nullptr, 0, 0, 0} : s1.view(),
-                               s2.empty() ? vk::DMatView{nullptr, 0, 0, 0} : s2.view());
+                               s2.empty() ? vk::DMatView{nullptr, 0, 0, 0} : s2.view(), colmap.data);
         c->check_launch("coset_lde");
-        return lde;  // s1 / s2 return to the pool while the kernels may still be queued: safe for the same reason as `coeffs` below
+        return lde;  // s1 / s2 / colmap return to the pool while the kernels may still be queued: safe for the same reason as `coeffs` below
     }
     DMat coeffs;
     if (in.rows_bitrev && in.consume) coeffs = std::move(*in.mat);

@@ -331,6 +331,23 @@ std::vector<uint32_t> Prover::prove(const std::vector<const DeviceTrace*>& main,
     std::vector<unsigned> log_deg(NC);
     std::vector<DMat> main_own(NC);
     std::vector<const DMat*> main_nat(NC);
+    // Constant columns (kernels/ntt.hip: k_lde_colmap): the ingest of a trace whose LDE takes three passes also flags the columns in which some row
+    // differs from row 0; the commitment below hands the flags to the LDE, which fills the unflagged columns instead of transforming them.  One pool
+    // block for all of them, zeroed on the main stream in front of the fork — inside this proof: an uploaded trace carries nothing from outside it.
+    const size_t NO_FLAGS = (size_t)-1;
+    std::vector<size_t> main_flags(NC, NO_FLAGS), prep_flags(preprocessed.size(), NO_FLAGS);
+    size_t flag_words = 0;
+    auto wants_flags = [&](const DeviceTrace* t) { return c.const_cols_on && t->nat.empty() && t->height > (1ull << 12) && t->width <= vk::INGEST_FLAGS_MAX_WIDTH; };
+    for (size_t i = 0; i < NC; i++)
+        if (wants_flags(main[i])) { main_flags[i] = flag_words; flag_words += main[i]->width; }
+    for (size_t k = 0; k < preprocessed.size(); k++)
+        if (wants_flags(preprocessed[k].second)) { prep_flags[k] = flag_words; flag_words += preprocessed[k].second->width; }
+    DBuf flags;
+    if (flag_words) {
+        flags = DBuf(&c, flag_words);
+        VG_HIP_CHECK(hipMemsetAsync(flags.data, 0, flag_words * 4, c.stream));
+    }
+    auto flags_at = [&](size_t off) -> uint32_t* { return off == NO_FLAGS ? nullptr : flags.data + off; };
     Section ingest_section(&c);
     for (size_t i = 0; i < NC; i++) {
         if (main[i]->width != machine_.airs[i].width) throw std::invalid_argument("prove: trace width mismatch for chip " + machine_.airs[i].name);
@@ -340,7 +357,7 @@ std::vector<uint32_t> Prover::prove(const std::vector<const DeviceTrace*>& main,
         if (!main[i]->nat.empty()) { main_nat[i] = &main[i]->nat; continue; }  // generated on the device: already in working layout
         main_own[i] = DMat(&c, h, main[i]->width);
         main_nat[i] = &main_own[i];
-        vk::launch_ingest(c.stream_for(i, h), main[i]->raw.data, main_own[i].view(), false);
+        vk::launch_ingest(c.stream_for(i, h), main[i]->raw.data, main_own[i].view(), false, flags_at(main_flags[i]));
     }
     std::vector<std::pair<int, uint64_t>> prep_key;
     for (auto& pr : preprocessed) prep_key.emplace_back(pr.first, pr.second->uid);
@@ -362,7 +379,7 @@ std::vector<uint32_t> Prover::prove(const std::vector<const DeviceTrace*>& main,
         if (!t->nat.empty())  // a device-resident working-layout trace handed in as preprocessed: copy, never read the (absent) raw image
             VG_HIP_CHECK(hipMemcpyAsync(prep_nat[k].data, t->nat.data, t->height * t->width * 4, hipMemcpyDeviceToDevice, c.stream_for(k, t->height)));
         else
-            vk::launch_ingest(c.stream_for(k, t->height), t->raw.data, prep_nat[k].view(), false);
+            vk::launch_ingest(c.stream_for(k, t->height), t->raw.data, prep_nat[k].view(), false, flags_at(prep_flags[k]));
     }
     ingest_section.join();
     c.check_launch("ingest");
@@ -378,11 +395,11 @@ std::vector<uint32_t> Prover::prove(const std::vector<const DeviceTrace*>& main,
     std::vector<CommitInput> prep_in;
     const bool ride = !prep_nat.empty() && !prep_hit;
     if (ride)
-        for (auto& m : prep_nat) prep_in.push_back({&m, false, false});
+        for (size_t k = 0; k < prep_nat.size(); k++) prep_in.push_back({&prep_nat[k], false, false, flags_at(prep_flags[k])});  // (ride = every one was ingested or copied above)
     std::unique_ptr<ProverData> main_pd;
     {
         std::vector<CommitInput> in;
-        for (auto m : main_nat) in.push_back({const_cast<DMat*>(m), false, false});  // consume = false: never modified
+        for (size_t i = 0; i < NC; i++) in.push_back({const_cast<DMat*>(main_nat[i]), false, false, flags_at(main_flags[i])});  // consume = false: never modified
         const CommitRider rider{&prep_in, &prep_pd_cache_};
         main_pd = commit_batches(&c, in, nullptr, fri_, ride ? &rider : nullptr);
     }

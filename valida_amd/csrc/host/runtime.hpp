@@ -87,6 +87,9 @@ struct DeviceCtx {
     std::atomic<uint64_t> lane_entered{0}, lane_waited{0};  // vgpu_prover_lane_stats
     static const DeviceCtx*& lane_thread_ctx() { static thread_local const DeviceCtx* c = nullptr; return c; }
     bool lane_open_here() const { return lane_on && lane && lane_thread_ctx() == this; }
+    // Constant columns of the main and preprocessed traces are filled, not transformed, by the LDE (Prover::prove; kernels/ntt.hip: k_lde_colmap).
+    // vgpu_prover_set_const_columns, set between proofs (the switch of the A/B and of the parity tests).  No proof word depends on it.
+    bool const_cols_on = true;
     std::vector<void*> deferred;  // blocks released inside a section return to the pool at the join
     // The pool is shared by the thread that drives a proof (vgpu_prove_async's worker) and by whichever host thread frees a
     // handle meanwhile (vgpu_trace_free / vgpu_oplog_free / a garbage collector): every pool operation takes this lock.

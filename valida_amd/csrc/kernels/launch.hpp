@@ -66,7 +66,10 @@ inline unsigned interp_lds_threads(uint32_t n_regs) {
 }
 
 // layout.hip
-void launch_ingest(hipStream_t st, const uint32_t* src_dev, DMatView dst, bool bitrev);
+// varies (optional, dst.width words, ZEROED on `st` before this launch): varies[j] = 1 afterwards iff some row of column j differs from row 0
+// — every row is compared, as field elements; the constant-column detection of the fused LDE (launch_lde_colmap).  Widths up to ingest_flags_max_width.
+void launch_ingest(hipStream_t st, const uint32_t* src_dev, DMatView dst, bool bitrev, uint32_t* varies = nullptr);
+constexpr uint64_t INGEST_FLAGS_MAX_WIDTH = 512;  // one more LDS row (the Montgomery forms of row 0) beside the 64-row tile
 void launch_bitrev_rows(hipStream_t st, DMatView src, DMatView dst);
 void launch_clock_probe(hipStream_t st, uint64_t* out3, uint32_t iters);  // out3: page-locked host memory (device-visible); see vgpu_shader_clock_probe
 // n_cols columns of Wq = 2^log_wq blocks of `rows` rows (block r in the natural order of the sub-coset bitrev(r)) -> columns in global natural order
@@ -89,7 +92,15 @@ void launch_field_probe(hipStream_t st, uint32_t op, const uint32_t* in_dev, uin
 void launch_intt(hipStream_t st, DMatView m, const DeviceTables& tb);
 void launch_coset_ntt(hipStream_t st, DMatView coeffs, DMatView dst, uint64_t dst_row0, Fp shift, const DeviceTables& tb);
 // natural-order evaluations -> committed (bit-reversed) LDE in 3 fused passes (1 for heights <= 2^12); lt: build_lde_tables(k, log_blowup, shift)
-void launch_lde_natural(hipStream_t st, DMatView nat, DMatView lde, int log_blowup, const DeviceTables& tb, const LdeTables& lt, DMatView s1, DMatView s2);
+// colmap (optional; heights above 2^12 only, ignored below): the column map launch_lde_colmap wrote on `st` — the passes transform its live columns
+// only (the scratch matrices used compactly) and k_lde_fill_const fills every constant column of `lde` with the column's row 0.  nullptr = every column.
+void launch_lde_natural(hipStream_t st, DMatView nat, DMatView lde, int log_blowup, const DeviceTables& tb, const LdeTables& lt, DMatView s1, DMatView s2,
+                        const uint32_t* colmap = nullptr);
+// The column map of a `width`-column matrix, 2 + 2 width words: [live_count, const_count, live[0 .. width) ascending, const[0 .. width) ascending]
+// (only the first live_count / const_count entries of each list are written).  One workgroup, from the flags launch_ingest left in `varies`.
+constexpr uint32_t COLMAP_LIVE_COUNT = 0, COLMAP_CONST_COUNT = 1, COLMAP_LIVE = 2;  // const[] starts at COLMAP_LIVE + width
+inline size_t lde_colmap_words(uint64_t width) { return 2 + 2 * (size_t)width; }
+void launch_lde_colmap(hipStream_t st, const uint32_t* varies, uint64_t width, uint32_t* colmap);
 // verify.hip: the per-query checks of a chunk of Machine::verify plans (k_verify_open, k_verify_fold, k_verify_tree in that order on `st`)
 void launch_verify_chunk(hipStream_t st, const VerifyChunkArgs& a);
 // merkle.hip

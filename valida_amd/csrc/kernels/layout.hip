@@ -14,8 +14,19 @@ thread_local ProfScope* g_scope = nullptr;
 // basic/src/lib.rs:223).  dst: column-major Montgomery; row r lands at position bitrev(r) if `bitrev`
 // (the in-place DIT inverse NTT wants bit-reversed-position input) else at r.
 // One block handles 64 destination rows x all columns.
-__global__ void k_ingest(const uint32_t* __restrict__ src, DMatView dst, int log_h, int bitrev) {
-    extern __shared__ uint32_t lds[];  // [64][width | 1]
+// varies (optional, one word per column, zeroed before the launch): set to 1 for every column in which some row differs from row 0 of the matrix.
+// The comparison rides on the column-major store below, where a wave holds 64 rows of ONE column: a compare per element against the Montgomery
+// form of row 0 (one more LDS row, a broadcast read), one ballot per wave and at most one store per wave, by its first lane — every writer writes
+// the same value.  nullptr: no flags, the code below is the plain ingest.
+__device__ __forceinline__ bool wave_any_elected(bool pred) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_ballot_w64(pred) != 0 && (threadIdx.x & 63) == 0;  // all 64 lanes are in the loop: rows come in whole waves
+#else
+    return pred;  // host pass / emulation: every thread its own wave
+#endif
+}
+__global__ void k_ingest(const uint32_t* __restrict__ src, DMatView dst, int log_h, int bitrev, uint32_t* varies) {
+    extern __shared__ uint32_t lds[];  // [64][width | 1], and with `varies` one more row: row 0 of the matrix in Montgomery form
     const int W = (int)dst.width, LD = W | 1;  // odd row stride: conflict-free column reads
     const uint64_t j0 = (uint64_t)blockIdx.x * 64;
     const int rows = (int)((dst.height - j0) < 64 ? (dst.height - j0) : 64);
@@ -52,10 +63,22 @@ __global__ void k_ingest(const uint32_t* __restrict__ src, DMatView dst, int log
             for (int c = lane; c < W; c += 64) lds[jr * LD + c] = Fp::from_canonical(row[c]).v;
         }
     }
+    if (varies)
+        for (int c = threadIdx.x; c < W; c += blockDim.x) lds[64 * LD + c] = Fp::from_canonical(src[c]).v;  // row 0 sits at position 0 in either row order
     __syncthreads();
+    if (!varies) {
+        for (int e = threadIdx.x; e < W * 64; e += blockDim.x) {
+            int jr = e & 63, c = e >> 6;
+            if (jr < rows) dst.data[(uint64_t)c * dst.stride + j0 + jr] = lds[jr * LD + c];
+        }
+        return;
+    }
     for (int e = threadIdx.x; e < W * 64; e += blockDim.x) {
         int jr = e & 63, c = e >> 6;
-        if (jr < rows) dst.data[(uint64_t)c * dst.stride + j0 + jr] = lds[jr * LD + c];
+        const uint32_t first = lds[64 * LD + c];
+        const uint32_t v = jr < rows ? lds[jr * LD + c] : first;
+        if (jr < rows) dst.data[(uint64_t)c * dst.stride + j0 + jr] = v;
+        if (wave_any_elected(v != first)) varies[c] = 1;
     }
 }
 
@@ -114,6 +137,7 @@ void launch_interleave_blocks(hipStream_t st, const uint32_t* src, uint32_t* dst
 }
 
 // vgpu_shader_clock_probe: shader cycles (s_memtime) against the constant 100 MHz clock over a chain of dependent VALU additions
+#ifdef __HIPCC__  // (device instructions and clocks: not part of the host emulation of this file, tests/emu/lde_colmap_emu.cpp)
 __global__ void k_clock_probe(uint64_t* out, uint32_t iters) {
     const uint64_t c0 = __builtin_readcyclecounter(), w0 = wall_clock64();
     uint32_t x = threadIdx.x;
@@ -123,15 +147,17 @@ __global__ void k_clock_probe(uint64_t* out, uint32_t iters) {
 }
 // a plain launch: the caller is not a proving thread, the profiler's launch scope (profiler.hpp) belongs to those
 void launch_clock_probe(hipStream_t st, uint64_t* out3, uint32_t iters) { hipLaunchKernelGGL(k_clock_probe, dim3(1), dim3(64), 0, st, out3, iters); }
+#endif
 
-void launch_ingest(hipStream_t st, const uint32_t* src_dev, DMatView dst, bool bitrev) {
+void launch_ingest(hipStream_t st, const uint32_t* src_dev, DMatView dst, bool bitrev, uint32_t* varies) {
     int log_h = (int)vg::log2_strict_u64(dst.height);
     unsigned blocks = (unsigned)((dst.height + 63) / 64);
-    size_t lds = (size_t)64 * (dst.width | 1) * 4;
+    if (varies && dst.width > INGEST_FLAGS_MAX_WIDTH) throw std::invalid_argument("ingest: column flags are for matrices of at most " + std::to_string(INGEST_FLAGS_MAX_WIDTH) + " columns");
+    size_t lds = (size_t)(varies ? 65 : 64) * (dst.width | 1) * 4;
     // the 64-row tile of every column has to fit a workgroup's LDS (160 KiB: 639 columns); said here, not by the launch's "invalid argument"
     if (lds > 160 * 1024) throw std::invalid_argument("ingest: a matrix of " + std::to_string(dst.width) + " columns is wider than the 639 columns whose 64-row tile fits a workgroup's LDS");
     ProfScope ps("k_ingest", st, 8.0 * dst.height * dst.width);
-    VK_LAUNCH(k_ingest, dim3(blocks), dim3(256), lds, st, src_dev, dst, log_h, bitrev ? 1 : 0);
+    VK_LAUNCH(k_ingest, dim3(blocks), dim3(256), lds, st, src_dev, dst, log_h, bitrev ? 1 : 0, varies);
 }
 void launch_bitrev_rows(hipStream_t st, DMatView src, DMatView dst) {
     int k = (int)vg::log2_strict_u64(src.height);

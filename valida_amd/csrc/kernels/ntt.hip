@@ -459,13 +459,22 @@ __device__ __forceinline__ void strided_tile_store_transposed(uint32_t* out_col,
 
 // ---- pass A: inverse, strided, natural input: grid = (n_lo / T, columns) -------------------------------
 // FK_HI / FLOGT: one of the two hot tile shapes fixed at compile time (8 / 6, 10 / 4: 512 threads), or 0 / 0 = any shape (run-time k_hi, logT)
-template <int FK_HI, int FLOGT>
-__global__ void __launch_bounds__(FK_HI ? 512 : 1024) k_lde_a(DMatView src, DMatView dst, int k, int k_lo, int logT_arg, DeviceTables tb) {
+// MAPPED (every pass below): the launch carries a column map (k_lde_colmap) and transforms the map's live columns only.  The scratch matrices are used
+// compactly — scratch column y holds source column live[y] — so pass A reads nat.col(live[y]), the middle pass counts its tiles from live_count and
+// pass C writes lde.col(live[y]); the grids stay sized for the full width (the host never learns the count) and a slice y >= live_count exits at once.
+// Without a map (MAPPED = false; `colmap` is then an unused argument) the code is the unmapped kernel's, instruction for instruction.
+template <int FK_HI, int FLOGT, bool MAPPED = false>
+__global__ void __launch_bounds__(FK_HI ? 512 : 1024) k_lde_a(DMatView src, DMatView dst, int k, int k_lo, int logT_arg, DeviceTables tb, const uint32_t* colmap) {
     extern __shared__ uint32_t lds[];
+    uint64_t src_col = blockIdx.y;
+    if constexpr (MAPPED) {
+        if (blockIdx.y >= colmap[COLMAP_LIVE_COUNT]) return;
+        src_col = colmap[COLMAP_LIVE + blockIdx.y];
+    }
     const int k_hi = FK_HI ? FK_HI : k - k_lo, logT = FK_HI ? FLOGT : logT_arg, n_hi = 1 << k_hi, T = 1 << logT, LD = T + 1;
     const uint64_t n_lo = 1ull << k_lo, r0 = (uint64_t)strided_tile_of_block(blockIdx.x, gridDim.x) * T;
     uint32_t* tw = lds + n_hi * LD;
-    const uint32_t* in = src.col(blockIdx.y) + r0;
+    const uint32_t* in = src.col(src_col) + r0;
     uint32_t* out = dst.col(blockIdx.y) + r0;
     const int total = n_hi << logT;
     if constexpr (FK_HI != 0) strided_tile_load<FK_HI, FLOGT, false>(in, (uint32_t)n_lo, lds);
@@ -504,13 +513,13 @@ __global__ void __launch_bounds__(FK_HI ? 512 : 1024) k_lde_a(DMatView src, DMat
 // (What remains: ~110 SGPRs parked in VGPR lanes — the loop-invariant twiddle-table addresses of the run-time round dispatch, hoisted out of the tile
 // loop; fixing the tile size at compile time, 13 instantiations, halves the code and leaves 10-90 of them: not adopted, these launches sit on the
 // auxiliary stream beside the big matrices' passes.)
-template <int MAXT>
-__global__ void __launch_bounds__(MAXT) k_lde_mid(DMatView src, DMatView dst, int k, int k_lo, int lb, DeviceTables tb, LdeTables lt) {
+template <int MAXT, bool MAPPED = false>
+__global__ void __launch_bounds__(MAXT) k_lde_mid(DMatView src, DMatView dst, int k, int k_lo, int lb, DeviceTables tb, LdeTables lt, const uint32_t* colmap) {
     extern __shared__ uint32_t lds[];
     const int n_lo = 1 << k_lo, k_hi = k - k_lo, n_hi = 1 << k_hi, b = 1 << lb;
     uint32_t* A = lds;
     uint32_t* W = lds + padded_words(n_lo);
-    const uint64_t N = 1ull << k, tiles_per_col = (uint64_t)n_hi, total = tiles_per_col * src.width;
+    const uint64_t N = 1ull << k, tiles_per_col = (uint64_t)n_hi, total = tiles_per_col * (MAPPED ? (uint64_t)colmap[COLMAP_LIVE_COUNT] : src.width);
     const uint32_t nmask = (uint32_t)(N - 1);
     auto tile_ptr = [&](uint64_t t) { const uint64_t cidx = t >> k_hi; return src.col(cidx) + (t & (tiles_per_col - 1)) * n_lo; };
     uint32_t pre[CONTIG_MAX_PER_THREAD];
@@ -551,11 +560,12 @@ __global__ void __launch_bounds__(MAXT) k_lde_mid(DMatView src, DMatView dst, in
 // fed straight from the global loads, its last round and the first round of every forward transform joined in registers (both work on the
 // thread's own 16 consecutive positions: the coefficients never leave the register file), the last forward round stored straight to
 // HBM: ONE LDS tile instead of two, 2 + 3 b barriers per tile instead of 4 + 5 b, half the LDS traffic.  256 threads x 16 points.
-__global__ void __launch_bounds__(256) k_lde_mid12(DMatView src, DMatView dst, int k, int lb, DeviceTables tb, LdeTables lt) {
+template <bool MAPPED>
+__global__ void __launch_bounds__(256) k_lde_mid12(DMatView src, DMatView dst, int k, int lb, DeviceTables tb, LdeTables lt, const uint32_t* colmap) {
     extern __shared__ uint32_t lds[];
     constexpr int K_LO = 12, N_LO = 1 << K_LO;
     const int k_hi = k - K_LO, n_hi = 1 << k_hi, b = 1 << lb, tid = threadIdx.x;
-    const uint64_t N = 1ull << k, tiles_per_col = (uint64_t)n_hi, total = tiles_per_col * src.width;
+    const uint64_t N = 1ull << k, tiles_per_col = (uint64_t)n_hi, total = tiles_per_col * (MAPPED ? (uint64_t)colmap[COLMAP_LIVE_COUNT] : src.width);
     const uint32_t nmask = (uint32_t)(N - 1);
     auto tile_ptr = [&](uint64_t t) { const uint64_t cidx = t >> k_hi; return src.col(cidx) + (t & (tiles_per_col - 1)) * N_LO; };
     Fp tw_in[15], tw_out[15];
@@ -631,12 +641,13 @@ __global__ void __launch_bounds__(256) k_lde_mid12(DMatView src, DMatView dst, i
 // ---- pass B for 2^14-point tiles (heights from 2^23: C3's memory chip): the same fusion with one more, radix-4, round at the outer end of each
 // transform (stages 14, 13).  1024 threads x 16 points; a thread's prefetched element tid + 1024 u is point g = u >> 2 of its outer-round
 // item j = u & 3 (points tid + 1024 j + 4096 g).  One LDS tile (70 KiB) instead of the generic kernel's two; 128 registers (one workgroup per CU).
-__global__ void __launch_bounds__(1024) k_lde_mid14(DMatView src, DMatView dst, int k, int lb, DeviceTables tb, LdeTables lt) {
+template <bool MAPPED>
+__global__ void __launch_bounds__(1024) k_lde_mid14(DMatView src, DMatView dst, int k, int lb, DeviceTables tb, LdeTables lt, const uint32_t* colmap) {
     extern __shared__ uint32_t lds[];
     constexpr int K_LO = 14, N_LO = 1 << K_LO, NT = 1024;
     uint32_t* const coef = lds + (N_LO + (N_LO >> 4));  // second padded tile: the coefficients of the current column tile
     const int k_hi = k - K_LO, n_hi = 1 << k_hi, b = 1 << lb, tid = threadIdx.x;
-    const uint64_t N = 1ull << k, tiles_per_col = (uint64_t)n_hi, total = tiles_per_col * src.width;
+    const uint64_t N = 1ull << k, tiles_per_col = (uint64_t)n_hi, total = tiles_per_col * (MAPPED ? (uint64_t)colmap[COLMAP_LIVE_COUNT] : src.width);
     const uint32_t nmask = (uint32_t)(N - 1);
     for (uint64_t t = blockIdx.x; t < total; t += gridDim.x) {
         const uint64_t cidx = t >> k_hi, p = t & (tiles_per_col - 1);
@@ -706,16 +717,20 @@ __global__ void __launch_bounds__(1024) k_lde_mid14(DMatView src, DMatView dst, 
 }
 
 // ---- pass C: forward, strided, transposing store: grid = (n_lo / T, columns, cosets) --------------------
-template <int FK_HI, int FLOGT>  // as k_lde_a
-__global__ void __launch_bounds__(FK_HI ? 512 : 1024) k_lde_c(DMatView src, DMatView dst, int k, int k_lo, int lb, int logT_arg, DeviceTables tb
-                        ) {
+template <int FK_HI, int FLOGT, bool MAPPED = false>  // as k_lde_a
+__global__ void __launch_bounds__(FK_HI ? 512 : 1024) k_lde_c(DMatView src, DMatView dst, int k, int k_lo, int lb, int logT_arg, DeviceTables tb, const uint32_t* colmap) {
     extern __shared__ uint32_t lds[];
+    uint64_t dst_col = blockIdx.y;
+    if constexpr (MAPPED) {
+        if (blockIdx.y >= colmap[COLMAP_LIVE_COUNT]) return;
+        dst_col = colmap[COLMAP_LIVE + blockIdx.y];
+    }
     const int k_hi = FK_HI ? FK_HI : k - k_lo, logT = FK_HI ? FLOGT : logT_arg, n_hi = 1 << k_hi, T = 1 << logT, LD = T + 1;
     const uint64_t n_lo = 1ull << k_lo, N = 1ull << k, q0 = (uint64_t)strided_tile_of_block(blockIdx.x, gridDim.x) * T;
     const uint32_t tc = blockIdx.z, blk = lb ? __brev(tc) >> (32 - lb) : 0u;
     uint32_t* tw = lds + n_hi * LD;
     const uint32_t* in = src.col(blockIdx.y) + (uint64_t)tc * N + q0;
-    uint32_t* out = dst.col(blockIdx.y) + (uint64_t)blk * N;
+    uint32_t* out = dst.col(dst_col) + (uint64_t)blk * N;
     const int total = n_hi << logT;
     if constexpr (FK_HI != 0) strided_tile_load<FK_HI, FLOGT, true>(in, (uint32_t)n_lo, lds);
     else {
@@ -751,6 +766,34 @@ __global__ void __launch_bounds__(FK_HI ? 512 : 1024) k_lde_c(DMatView src, DMat
         const uint32_t qb = __brev((uint32_t)(q0 + c)) >> (32 - k_lo);
         out[(uint64_t)qb * n_hi + p2] = lds[p2 * LD + c];
     }
+}
+
+// ---- constant columns: the map and the fill -------------------------------------------------------------
+// A column that holds one value c in every row is the constant polynomial c, and its LDE on any coset is c in every row: no transform.  k_ingest
+// (layout.hip) leaves varies[j] != 0 for every column j in which some row differs from row 0; from those flags ONE workgroup writes the map the three
+// passes above take (layout: COLMAP_* in launch.hpp): the live columns ascending, then the constant ones ascending.  A thread's rank is the number of
+// flagged columns before its own, counted straight from the LDS copy of the flags (widths are a few hundred at most: at most `width` LDS reads a thread).
+__global__ void __launch_bounds__(256) k_lde_colmap(const uint32_t* __restrict__ varies, uint32_t width, uint32_t* __restrict__ colmap) {
+    extern __shared__ uint32_t lds[];  // [width]
+    for (uint32_t j = threadIdx.x; j < width; j += blockDim.x) lds[j] = varies[j] != 0 ? 1u : 0u;
+    __syncthreads();
+    for (uint32_t j = threadIdx.x; j < width; j += blockDim.x) {
+        uint32_t rank = 0;
+        for (uint32_t i = 0; i < j; i++) rank += lds[i];
+        if (lds[j]) colmap[COLMAP_LIVE + rank] = j;
+        else colmap[COLMAP_LIVE + width + (j - rank)] = j;
+        if (j + 1 == width) { colmap[COLMAP_LIVE_COUNT] = rank + lds[j]; colmap[COLMAP_CONST_COUNT] = width - (rank + lds[j]); }
+    }
+}
+// lde.col(c)[0 .. lde.height) = nat.col(c)[0] (Montgomery form already) for every constant column c of the map: grid = (chunks, width), 16-byte stores;
+// a slice y >= const_count exits at once.  Columns of an LDE start at multiples of its height (>= 2^13 words) from a 256-byte-aligned block.
+__global__ void __launch_bounds__(256) k_lde_fill_const(DMatView nat, DMatView lde, const uint32_t* __restrict__ colmap) {
+    if (blockIdx.y >= colmap[COLMAP_CONST_COUNT]) return;
+    const uint32_t c = colmap[COLMAP_LIVE + nat.width + blockIdx.y];
+    const uint32_t v = nat.col(c)[0];
+    uint4* out = reinterpret_cast<uint4*>(lde.col(c));
+    const uint64_t quads = lde.height >> 2;
+    for (uint64_t q = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; q < quads; q += (uint64_t)gridDim.x * blockDim.x) out[q] = make_uint4(v, v, v, v);
 }
 
 // ---- host launchers -----------------------------------------------------------------------------------
@@ -790,8 +833,18 @@ static void set_lds_limit() {
     (void)hipFuncSetAttribute((const void*)k_lde_c<0, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
     (void)hipFuncSetAttribute((const void*)k_lde_c<8, 6>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
     (void)hipFuncSetAttribute((const void*)k_lde_c<10, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    (void)hipFuncSetAttribute((const void*)k_lde_mid12, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
-    (void)hipFuncSetAttribute((const void*)k_lde_mid14, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_mid12<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_mid14<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_a<0, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_a<8, 6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_a<10, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_mid<256, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_mid<1024, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_c<0, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_c<8, 6, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_c<10, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_mid12<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
+    (void)hipFuncSetAttribute((const void*)k_lde_mid14<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lim);
     done = true;
 }
 
@@ -847,9 +900,18 @@ void launch_coset_ntt(hipStream_t st, DMatView coeffs, DMatView dst, uint64_t ds
     }
 }
 
+// The column map of launch_lde_natural from the flags the ingest left (launch.hpp): one workgroup, the flags staged in LDS
+void launch_lde_colmap(hipStream_t st, const uint32_t* varies, uint64_t width, uint32_t* colmap) {
+    if (width == 0 || width > 16384) throw std::invalid_argument("lde colmap: width out of range");
+    ProfScope ps("k_lde_colmap", st, 4.0 * 3 * width);
+    VK_LAUNCH(k_lde_colmap, dim3(1), dim3(256), (size_t)width * 4, st, varies, (uint32_t)width, colmap);
+}
+
 // The bit-reversed LDE of the natural-order evaluations `nat` (column-major, height N = 2^k) on shift * H_{N << log_blowup}, into `lde`
 // (height N << log_blowup).  s1 (N x width) and s2 ((N << log_blowup) x width) are scratch, needed only when N > 2^12 (null views otherwise).
-void launch_lde_natural(hipStream_t st, DMatView nat, DMatView lde, int log_blowup, const DeviceTables& tb, const LdeTables& lt, DMatView s1, DMatView s2) {
+// colmap (optional, heights above 2^12): transform the map's live columns only and fill the constant ones (k_lde_fill_const).
+void launch_lde_natural(hipStream_t st, DMatView nat, DMatView lde, int log_blowup, const DeviceTables& tb, const LdeTables& lt, DMatView s1, DMatView s2,
+                        const uint32_t* colmap) {
     set_lds_limit();
     const int k = (int)vg::log2_strict_u64(nat.height);
     NttPlan p = make_plan(k);
@@ -857,35 +919,59 @@ void launch_lde_natural(hipStream_t st, DMatView nat, DMatView lde, int log_blow
     dim3 gm((unsigned)(tiles < 4096 ? tiles : 4096));
     const size_t lds_mid = 2 * (size_t)padded_words(1 << p.k_lo) * 4;
     const double nw = 4.0 * nat.height * nat.width, b = (double)(1u << log_blowup);
-    if (p.k_hi == 0) {
+    if (p.k_hi == 0) {  // one-tile columns: the map is ignored (nothing to win on a single small launch)
         ProfScope ps("k_lde_mid", st, nw * (1.0 + b));
-        VK_LAUNCH(k_lde_mid<256>, gm, dim3(p.threads_contig), lds_mid, st, nat, lde, k, p.k_lo, log_blowup, tb, lt);  // k_lo <= 12: at most 256 threads
+        VK_LAUNCH(k_lde_mid<256>, gm, dim3(p.threads_contig), lds_mid, st, nat, lde, k, p.k_lo, log_blowup, tb, lt, nullptr);  // k_lo <= 12: at most 256 threads
         return;
+    }
+    // (the algorithmic bytes of the mapped launches stay the full-width figures: the host does not know the live count)
+    if (colmap) {
+        const uint64_t quads = lde.height >> 2, per_block = 256 * 16;  // 16 stores of 16 bytes per thread
+        ProfScope ps("k_lde_fill_const", st, 0.0);
+        VK_LAUNCH(k_lde_fill_const, dim3((unsigned)((quads + per_block - 1) / per_block), (unsigned)nat.width), dim3(256), 0, st, nat, lde, colmap);
     }
     dim3 gs((unsigned)((1u << p.k_lo) >> p.logT), (unsigned)nat.width);
     {
         ProfScope ps("k_lde_a", st, 2.0 * nw);
         const int shape = VGPU_STRIDED_IO && VGPU_STRIDED_FIXED && p.threads_strided == 512 ? (p.k_hi == 8 && p.logT == 6 ? 8 : (p.k_hi == 10 && p.logT == 4 ? 10 : 0)) : 0;
-        if (shape == 8) VK_LAUNCH((k_lde_a<8, 6>), gs, dim3(512), p.lds_strided, st, nat, s1, k, p.k_lo, p.logT, tb);
-        else if (shape == 10) VK_LAUNCH((k_lde_a<10, 4>), gs, dim3(512), p.lds_strided, st, nat, s1, k, p.k_lo, p.logT, tb);
-        else VK_LAUNCH((k_lde_a<0, 0>), gs, dim3(p.threads_strided), p.lds_strided, st, nat, s1, k, p.k_lo, p.logT, tb);
+#define VG_LDE_A(A, B, THREADS)                                                                                                       \
+    do {                                                                                                                              \
+        if (colmap) VK_LAUNCH((k_lde_a<A, B, true>), gs, dim3(THREADS), p.lds_strided, st, nat, s1, k, p.k_lo, p.logT, tb, colmap);      \
+        else VK_LAUNCH((k_lde_a<A, B, false>), gs, dim3(THREADS), p.lds_strided, st, nat, s1, k, p.k_lo, p.logT, tb, colmap);           \
+    } while (0)
+        if (shape == 8) VG_LDE_A(8, 6, 512);
+        else if (shape == 10) VG_LDE_A(10, 4, 512);
+        else VG_LDE_A(0, 0, p.threads_strided);
+#undef VG_LDE_A
     }
     if (p.k_lo == 12) {
         if (gm.x > 4096u) gm.x = 4096u;  // persistent blocks
         ProfScope ps("k_lde_mid12", st, nw * (1.0 + b));
-        VK_LAUNCH(k_lde_mid12, gm, dim3(256), (size_t)padded_words(4096) * 4, st, s1, s2, k, log_blowup, tb, lt);
+        if (colmap) VK_LAUNCH(k_lde_mid12<true>, gm, dim3(256), (size_t)padded_words(4096) * 4, st, s1, s2, k, log_blowup, tb, lt, colmap);
+        else VK_LAUNCH(k_lde_mid12<false>, gm, dim3(256), (size_t)padded_words(4096) * 4, st, s1, s2, k, log_blowup, tb, lt, colmap);
     } else if (p.k_lo == 14) {
         ProfScope ps("k_lde_mid14", st, nw * (1.0 + b));
-        VK_LAUNCH(k_lde_mid14, gm, dim3(1024), 2 * (size_t)padded_words(16384) * 4, st, s1, s2, k, log_blowup, tb, lt);  // work tile + coefficient tile: 139 KiB
+        const size_t lds14 = 2 * (size_t)padded_words(16384) * 4;  // work tile + coefficient tile: 139 KiB
+        if (colmap) VK_LAUNCH(k_lde_mid14<true>, gm, dim3(1024), lds14, st, s1, s2, k, log_blowup, tb, lt, colmap);
+        else VK_LAUNCH(k_lde_mid14<false>, gm, dim3(1024), lds14, st, s1, s2, k, log_blowup, tb, lt, colmap);
     } else {
         ProfScope ps("k_lde_mid", st, nw * (1.0 + b));
-        if (p.threads_contig <= 256) VK_LAUNCH(k_lde_mid<256>, gm, dim3(p.threads_contig), lds_mid, st, s1, s2, k, p.k_lo, log_blowup, tb, lt);
-        else VK_LAUNCH(k_lde_mid<1024>, gm, dim3(p.threads_contig), lds_mid, st, s1, s2, k, p.k_lo, log_blowup, tb, lt);
+        if (p.threads_contig <= 256) {
+            if (colmap) VK_LAUNCH((k_lde_mid<256, true>), gm, dim3(p.threads_contig), lds_mid, st, s1, s2, k, p.k_lo, log_blowup, tb, lt, colmap);
+            else VK_LAUNCH(k_lde_mid<256>, gm, dim3(p.threads_contig), lds_mid, st, s1, s2, k, p.k_lo, log_blowup, tb, lt, colmap);
+        } else {
+            if (colmap) VK_LAUNCH((k_lde_mid<1024, true>), gm, dim3(p.threads_contig), lds_mid, st, s1, s2, k, p.k_lo, log_blowup, tb, lt, colmap);
+            else VK_LAUNCH(k_lde_mid<1024>, gm, dim3(p.threads_contig), lds_mid, st, s1, s2, k, p.k_lo, log_blowup, tb, lt, colmap);
+        }
     }
     dim3 gc((unsigned)((1u << p.k_lo) >> p.logT), (unsigned)nat.width, 1u << log_blowup);
     ProfScope ps("k_lde_c", st, 2.0 * nw * b);
     const int shape_c = VGPU_STRIDED_IO && VGPU_STRIDED_FIXED && p.threads_strided == 512 ? (p.k_hi == 8 && p.logT == 6 ? 8 : (p.k_hi == 10 && p.logT == 4 ? 10 : 0)) : 0;
-#define VG_LDE_C(A, B, THREADS) VK_LAUNCH((k_lde_c<A, B>), gc, dim3(THREADS), p.lds_strided, st, s2, lde, k, p.k_lo, log_blowup, p.logT, tb)
+#define VG_LDE_C(A, B, THREADS)                                                                                                              \
+    do {                                                                                                                                     \
+        if (colmap) VK_LAUNCH((k_lde_c<A, B, true>), gc, dim3(THREADS), p.lds_strided, st, s2, lde, k, p.k_lo, log_blowup, p.logT, tb, colmap); \
+        else VK_LAUNCH((k_lde_c<A, B, false>), gc, dim3(THREADS), p.lds_strided, st, s2, lde, k, p.k_lo, log_blowup, p.logT, tb, colmap);     \
+    } while (0)
     if (shape_c == 8) VG_LDE_C(8, 6, 512);
     else if (shape_c == 10) VG_LDE_C(10, 4, 512);
     else VG_LDE_C(0, 0, p.threads_strided);
