@@ -302,7 +302,13 @@ int32_t vgpu_fri_fold(vgpu_prover_t* p, const uint32_t* f, uint64_t n, const uin
  * unspecified words; a butterfly item whose low / lowbits would index past the twiddle tables is refused. */
 int32_t vgpu_field_probe(vgpu_prover_t* p, uint32_t op, const uint32_t* operands, uint64_t operand_words, uint64_t n_items, uint32_t* results, uint64_t result_words);
 
-/* Test hook: poison the prover's HBM pool (vgpu_prover_trim's cache).  The pool clears nothing, so a recycled block holds the last contents of a
+/* Test hook: the lazily folded sums of the device's field arithmetic (kernels/lazy_probe.hip) on n_items operand tuples of RAW STORED WORDS, laid
+ * out as vgpu_field_probe's.  op 0 fold_hi: (lo, hi), hi < 2p -> (lo, hi); op 1 ext_mul: a[5], b[5] -> a b; op 2 lin_dot: terms x { A[5], v } -> sum A v,
+ * terms = 1 .. 17 or 34, unrolled; op 3 ext_dot: terms x { A[5], C[5] } -> sum A C, terms = 1 .. 8; op 4: op 2 as a rolled loop, terms = 1 .. 64.
+ * terms = 0 for ops 0 and 1.  Any other op / length, or buffer sizes that do not match the shape: VGPU_ERR_INVALID_ARG. */
+int32_t vgpu_lazy_probe(vgpu_prover_t* p, uint32_t op, uint32_t terms, const uint32_t* operands, uint64_t operand_words, uint64_t n_items, uint32_t* results, uint64_t result_words);
+
+/* Test hook: poison the prover's HBM pool(vgpu_prover_trim's cache).  The pool clears nothing, so a recycled block holds the last contents of a
  * buffer of the same size — usually the previous identical call's correct answer, which hides a stage that reads what it has not written.
  * mode bit 0: every block the pool hands out, fresh or recycled, is filled with `word` first; bit 1: every block is filled at the moment it
  * returns to the cache (a block released inside a fork/join section: at the join); 0 switches the hook off (the default; the only cost is

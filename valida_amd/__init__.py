@@ -390,6 +390,31 @@ def field_probe(prover, op, operands):
     return np.ascontiguousarray(out.T)
 
 
+# vgpu_lazy_probe: op name -> (op code, operand words per item as a function of the sum's length, result words per item, the lengths the op is built
+# for; (0,) = the op has no length).  In the order of vk::LazyProbeOp (kernels/launch.hpp); a list of its own beside FIELD_PROBE_OPS.
+LAZY_PROBE_OPS = {name: (code, iw, ow, tuple(terms)) for code, (name, iw, ow, terms) in enumerate([
+    ("fold_hi", lambda n: 2, 2, (0,)), ("ext_mul", lambda n: 10, 5, (0,)), ("lin_dot", lambda n: 6 * n, 5, list(range(1, 18)) + [34]),
+    ("ext_dot", lambda n: 10 * n, 5, range(1, 9)), ("lin_dot_loop", lambda n: 6 * n, 5, range(1, 65))])}
+
+
+def lazy_probe(prover, op, terms, operands):
+    """Test hook (vgpu_lazy_probe): fold_hi, the Ext5 product or a lazily folded sum of `terms` terms (a key of LAZY_PROBE_OPS; terms = 0 where the op
+    has none) of the DEVICE's field arithmetic on operands[i] = one item's raw stored words -> (n_items, result words) raw stored words."""
+    code, iwf, ow, lengths = LAZY_PROBE_OPS[op]
+    if terms not in lengths:
+        raise ValueError("lazy_probe(%s): no such length %r" % (op, terms))
+    iw = iwf(terms)
+    a = np.ascontiguousarray(operands, dtype=np.uint32)
+    if a.ndim != 2 or a.shape[1] != iw or a.shape[0] == 0:
+        raise ValueError("lazy_probe(%s, %d): operands must be a non-empty (n_items, %d) array" % (op, terms, iw))
+    n = a.shape[0]
+    src = np.ascontiguousarray(a.T)
+    out = np.zeros((ow, n), dtype=np.uint32)
+    _check(lib().vgpu_lazy_probe(prover._h, ctypes.c_uint32(code), ctypes.c_uint32(terms), src.ctypes.data_as(c_u32p), ctypes.c_uint64(src.size), ctypes.c_uint64(n),
+                                 out.ctypes.data_as(c_u32p), ctypes.c_uint64(out.size)))
+    return np.ascontiguousarray(out.T)
+
+
 class _PinnedBlock:
     def __init__(self, nbytes):
         self.ptr = ctypes.c_void_p()

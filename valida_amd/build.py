@@ -39,6 +39,7 @@ SOURCES = [
     "kernels/memory_audit.hip",
     "kernels/program_audit.hip",
     "kernels/field_probe.hip",
+    "kernels/lazy_probe.hip",
     "host/prover.cpp",
     "host/prover_audits.cpp",
     "host/sharded_prover.cpp",

@@ -951,6 +951,24 @@ int32_t vgpu_field_probe(vgpu_prover_t* p, uint32_t op, const uint32_t* operands
     })
 }
 
+// test hook: fold_hi, the Ext5 product and the lazily folded sums on raw stored words (kernels/lazy_probe.hip)
+int32_t vgpu_lazy_probe(vgpu_prover_t* p, uint32_t op, uint32_t terms, const uint32_t* operands, uint64_t operand_words, uint64_t n_items, uint32_t* results, uint64_t result_words) {
+    VG_TRY({
+        int iw = 0, ow = 0;
+        if (!p || !operands || !results) throw std::invalid_argument("null argument");
+        if (!vk::lazy_probe_shape(op, terms, &iw, &ow)) throw std::invalid_argument("lazy probe: unknown op or length");
+        if (n_items == 0 || n_items > (1ull << 24)) throw std::invalid_argument("lazy probe: 1 .. 2^24 items");
+        if (operand_words != n_items * (uint64_t)iw || result_words != n_items * (uint64_t)ow) throw std::invalid_argument("lazy probe: buffer sizes do not match the op's shape");
+        DeviceCtx& c = p->p->ctx();
+        c.activate();
+        DBuf din(&c, (size_t)operand_words), dout(&c, (size_t)result_words);
+        c.upload(din.data, operands, operand_words * 4);
+        vk::launch_lazy_probe(c.stream, op, terms, din.data, n_items, dout.data);
+        c.check_launch("lazy probe");
+        c.download(results, dout.data, result_words * 4);
+    })
+}
+
 // test hooks: the pool's poison (host/runtime.hpp: DeviceCtx::poison_mode)
 int32_t vgpu_prover_set_pool_poison(vgpu_prover_t* p, uint32_t mode, uint32_t word) {
     VG_TRY({

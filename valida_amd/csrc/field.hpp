@@ -113,15 +113,80 @@ VG_HD uint32_t monty_reduce(uint64_t t) {
 #endif
 }
 
-// Montgomery reduction of a lazily accumulated sum of up to FOUR products of values < p
-// (t < 4 p^2 < 2^64, high word < 2p): one conditional subtraction of p * 2^32 first, then as above.
-// 7 VALU instructions for 4 multiply-adds that each cost one v_mad_u64_u32.
+// Montgomery reduction of any 64-bit t whose HIGH WORD is < 2p: one conditional subtraction of p * 2^32 first (fold_hi below), then as
+// above.  A sum of up to FOUR products of values < p qualifies (t < 4 p^2, high word < 1.875 p), and so does a folded sum plus two more
+// products (LazyAcc below).  7 VALU instructions.
 VG_HD uint32_t monty_reduce_wide(uint64_t t) {
     uint32_t lo = (uint32_t)t, hi = reduce_once((uint32_t)(t >> 32));
     uint32_t m = mul_lo_pinv(lo);
     uint32_t u = mul_hi_u32(m, P);
     return sub_mod(hi, u);
 }
+
+// t -> t - [hi(t) >= p] * p * 2^32 for a high word < 2p: the same residue mod p, now below p * 2^32.  reduce_once on the high word (two
+// instructions on the device), the low word untouched.
+VG_HD uint64_t fold_hi(uint64_t t) { return ((uint64_t)reduce_once((uint32_t)(t >> 32)) << 32) | (uint32_t)t; }
+
+// A sum of products of stored words that is Montgomery-reduced ONCE, at its end, however long it is.  Between the products only the high
+// word is folded.  With u = p^2 (one product of two words < p):
+//   empty                       takes 4 u:  4 p^2 < 2^64, high word < 1.875 p < 2p
+//   after a fold (t < p 2^32)   takes 2 u:  p 2^32 + 2 p^2 = 1.9375 p 2^32 < 2^64, high word < 1.9375 p < 2p  (a third: p 2^32 + 3 p^2 > 2^64)
+// so a sum goes 4 products, fold, 2 products, fold, 2 products, ... : one fold (2 instructions) per two terms where a Montgomery reduction per
+// four terms and a modular add into a second register cost 10 per four.  `room` is how many u the sum still takes before it must fold; the
+// call sites are unrolled, so it is a constant at every one of them and the test on it compiles away (in a rolled loop it is a wave-uniform
+// scalar).  A product with one operand in [0, 2p) is 2 u (mac2).
+// VG_LAZY_CHECK (host builds only; tests/emu/lazy_bounds_host.cpp): a shadow 128-bit sum beside the 64-bit one; abort when the 64-bit sum
+// would wrap or a high word reaches 2p where it is folded or reduced.
+#ifndef VG_LAZY_CHECK
+#define VG_LAZY_CHECK 0
+#endif
+#if VG_LAZY_CHECK
+[[noreturn]] void lazy_check_failed(const char* what, uint64_t t);  // defined by the checking program
+#endif
+struct LazyAcc {
+    uint64_t t;
+    int room;
+#if VG_LAZY_CHECK
+    unsigned __int128 shadow;
+    inline void check_hi(const char* what) const {
+        if (shadow != (unsigned __int128)t) lazy_check_failed("the 64-bit sum wrapped", t);
+        if ((uint32_t)(t >> 32) >= 2u * P) lazy_check_failed(what, t);
+    }
+#endif
+    VG_HD void clear() {
+        t = 0; room = 4;
+#if VG_LAZY_CHECK
+        shadow = 0;
+#endif
+    }
+    VG_HD static LazyAcc zero() { LazyAcc a; a.clear(); return a; }
+    VG_HD void fold() {
+#if VG_LAZY_CHECK
+        check_hi("high word >= 2p at a fold");
+#endif
+        t = fold_hi(t); room = 2;
+#if VG_LAZY_CHECK
+        shadow = t;
+#endif
+    }
+    template <int W> VG_HD void add_product(uint32_t a, uint32_t b) {
+        if (room < W) fold();
+        room -= W;
+#if VG_LAZY_CHECK
+        shadow += (unsigned __int128)((uint64_t)a * b);
+        if (shadow >> 64) lazy_check_failed("the 64-bit sum would wrap", t);
+#endif
+        t += (uint64_t)a * b;
+    }
+    VG_HD void mac(uint32_t a, uint32_t b) { add_product<1>(a, b); }   // a, b < p
+    VG_HD void mac2(uint32_t a, uint32_t b) { add_product<2>(a, b); }  // one of them in [0, 2p), the other < p
+    VG_HD uint32_t reduce() const {
+#if VG_LAZY_CHECK
+        check_hi("high word >= 2p at the final reduction");
+#endif
+        return monty_reduce_wide(t);
+    }
+};
 
 struct Fp {
     uint32_t v;  // Montgomery representation, < p
@@ -190,8 +255,8 @@ struct Ext5 {
     VG_HD Ext5 operator+(const Fp& s) const { Ext5 r = *this; r.c[0] += s; return r; }
     VG_HD Ext5 operator-(const Fp& s) const { Ext5 r = *this; r.c[0] -= s; return r; }
     // Schoolbook, X^5 = 2 folded by pre-doubling one operand: limb k = sum_i a_i * B_{k,i} with
-    // B_{k,i} = b_{k-i} (i <= k) or 2*b_{k+5-i} (i > k).  Four products (< 4 p^2 < 2^64) share one
-    // Montgomery reduction (monty_reduce_wide): 2 reductions per limb instead of 5.
+    // B_{k,i} = b_{k-i} (i <= k) or 2*b_{k+5-i} (i > k).  The five products of a limb go on one LazyAcc: four multiply-adds, a fold of
+    // the high word, the fifth, ONE Montgomery reduction (14 instructions per limb; reducing the fifth product on its own and adding: 20).
     VG_HD Ext5 operator*(const Ext5& o) const {
         Fp d[5];
 #pragma unroll
@@ -199,12 +264,10 @@ struct Ext5 {
         Ext5 r;
 #pragma unroll
         for (int k = 0; k < 5; k++) {
-            uint32_t bb[5];
+            LazyAcc acc = LazyAcc::zero();
 #pragma unroll
-            for (int i = 0; i < 5; i++) bb[i] = i <= k ? o.c[k - i].v : d[k + 5 - i].v;
-            uint64_t t0123 = (uint64_t)c[0].v * bb[0] + (uint64_t)c[1].v * bb[1] + (uint64_t)c[2].v * bb[2] + (uint64_t)c[3].v * bb[3];
-            uint64_t t4 = (uint64_t)c[4].v * bb[4];
-            r.c[k] = Fp::raw(monty_reduce_wide(t0123)) + Fp::raw(monty_reduce(t4));
+            for (int i = 0; i < 5; i++) acc.mac(c[i].v, i <= k ? o.c[k - i].v : d[k + 5 - i].v);
+            r.c[k] = Fp::raw(acc.reduce());
         }
         return r;
     }
@@ -240,6 +303,31 @@ struct Ext5 {
         Fp norm = c[0] * prod.c[0] + hi + hi;
         return prod * norm.inv();
     }
+};
+
+// Five LazyAccs, one per limb: sums of (Ext5 x base word) and of (Ext5 x Ext5) products with ONE Montgomery reduction per limb for the
+// whole sum.  Ten registers where an Ext5 takes five: for sums whose terms arrive one after the other, not for many sums held at once.
+struct ExtAcc {
+    LazyAcc l[5];
+    VG_HD static ExtAcc zero() { ExtAcc a; for (int k = 0; k < 5; k++) a.l[k].clear(); return a; }
+    VG_HD void mac(const uint32_t* a5, uint32_t v) {  // += a5[0..5) (stored words of an Ext5) * v
+#pragma unroll
+        for (int k = 0; k < 5; k++) l[k].mac(a5[k], v);
+    }
+    VG_HD void mac(const Ext5& a, const Fp& v) {
+#pragma unroll
+        for (int k = 0; k < 5; k++) l[k].mac(a.c[k].v, v.v);
+    }
+    VG_HD void mac(const Ext5& a, const Ext5& b) {  // the 25 multiply-adds of Ext5::operator*
+        Fp d[5];
+#pragma unroll
+        for (int j = 0; j < 5; j++) d[j] = b.c[j] + b.c[j];
+#pragma unroll
+        for (int k = 0; k < 5; k++)
+#pragma unroll
+            for (int i = 0; i < 5; i++) l[k].mac(a.c[i].v, i <= k ? b.c[k - i].v : d[k + 5 - i].v);
+    }
+    VG_HD Ext5 reduce() const { Ext5 r; for (int k = 0; k < 5; k++) r.c[k] = Fp::raw(l[k].reduce()); return r; }
 };
 
 VG_HD uint32_t reverse_bits_len(uint32_t x, unsigned bits) {

@@ -88,6 +88,11 @@ enum FieldProbeOp {
 bool field_probe_shape(uint32_t op, int* in_words, int* out_words);  // words per item; false: unknown op
 void field_probe_check_twiddle_range(uint32_t op, const uint32_t* in_host, uint64_t n);
 void launch_field_probe(hipStream_t st, uint32_t op, const uint32_t* in_dev, uint64_t n, const DeviceTables& tb, const uint32_t* pos_dev, bool sparse, uint32_t* out_dev);
+// lazy_probe.hip (test hook): fold_hi, the Ext5 product and the lazily folded sums of field.hpp (LazyAcc / ExtAcc) on n operand tuples of raw stored
+// words, laid out as the field probe's.  `terms` = the length of a sum (0 for the two ops that have none); shapes and lengths: lazy_probe_shape.
+enum LazyProbeOp { LP_FOLD_HI = 0, LP_EXT_MUL, LP_LIN_DOT, LP_EXT_DOT, LP_LIN_DOT_LOOP, LAZY_PROBE_OPS };
+bool lazy_probe_shape(uint32_t op, uint32_t terms, int* in_words, int* out_words);  // words per item; false: unknown op or a length the op is not built for
+void launch_lazy_probe(hipStream_t st, uint32_t op, uint32_t terms, const uint32_t* in_dev, uint64_t n, uint32_t* out_dev);
 // ntt.hip
 void launch_intt(hipStream_t st, DMatView m, const DeviceTables& tb);
 void launch_coset_ntt(hipStream_t st, DMatView coeffs, DMatView dst, uint64_t dst_row0, Fp shift, const DeviceTables& tb);

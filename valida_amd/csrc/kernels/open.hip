@@ -356,36 +356,28 @@ __global__ void __launch_bounds__(256) k_reduce_openings(const uint32_t* __restr
         const uint64_t stride = ((uint64_t)md[3] << 32) | md[2];
         const uint32_t width = md[4], npts = md[5];
         md += 6;
-        // reduced row sum_c alpha^c * M[j][c], lazily: 4 columns per Montgomery reduction and limb.  The kernel is a stream over
-        // every committed LDE (2 GB per proof) and lives on memory-level parallelism: SIXTEEN independent column loads are issued
-        // before the first is consumed (the alpha powers are wave-uniform scalar loads).
-        Ext5 rr = Ext5::zero();
+        // reduced row sum_c alpha^c * M[j][c].  The kernel is a stream over every committed LDE (2 GB per proof) and lives on
+        // memory-level parallelism: SIXTEEN independent column loads are issued before the first is consumed (the alpha powers are
+        // wave-uniform scalar loads).
+        // All of a row's terms go on ONE lazy sum per limb (vg::ExtAcc: a fold of the high word between the products, one Montgomery
+        // reduction per matrix and limb); the loops are rolled here, so the sums carry their fold state as a wave-uniform scalar.
+        vg::ExtAcc ra = vg::ExtAcc::zero();
         uint32_t c = 0;
         for (; c + 16 <= width; c += 16) {
             uint32_t v[16];
 #pragma unroll
             for (int u = 0; u < 16; u++) v[u] = colp[(uint64_t)(c + u) * stride + j];
 #pragma unroll
-            for (int g = 0; g < 16; g += 4) {
-                const uint32_t* a0 = apow + 5 * (c + g);
-#pragma unroll
-                for (int k = 0; k < 5; k++) {
-                    uint64_t t = (uint64_t)a0[k] * v[g] + (uint64_t)a0[5 + k] * v[g + 1] + (uint64_t)a0[10 + k] * v[g + 2] + (uint64_t)a0[15 + k] * v[g + 3];
-                    rr.c[k] += Fp::raw(vg::monty_reduce_wide(t));
-                }
-            }
+            for (int u = 0; u < 16; u++) ra.mac(apow + 5 * (c + u), v[u]);
         }
         for (; c + 4 <= width; c += 4) {
             const uint32_t v0 = colp[(uint64_t)c * stride + j], v1 = colp[(uint64_t)(c + 1) * stride + j];
             const uint32_t v2 = colp[(uint64_t)(c + 2) * stride + j], v3 = colp[(uint64_t)(c + 3) * stride + j];
             const uint32_t* a0 = apow + 5 * c;
-#pragma unroll
-            for (int k = 0; k < 5; k++) {
-                uint64_t t = (uint64_t)a0[k] * v0 + (uint64_t)a0[5 + k] * v1 + (uint64_t)a0[10 + k] * v2 + (uint64_t)a0[15 + k] * v3;
-                rr.c[k] += Fp::raw(vg::monty_reduce_wide(t));
-            }
+            ra.mac(a0, v0); ra.mac(a0 + 5, v1); ra.mac(a0 + 10, v2); ra.mac(a0 + 15, v3);
         }
-        for (; c < width; c++) rr += ext_from_words(apow + 5 * c) * Fp::raw(colp[(uint64_t)c * stride + j]);
+        for (; c < width; c++) ra.mac(apow + 5 * c, colp[(uint64_t)c * stride + j]);
+        const Ext5 rr = ra.reduce();
         for (uint32_t q = 0; q < npts; q++, md += 11) {
             Ext5 t = ext_from_words(md + 1) * (ext_from_words(md + 6) - rr);
             const uint32_t slot = md[0];
@@ -459,41 +451,56 @@ __global__ void __launch_bounds__(256) k_reduce_openings_rows(const uint32_t* __
         const uint64_t stride = ((uint64_t)md[3] << 32) | md[2];
         const uint32_t width = md[4], npts = md[5];
         md += 6;
-        Ext5 rr[R];
+        // A row's terms alpha^c M[row][c] go on ONE lazy sum per limb (vg::ExtAcc): four multiply-adds, then a fold of the high word per two
+        // more, and one Montgomery reduction per matrix, row and limb (a reduction per four columns and a modular add cost 10 instructions
+        // per limb and four columns, the folds cost 4).  The control flow below keeps the sums' fold state a compile-time constant at every
+        // multiply-add: the first eight-column step is peeled (it starts from empty sums: 4, fold, 2, fold, 2; every later one starts and
+        // ends full), the tail counts its sums as full whichever way it is entered (an empty one then pays one fold of zero), and the up to
+        // three last columns are nested tests instead of a loop.
+        vg::ExtAcc ra[R];
 #pragma unroll
-        for (int r = 0; r < R; r++) rr[r] = Ext5::zero();
-        auto four_cols = [&](const V& v0, const V& v1, const V& v2, const V& v3, const uint32_t* a0) {
-            uint32_t e0[R], e1[R], e2[R], e3[R];
-            RowVec<R>::get(v0, e0); RowVec<R>::get(v1, e1); RowVec<R>::get(v2, e2); RowVec<R>::get(v3, e3);
+        for (int r = 0; r < R; r++) ra[r] = vg::ExtAcc::zero();
+        auto one_col = [&](const V& v, const uint32_t* a0) {
+            uint32_t e[R];
+            RowVec<R>::get(v, e);
 #pragma unroll
-            for (int r = 0; r < R; r++)
-#pragma unroll
-                for (int k = 0; k < 5; k++) {
-                    const uint64_t t = (uint64_t)a0[k] * e0[r] + (uint64_t)a0[5 + k] * e1[r] + (uint64_t)a0[10 + k] * e2[r] + (uint64_t)a0[15 + k] * e3[r];
-                    rr[r].c[k] += Fp::raw(vg::monty_reduce_wide(t));
-                }
+            for (int r = 0; r < R; r++) ra[r].mac(a0, e[r]);
         };
-        uint32_t c = 0;
-        for (; c + 8 <= width; c += 8) {  // eight vector loads in flight
+        auto eight_cols = [&](uint32_t c0) {  // eight vector loads in flight
             V v[8];
 #pragma unroll
-            for (int u = 0; u < 8; u++) v[u] = *reinterpret_cast<const V*>(colp + (uint64_t)(c + u) * stride);
-            four_cols(v[0], v[1], v[2], v[3], apow + 5 * c);
-            four_cols(v[4], v[5], v[6], v[7], apow + 5 * (c + 4));
+            for (int u = 0; u < 8; u++) v[u] = *reinterpret_cast<const V*>(colp + (uint64_t)(c0 + u) * stride);
+#pragma unroll
+            for (int u = 0; u < 8; u++) one_col(v[u], apow + 5 * (c0 + u));
+        };
+        auto last_col = [&](uint32_t c0) { one_col(*reinterpret_cast<const V*>(colp + (uint64_t)c0 * stride), apow + 5 * c0); };
+        uint32_t c = 0;
+        if (width >= 8) {
+            eight_cols(0);
+            for (c = 8; c + 8 <= width; c += 8) eight_cols(c);
         }
-        for (; c + 4 <= width; c += 4) {
+#pragma unroll
+        for (int r = 0; r < R; r++)
+#pragma unroll
+            for (int k = 0; k < 5; k++) ra[r].l[k].room = 0;
+        if (c + 4 <= width) {
             V v[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) v[u] = *reinterpret_cast<const V*>(colp + (uint64_t)(c + u) * stride);
-            four_cols(v[0], v[1], v[2], v[3], apow + 5 * c);
-        }
-        for (; c < width; c++) {
-            uint32_t e[R];
-            RowVec<R>::get(*reinterpret_cast<const V*>(colp + (uint64_t)c * stride), e);
-            const Ext5 a = ext_from_words(apow + 5 * c);
 #pragma unroll
-            for (int r = 0; r < R; r++) rr[r] += a * Fp::raw(e[r]);
+            for (int u = 0; u < 4; u++) one_col(v[u], apow + 5 * (c + u));
+            c += 4;
         }
+        if (c < width) {
+            last_col(c);
+            if (c + 1 < width) {
+                last_col(c + 1);
+                if (c + 2 < width) last_col(c + 2);
+            }
+        }
+        Ext5 rr[R];
+#pragma unroll
+        for (int r = 0; r < R; r++) rr[r] = ra[r].reduce();
         for (uint32_t q = 0; q < npts; q++, md += 11) {
             const Ext5 coef = ext_from_words(md + 1), Y = ext_from_words(md + 6);
             const uint32_t slot = md[0];

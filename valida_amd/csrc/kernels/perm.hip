@@ -28,11 +28,12 @@ __global__ void __launch_bounds__(256) k_perm_recip(DMatView main, DMatView prep
         const uint32_t nf = iw[pos + 1];
         pos += 2;
         Fp mult = eval_vcol(iw, pos, main.data, main.stride, prep.data, prep.stride, n);
-        Ext5 rlc = ext_from_words(chal + 5 * m);
+        vg::ExtAcc t = vg::ExtAcc::zero();  // sum_j beta^j f_j on one lazy sum per limb, reduced once
         for (uint32_t j = 0; j < nf; j++) {
             Fp f = eval_vcol(iw, pos, main.data, main.stride, prep.data, prep.stride, n);
-            rlc += ext_from_words(betas + 5 * j) * f;
+            t.mac(betas + 5 * j, f.v);
         }
+        const Ext5 rlc = ext_from_words(chal + 5 * m) + t.reduce();
         Ext5 q = rlc.inv();  // inv(0) = 0
         store_ext(perm.data + (uint64_t)(5 * m) * perm.stride, perm.stride, n, q);
         Ext5 term = q * mult;
@@ -57,9 +58,8 @@ struct DevicePermRow {
     Ext5 rl[PERM_NATIVE_MAX_M];
     Fp mult[PERM_NATIVE_MAX_M];
     uint32_t snd;  // bit m: interaction m is a send
-    Ext5 rlc;
-    uint64_t t[5];
-    int pend, m, j;
+    vg::ExtAcc t;  // sum_j beta^j f_j of the interaction under way: one lazy sum per limb, reduced once in end()
+    int m, j;
     __device__ __forceinline__ Fp value(const vchips::Lin& f) const {
         Fp v = Fp::from_canonical(f.k);
 #pragma unroll
@@ -70,31 +70,22 @@ struct DevicePermRow {
             }
         return v;
     }
-    __device__ __forceinline__ void flush() {
-#pragma unroll
-        for (int c = 0; c < 5; c++) { rlc.c[c] += Fp::raw(vg::monty_reduce_wide(t[c])); t[c] = 0; }
-        pend = 0;
-    }
     // (the per-interaction slots are written through unrolled compares, never through a run-time index: where the visit's loops are not folded to a
     // compile-time m the arrays would otherwise move to scratch memory)
     __device__ __forceinline__ void begin(bool is_send, int) {
         snd |= (is_send ? 1u : 0u) << m;
-        rlc = ext_from_words(chal + 5 * m);
-#pragma unroll
-        for (int c = 0; c < 5; c++) t[c] = 0;
-        pend = 0; j = 0;
+        t = vg::ExtAcc::zero();
+        j = 0;
     }
     __device__ __forceinline__ void field(const vchips::Lin& f) {
         if (!(f.n == 0 && f.k == 0)) {
             const Fp x = value(f);
-#pragma unroll
-            for (int c = 0; c < 5; c++) t[c] += (uint64_t)betas[5 * j + c] * x.v;
-            if (++pend == 4) flush();
+            t.mac(betas + 5 * j, x.v);
         }
         j++;
     }
     __device__ __forceinline__ void end(const vchips::Lin& count) {
-        if (pend) flush();
+        const Ext5 rlc = ext_from_words(chal + 5 * m) + t.reduce();
         const Fp cnt = value(count);
 #pragma unroll
         for (int mm = 0; mm < PERM_NATIVE_MAX_M; mm++) if (mm == m) { rl[mm] = rlc; mult[mm] = cnt; }
@@ -108,7 +99,7 @@ __device__ __forceinline__ Ext5 perm_row_native(const DMatView& main, const uint
     DevicePermRow v;
     v.main = main.data; v.stride = main.stride; v.roff = (uint32_t)n * 4u;  // trace heights <= 2^27 rows: the byte offset fits
     v.chal = chal; v.betas = chal + 5 * M;
-    v.m = 0; v.pend = 0; v.j = 0; v.snd = 0;
+    v.m = 0; v.j = 0; v.snd = 0; v.t = vg::ExtAcc::zero();
     vchips::visit_interactions(CHIP, v);  // CHIP is a compile-time constant: straight-line code, v.m ends at M <= PERM_NATIVE_MAX_M
     Ext5 pre[PERM_NATIVE_MAX_M];
     Ext5 run = Ext5::one();

@@ -97,10 +97,16 @@ __device__ __forceinline__ Ext5 run_program_lds(const QuotientArgs& a, const Poi
 // chips' unchanged `eval` templates (chips/basic_machine.hpp) are instantiated over it, so every constraint
 // becomes straight-line VALU code with column loads the compiler schedules and CSEs — no interpretation.
 // assert_zero(c_k) accumulates alpha^(K-1-k) * c_k LAZILY: five v_mad_u64_u32 per constraint into 64-bit limb
-// accumulators, one Montgomery reduction per limb for every four constraints (4 p^2 < 2^64).
+// accumulators (vg::ExtAcc) that are folded in their high words between the constraints (four, then a fold per two) and
+// Montgomery-reduced ONCE per limb, behind the chip's last constraint.
 #ifndef VGPU_QUOT_SADDR
 #define VGPU_QUOT_SADDR 1  // 1: column loads as uniform base (SGPR pair: data + col * stride) + the point's 32-bit byte offset (global_load ... v_off, s[base]); 0: 64-bit per-lane addresses (A/B)
 #endif
+// ONE_SUM = false (the cpu chip): the former form, a Montgomery reduction per four constraints added into `total`.  As one sum the
+// scheduler, no longer held by the reductions, draws the constraints' loads and products together until the cpu chip's kernel needs more
+// than the 80 VGPRs of six waves per SIMD and spills (80, none spilled, in this form); a scheduling fence behind every fourth constraint
+// keeps it at 74 but the kernel then ran 17 % slower (0.325 -> 0.379 ms of a lone proof; profiles/r17_lazy_sums_isa.txt).
+template <bool ONE_SUM>
 struct DeviceFolder {
     using Expr = Fp;
 #if VGPU_QUOT_SADDR
@@ -121,9 +127,9 @@ struct DeviceFolder {
 #endif
     Fp first, last, trans;
     const uint32_t* __restrict__ apow;  // alpha powers, 5 words per constraint (wave-uniform: scalar loads)
-    uint64_t t[5];
+    vg::ExtAcc t;
     Ext5 total;
-    int k, pending;
+    int k;
     __device__ __forceinline__ Fp constant(uint32_t c) const { return Fp::from_canonical(c); }
 #if VGPU_QUOT_SADDR
     __device__ __forceinline__ Fp main(int col, bool next) const { return Fp::raw(load_at((next ? main_n : main_p) + (uint64_t)col * mstride, next ? noff : roff)); }
@@ -135,18 +141,16 @@ struct DeviceFolder {
     __device__ __forceinline__ Fp is_first_row() const { return first; }
     __device__ __forceinline__ Fp is_last_row() const { return last; }
     __device__ __forceinline__ Fp is_transition() const { return trans; }
-    __device__ __forceinline__ void flush() {
-#pragma unroll
-        for (int c = 0; c < 5; c++) { total.c[c] += Fp::raw(vg::monty_reduce_wide(t[c])); t[c] = 0; }
-        pending = 0;
-    }
     // (two alternating accumulator sets were measured in round 6: the cpu chip's kernel drops to 3 waves per SIMD and runs 7x slower — the
     // accumulators are not a dependency chain, the powers of alpha are precomputed; profiles/r06_ab_quotient_acc2_poseidon_waves.txt)
     __device__ __forceinline__ void assert_zero(const Fp& e) {
-#pragma unroll
-        for (int c = 0; c < 5; c++) t[c] += (uint64_t)apow[5 * k + c] * e.v;
+        t.mac(apow + 5 * k, e.v);
         k++;
-        if (++pending == 4) flush();
+        if (!ONE_SUM && t.l[0].room == 0) { total += t.reduce(); t = vg::ExtAcc::zero(); }
+    }
+    __device__ __forceinline__ Ext5 sum() const {
+        if (ONE_SUM) return t.reduce();
+        return t.l[0].room != 4 ? total + t.reduce() : total;
     }
 };
 
@@ -154,7 +158,7 @@ struct DeviceFolder {
 template <int CHIP>
 __device__ __forceinline__ Ext5 run_native(const QuotientArgs& a, const PointCtx& p) {
     if (CHIP < 0) return Ext5::zero();
-    DeviceFolder f;
+    DeviceFolder<CHIP != vchips::CHIP_CPU> f;
 #if VGPU_QUOT_SADDR
     f.main_p = a.main_lde.data; f.main_n = a.main_nx; f.mstride = a.main_lde.stride;
     f.prep_p = a.prep_lde.data; f.prep_n = a.prep_nx; f.pstride = a.prep_lde.stride;
@@ -165,13 +169,11 @@ __device__ __forceinline__ Ext5 run_native(const QuotientArgs& a, const PointCtx
 #endif
     f.first = p.is_first; f.last = p.is_last; f.trans = p.is_trans;
     f.apow = a.consts;
+    f.t = vg::ExtAcc::zero();
     f.total = Ext5::zero();
-    f.k = 0; f.pending = 0;
-#pragma unroll
-    for (int c = 0; c < 5; c++) f.t[c] = 0;
+    f.k = 0;
     vchips::eval_chip(CHIP, f);  // CHIP is a compile-time constant: the switch folds to the one chip
-    if (f.pending) f.flush();
-    return f.total;
+    return f.sum();
 }
 
 // eval_permutation_constraints at one point: M reciprocal constraints + transition/first/last.
@@ -198,19 +200,13 @@ __device__ __forceinline__ Ext5 perm_constraints(const QuotientArgs& a, const Po
         uint32_t pos_n = pos;
         Fp mult_local = eval_vcol_at(iw, pos, a.main_lde.data, a.main_lde.stride, a.prep_lde.data, a.prep_lde.stride, roff);
         Fp mult_next = eval_vcol_at(iw, pos_n, a.main_nx, a.main_lde.stride, a.prep_nx, a.prep_lde.stride, noff);
-        // rlc = alpha_bus + sum_j beta^j f_j: Ext5 x base products accumulated four at a time per limb
-        Ext5 rlc = ext_from_words(bus + 5 * m);
-        for (uint32_t j0 = 0; j0 < nf; j0 += 4) {
-            uint64_t t[5] = {0, 0, 0, 0, 0};
-            const uint32_t je = nf - j0 < 4 ? nf - j0 : 4;
-            for (uint32_t j = 0; j < je; j++) {
-                Fp f = eval_vcol_at(iw, pos, a.main_lde.data, a.main_lde.stride, a.prep_lde.data, a.prep_lde.stride, roff);
-#pragma unroll
-                for (int c = 0; c < 5; c++) t[c] += (uint64_t)betas[5 * (j0 + j) + c] * f.v;
-            }
-#pragma unroll
-            for (int c = 0; c < 5; c++) rlc.c[c] += Fp::raw(vg::monty_reduce_wide(t[c]));
+        // rlc = alpha_bus + sum_j beta^j f_j: the Ext5 x base products on one lazy sum per limb, reduced once
+        vg::ExtAcc t = vg::ExtAcc::zero();
+        for (uint32_t j = 0; j < nf; j++) {
+            Fp f = eval_vcol_at(iw, pos, a.main_lde.data, a.main_lde.stride, a.prep_lde.data, a.prep_lde.stride, roff);
+            t.mac(betas + 5 * j, f.v);
         }
+        const Ext5 rlc = ext_from_words(bus + 5 * m) + t.reduce();
         const uint32_t* pcol = a.perm_lde.data + (uint64_t)(5 * m) * a.perm_lde.stride;
         Ext5 pl = load_ext_at(pcol, a.perm_lde.stride, roff), pn = load_ext_at(a.perm_nx + (uint64_t)(5 * m) * a.perm_lde.stride, a.perm_lde.stride, noff);
         acc += ext_from_words(apow + 5 * m) * (rlc * pl - Fp::one());  // assert_one_ext(rlc * perm_local[m])
@@ -231,6 +227,9 @@ __device__ __forceinline__ Ext5 perm_constraints(const QuotientArgs& a, const Po
 // (chips/basic_machine.hpp: visit_interactions, the one definition the host's Interaction lists are collected from as well), so for a native chip
 // the visit is instantiated over this evaluator: every field is a load at a compile-time column, the whole point's loads are the compiler's to
 // hoist and batch, the betas / bus alphas / alpha powers are scalar loads at compile-time offsets.  Same values (exact field arithmetic).
+// ONE_SUM = false (the shift chip): the former form, a Montgomery reduction per four fields added into `rlc` — as one sum its kernel needs
+// 80 VGPRs and spills where it took 64.
+template <bool ONE_SUM>
 struct DevicePerm {
     const QuotientArgs& a;
     uint32_t roff, noff;
@@ -238,8 +237,8 @@ struct DevicePerm {
     const uint32_t* bus;
     const uint32_t* betas;
     Ext5 acc, rhs, phi_0, rlc;
-    uint64_t t[5];
-    int pend, m, j;
+    vg::ExtAcc t;  // sum_j beta^j f_j of the interaction under way: one lazy sum per limb, reduced once in end()
+    int m, j;
     bool send;
     __device__ __forceinline__ Fp value(const vchips::Lin& f, bool next) const {
         Fp v = Fp::from_canonical(f.k);
@@ -251,29 +250,22 @@ struct DevicePerm {
             }
         return v;
     }
-    __device__ __forceinline__ void flush() {
-#pragma unroll
-        for (int c = 0; c < 5; c++) { rlc.c[c] += Fp::raw(vg::monty_reduce_wide(t[c])); t[c] = 0; }
-        pend = 0;
-    }
     __device__ __forceinline__ void begin(bool is_send, int) {
         send = is_send;
         rlc = ext_from_words(bus + 5 * m);
-#pragma unroll
-        for (int c = 0; c < 5; c++) t[c] = 0;
-        pend = 0; j = 0;
+        t = vg::ExtAcc::zero();
+        j = 0;
     }
     __device__ __forceinline__ void field(const vchips::Lin& f) {
         if (!(f.n == 0 && f.k == 0)) {  // a zero field adds nothing to the combination
             const Fp x = value(f, false);
-#pragma unroll
-            for (int c = 0; c < 5; c++) t[c] += (uint64_t)betas[5 * j + c] * x.v;
-            if (++pend == 4) flush();
+            t.mac(betas + 5 * j, x.v);
+            if (!ONE_SUM && t.l[0].room == 0) { rlc += t.reduce(); t = vg::ExtAcc::zero(); }
         }
         j++;
     }
     __device__ __forceinline__ void end(const vchips::Lin& count) {
-        if (pend) flush();
+        if (ONE_SUM || t.l[0].room != 4) rlc += t.reduce();
         const Fp mult_local = value(count, false), mult_next = value(count, true);
         const Ext5 pl = load_ext_at(a.perm_lde.data + (uint64_t)(5 * m) * a.perm_lde.stride, a.perm_lde.stride, roff);
         const Ext5 pn = load_ext_at(a.perm_nx + (uint64_t)(5 * m) * a.perm_lde.stride, a.perm_lde.stride, noff);
@@ -286,8 +278,8 @@ struct DevicePerm {
 template <int CHIP>
 __device__ __forceinline__ Ext5 perm_constraints_native(const QuotientArgs& a, const PointCtx& p) {
     const uint32_t M = a.iw[0], maxf = a.iw[1];
-    DevicePerm v{a, (uint32_t)p.row * 4u, (uint32_t)p.next_row * 4u, a.consts + 5 * a.n_air_asserts, a.consts + 5 * a.K, a.consts + 5 * a.K + 5 * M,
-                 Ext5::zero(), Ext5::zero(), Ext5::zero(), Ext5::zero(), {0, 0, 0, 0, 0}, 0, 0, 0, false};
+    DevicePerm<CHIP != vchips::CHIP_SHIFT> v{a, (uint32_t)p.row * 4u, (uint32_t)p.next_row * 4u, a.consts + 5 * a.n_air_asserts, a.consts + 5 * a.K, a.consts + 5 * a.K + 5 * M,
+                 Ext5::zero(), Ext5::zero(), Ext5::zero(), Ext5::zero(), vg::ExtAcc::zero(), 0, 0, false};
     vchips::visit_interactions(CHIP, v);  // CHIP is a compile-time constant: the visit unrolls into straight-line code; v.m ends at M
     const Ext5 cumulative_sum = ext_from_words(v.betas + 5 * maxf);
     const Ext5 phi_local = load_ext_at(a.perm_lde.data + (uint64_t)(5 * v.m) * a.perm_lde.stride, a.perm_lde.stride, v.roff);
