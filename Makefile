@@ -7,7 +7,7 @@ HIPCC ?= hipcc
 ARCH ?= gfx950
 CSRC := valida_amd/csrc
 SRCS := kernels/ntt.hip kernels/layout.hip kernels/merkle.hip kernels/poseidon_mmcs.hip kernels/perm.hip kernels/quotient.hip kernels/open.hip \
-        kernels/tracegen.hip kernels/verify.hip kernels/bus_audit.hip kernels/constraint_audit.hip kernels/mutation_audit.hip kernels/coverage_audit.hip kernels/pair_audit.hip kernels/rank_audit.hip kernels/field_audit.hip kernels/link_audit.hip kernels/step_audit.hip kernels/invariant_audit.hip kernels/transition_audit.hip kernels/product_audit.hip kernels/domain_audit.hip kernels/memory_audit.hip kernels/program_audit.hip kernels/field_probe.hip kernels/lazy_probe.hip host/prover.cpp host/prover_audits.cpp host/sharded_prover.cpp capi.cpp
+        kernels/tracegen.hip kernels/verify.hip kernels/bus_audit.hip kernels/constraint_audit.hip kernels/mutation_audit.hip kernels/coverage_audit.hip kernels/pair_audit.hip kernels/rank_audit.hip kernels/field_audit.hip kernels/link_audit.hip kernels/step_audit.hip kernels/invariant_audit.hip kernels/transition_audit.hip kernels/product_audit.hip kernels/domain_audit.hip kernels/memory_audit.hip kernels/program_audit.hip kernels/arithmetic_audit.hip kernels/field_probe.hip kernels/lazy_probe.hip host/prover.cpp host/prover_audits.cpp host/sharded_prover.cpp capi.cpp
 OBJS := $(addprefix build/make/,$(addsuffix .o,$(subst /,_,$(SRCS))))
 HDRS := $(shell find $(CSRC) -name '*.hpp' -o -name '*.h') include/vgpu.h
 FLAGS := --offload-arch=$(ARCH) -O3 -std=c++17 -fPIC -Wno-unused-result

@@ -1186,7 +1186,8 @@ void vgpu_memory_report_free(vgpu_memory_report_t* r);
  *   lists     findings: the first max_findings hard findings, TABLE_KEY by i, then the fetch findings by row, then MULTIPLICITY by i; wrapped:
  *             the first max_findings WRAPPED_OPERAND rows in row order; unfetched: the first max_ranges ranges [lo, hi), ascending.
  * What it is not: it judges the fetches against the table of THIS witness only.  It does not ask whether the opcode flags fit the opcode,
- * whether the step did what the opcode says, or whether the preprocessed commitment is the verifier's.
+ * whether the step did what the opcode says (for the ALU results that is the arithmetic audit's question, below), or whether the preprocessed
+ * commitment is the verifier's.
  * vgpu_program_audit runs on the device (kernels/program_audit.hip), queued on the prover context, wave64, workgroups of 256: k_pg_hist (the
  * fetch counts in an LDS histogram of min(table height, 32768) bins per workgroup, taller tables in slices; a wave whose live lanes hold one pc
  * adds once), k_pg_judge (a thread per fetch: kind, mask, the window to the next row through an LDS tile with one halo row; counters by ballots,
@@ -1230,6 +1231,75 @@ const uint32_t* vgpu_program_report_words(const vgpu_program_report_t* r);
 /* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: fetches + table rows */
 void vgpu_program_report_timing(const vgpu_program_report_t* r, double out[3]);
 void vgpu_program_report_free(vgpu_program_report_t* r);
+
+/* ---- Arithmetic audit: the memory audit asks whether the memory table is a memory and the program audit whether the fetches match the ROM; this
+ * one asks whether the ALU records compute their opcode.  `div`'s eval is a TODO in the reference, the field audit reports all 13 fields of its
+ * receive as floating, `shift` delegates to `mul` and `div` on the general bus with a power of two as operand, and `lt`, `com`, `mul` and
+ * `bitwise` are only as tight as their transcribed constraints: a result planted consistently in the ALU chip's row, the cpu's write channel and
+ * the memory table passes every other audit.  This audit replays the general bus as arithmetic.  Inputs: exactly what vgpu_prove and the audits
+ * take.
+ *   options   max_findings (64, at most 2^20; in a struct taken as given: 0 lists nothing and every count stays exact), bus_is_global (1) and
+ *             bus_index (0: the BasicMachine's general bus), sides (1; bit 0 the receives, bit 1 the sends: with bit 1 the cpu's own send
+ *             (opcode, read 1, read 2, write, clk) is judged by the same rule), reserved (0).  A null pointer gives these defaults.
+ *             VGPU_ERR_INVALID_ARG before anything is queued, the message naming the reason: an entry with fewer than 13 fields, a bus with no
+ *             entry on the selected sides, sides outside 1..3, max_findings above 2^20, a non-zero reserved, more than 2^32 - 2 slots.
+ *   entries   an ENTRY is a (chip, interaction) on that bus and a selected side, in ascending (chip, interaction) order, read through its vcols
+ *             by the descriptor walk of the bus audit: the compiled and the interpreting machine give the same words.  Fields 0..12 are opcode,
+ *             x[0..3], y[0..3], z[0..3], word bytes most significant first; fields beyond 12 (the clk of output and cpu) are ignored.
+ *   records   a SLOT is (entry, row), LIVE iff its count vcol is non-zero at that row (lt's count is a multiplicity: any non-zero value is
+ *             live); values canonical.  A live record is JUDGED iff its opcode is in 100..118, the nineteen ALU opcodes (index opcode - 100: ADD
+ *             SUB MUL DIV LT SHL SHR AND OR XOR SDIV NE MULHU SRA MULHS LTE EQ SLT SLE), otherwise OTHER (WRITE 300 at output): counted, never
+ *             judged.
+ *   expected  the arithmetic the reference runs: ADD, SUB, MUL the low word; MULHU AND MULHS the unsigned high word of the 64-bit product (the
+ *             reference zero-extends, machine/src/core.rs:146-158); DIV the unsigned quotient; SDIV the signed quotient truncated toward zero;
+ *             SHL, SHR shift by y; SRA shifts by y and replicates the sign; AND, OR, XOR bitwise; LT, LTE unsigned, SLT, SLE signed, NE, EQ;
+ *             a boolean result is the word (0, 0, 0, r).
+ *   findings  per judged record at most one kind, the first that applies: 1 MALFORMED (some field among 1..12 is >= 256; mask: bit j - 1 for
+ *             field j); 2 UNDEFINED (reason 1: DIV or SDIV with y = 0, 2: SDIV of 0x80000000 by 0xFFFFFFFF, 3: SHL, SHR or SRA with y >= 32;
+ *             the VM refuses these, so no honest witness holds one); no finding if z is the expected word; 4 SHIFT_QUOTIENT (an SDIV record
+ *             with y = 2^k, k <= 31, and z = sra(x, k), which differs from the truncated quotient: the shift chip's delegation of SRA to div,
+ *             alu_u32/src/shift/mod.rs); 5 ARITHMETIC_SHR (an SHR record with z = sra(x, y), which differs from x >> y: the reference logs SRA
+ *             rows as Shr32, shift/mod.rs:325-328); 3 WRONG_RESULT otherwise.  mask of kinds 3, 4, 5: the differing bytes of z, bit j for z[j].
+ *             Kinds 1, 2, 3 are HARD, 4 and 5 SOFT: counted and listed apart, never a fault.
+ *   counters  exact: slots, live, judged, other, one count per opcode, per kind and per UNDEFINED reason, mulhs_sign_matters (the well-formed
+ *             MULHS records whose signed high word differs from the unsigned one: the rows on which the reference's MULHS is not the ISA's;
+ *             counted, never a finding), per entry live and hard.
+ *   lists     the first max_findings hard findings, then the first max_findings soft findings, each in slot order: entry-major, rows ascending.
+ * What it is not: it judges each record alone, and this witness only.  Whether senders and receivers agree is the bus audit's question.  It does
+ * not read the chips' auxiliary columns (carries, bit decompositions, power_of_two) and says nothing about the cpu's flags, pc or fp.
+ * vgpu_arithmetic_audit runs on the device (kernels/arithmetic_audit.hip), queued on the prover context, wave64, workgroups of 256: k_ar_judge (a
+ * launch per entry, a thread per row: one descriptor walk, the rule in plain u32 / u64 integer code, one packed verdict word per slot; counters by
+ * ballots, LDS, one integer atomicAdd per counter and workgroup), the memory audit's scan over the two workgroup tables, k_ar_list (a thread per
+ * row reads its verdict; a listed finding walks the descriptor again).  The only atomics are integer add: every word is the same run after run.
+ * Scratch from the pool, its totals zeroed by one memset; VGPU_ERR_OOM with the arithmetic when the pool cannot give it.
+ * vgpu_arithmetic_audit_host: the same contract on the host, one thread.
+ * Report image (vgpu_arithmetic_report_words, u32 words; u64 values as lo, hi; field values canonical):
+ *   [0] 0x31524156 "VAR1" [1] word count [2] bus_is_global [3] bus_index [4] sides [5] truncated (bit 0 hard list, bit 1 soft list) [6] listed
+ *   hard [7] listed soft [8] max_findings [9] entries [10,11] slots [12,13] live [14,15] judged [16,17] other [18,19] hard [20,21] malformed
+ *   [22,23] undefined [24,25] wrong_result [26,27] soft [28,29] shift_quotient [30,31] arithmetic_shr [32,33] mulhs_sign_matters [34,35]
+ *   division by zero [36,37] signed overflow [38,39] shift range [40..77] the nineteen opcode counts [78,79] 0
+ *   per entry 8 words: chip, interaction, is_send, n_fields, live (lo, hi), hard (lo, hi)
+ *   per listed hard finding, then per listed soft finding, 24 words: [0] kind [1] mask or reason [2] chip [3] interaction [4] row [5] opcode
+ *   [6..9] x [10..13] y [14..17] z [18] expected word (0 for kinds 1 and 2) [19] count [20] is_send [21..23] 0 */
+typedef struct vgpu_arithmetic_audit_opts {
+    uint32_t max_findings;
+    uint32_t bus_is_global;
+    uint32_t bus_index;
+    uint32_t sides;
+    uint32_t reserved;
+} vgpu_arithmetic_audit_opts_t;
+typedef struct vgpu_arithmetic_report vgpu_arithmetic_report_t;
+int32_t vgpu_arithmetic_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                              uint32_t n_prep, const vgpu_arithmetic_audit_opts_t* opts, vgpu_arithmetic_report_t** out);
+/* main[i]: canonical row-major heights[i] x widths[i]; prep[k] (prep_heights[k] x prep_widths[k]) belongs to chip prep_chips[k] */
+int32_t vgpu_arithmetic_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                                   const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                                   const vgpu_arithmetic_audit_opts_t* opts, vgpu_arithmetic_report_t** out);
+uint64_t vgpu_arithmetic_report_len(const vgpu_arithmetic_report_t* r);
+const uint32_t* vgpu_arithmetic_report_words(const vgpu_arithmetic_report_t* r);
+/* out[0]: the device pass (0 for the host audit), out[1]: wall time of the whole call; milliseconds.  out[2]: the live records */
+void vgpu_arithmetic_report_timing(const vgpu_arithmetic_report_t* r, double out[3]);
+void vgpu_arithmetic_report_free(vgpu_arithmetic_report_t* r);
 
 /* ---- Coverage audit: WHICH constraint or bus interaction detects each mutation of the mutation audit — per detector: does this witness exercise
  * it at all, and is it ever the only thing that catches a change.  Inputs: exactly what vgpu_prove and the audits take.

@@ -253,6 +253,10 @@ class Workload:
         """The host program audit of this workload's own witness with rom_len = program_len: the table's zero padding rows are not fetchable."""
         return program_audit_host(Machine.basic(), self.main_traces(), self.preprocessed(), rom_len=self.program_len, max_findings=max_findings, max_ranges=max_ranges)
 
+    def arithmetic_audit_host(self, max_findings=64, sides="receives"):
+        """The host arithmetic audit of this workload's own witness: the general bus's records recomputed as 32-bit arithmetic."""
+        return arithmetic_audit_host(Machine.basic(), self.main_traces(), self.preprocessed(), max_findings=max_findings, sides=sides)
+
     def __del__(self):
         if getattr(self, "_h", None):
             try:
@@ -1932,6 +1936,99 @@ def program_audit_host(machine, main_matrices, preprocessed, rom_len=0, max_find
     return _audit_host("program", machine, main_matrices, preprocessed, _program_opts(rom_len, max_findings, max_ranges, fetch, table))
 
 
+class ArithmeticAuditOpts(ctypes.Structure):  # vgpu_arithmetic_audit_opts_t
+    _fields_ = [("max_findings", ctypes.c_uint32), ("bus_is_global", ctypes.c_uint32), ("bus_index", ctypes.c_uint32), ("sides", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
+ARITHMETIC_OPCODES = ("ADD32", "SUB32", "MUL32", "DIV32", "LT32", "SHL32", "SHR32", "AND32", "OR32", "XOR32", "SDIV32", "NE32", "MULHU32", "SRA32", "MULHS32", "LTE32", "EQ32", "SLT32",
+                      "SLE32")  # opcode 100 + index
+ARITHMETIC_KINDS = ("malformed", "undefined", "wrong_result", "shift_quotient", "arithmetic_shr")
+ARITHMETIC_HARD_KINDS = ARITHMETIC_KINDS[:3]
+ARITHMETIC_SOFT_KINDS = ARITHMETIC_KINDS[3:]
+ARITHMETIC_REASONS = ("division_by_zero", "signed_overflow", "shift_range")
+ARITHMETIC_COUNTERS = ("slots", "live", "judged", "other", "hard", "malformed", "undefined", "wrong_result", "soft", "shift_quotient", "arithmetic_shr", "mulhs_sign_matters") + ARITHMETIC_REASONS
+ARITHMETIC_SIDES = dict(receives=1, sends=2, both=3)
+
+
+class ArithmeticReport(_AuditReport):
+    """The arithmetic audit of a witness (vgpu_arithmetic_audit / vgpu_arithmetic_audit_host; the contract is stated in include/vgpu.h), as
+    plain Python values: words (the image), bus = (is_global, bus_index), sides, max_findings, truncated = (hard, soft),
+    counters = dict(slots, live, judged, other, hard, malformed, undefined, wrong_result, soft, shift_quotient, arithmetic_shr,
+    mulhs_sign_matters, division_by_zero, signed_overflow, shift_range), opcodes = dict(name -> judged records),
+    entries = [dict(chip, interaction, is_send, n_fields, live, hard)], hard = the listed hard findings and soft = the listed soft ones, each
+    [dict(kind, mask (the reason of an undefined record), chip, interaction, row, opcode, x, y, z (four bytes each, most significant first),
+    expected (the word the opcode computes; 0 for malformed and undefined), count, is_send)], device_ms (the device pass; 0.0 for the host
+    audit), host_ms (the whole call), evaluations (the live records).  It judges each record alone; soft findings are never a fault."""
+
+    def __init__(self, words, device_ms=0.0, host_ms=0.0, evaluations=0.0):
+        w = [int(x) for x in words]
+        if len(w) < 80 or w[0] != 0x31524156 or w[1] != len(w) or len(w) != 80 + 8 * w[9] + 24 * (w[6] + w[7]):
+            raise ValueError("not an arithmetic report image")
+        self.words = np.array(w, dtype=np.uint32)
+        self.device_ms, self.host_ms, self.evaluations = float(device_ms), float(host_ms), float(evaluations)
+
+        def u64(at):
+            return w[at] | (w[at + 1] << 32)
+
+        self.bus, self.sides, self.max_findings = (bool(w[2]), w[3]), w[4], w[8]
+        self.truncated = (bool(w[5] & 1), bool(w[5] & 2))
+        self.counters = {name: u64(10 + 2 * k) for k, name in enumerate(ARITHMETIC_COUNTERS)}
+        self.opcodes = {name: u64(40 + 2 * k) for k, name in enumerate(ARITHMETIC_OPCODES)}
+        pos = 80
+        self.entries = []
+        for _ in range(w[9]):
+            self.entries.append(dict(chip=w[pos], interaction=w[pos + 1], is_send=bool(w[pos + 2]), n_fields=w[pos + 3], live=u64(pos + 4), hard=u64(pos + 6)))
+            pos += 8
+        self.hard, self.soft = [], []
+        for n, into in ((w[6], self.hard), (w[7], self.soft)):
+            for _ in range(n):
+                f = w[pos:pos + 24]
+                into.append(dict(kind=ARITHMETIC_KINDS[f[0] - 1], mask=f[1], chip=f[2], interaction=f[3], row=f[4], opcode=f[5], x=f[6:10], y=f[10:14], z=f[14:18], expected=f[18],
+                                 count=f[19], is_send=bool(f[20])))
+                pos += 24
+
+    @property
+    def total_hard(self):
+        return self.counters["hard"]
+
+    @property
+    def total_soft(self):
+        return self.counters["soft"]
+
+    def to_dict(self):
+        return dict(words=[int(x) for x in self.words], bus=list(self.bus), sides=self.sides, max_findings=self.max_findings, truncated=list(self.truncated), counters=self.counters,
+                    opcodes=self.opcodes, entries=self.entries, hard=self.hard, soft=self.soft, device_ms=self.device_ms, host_ms=self.host_ms, evaluations=self.evaluations)
+
+    @classmethod
+    def from_dict(cls, d):
+        """The report of to_dict()'s object (a `check --arithmetic` JSON report's "arithmetic" key)."""
+        return cls(d["words"], d.get("device_ms", 0.0), d.get("host_ms", 0.0), d.get("evaluations", 0.0))
+
+
+def _arithmetic_opts(max_findings, bus, sides):
+    """bus: None (global bus 0, the BasicMachine's general bus), a global bus index, or (is_global, bus_index); sides: "receives", "sends",
+    "both" or the bit set itself (bit 0 receives, bit 1 sends)."""
+    if int(max_findings) < 0 or int(max_findings) >= 1 << 32:
+        raise VgpuError(-1, "arithmetic_audit: max_findings must not be negative")
+    is_global, index = (True, 0) if bus is None else ((True, int(bus)) if isinstance(bus, (int, np.integer)) else (bool(bus[0]), int(bus[1])))
+    if index < 0 or index >= 1 << 32:
+        raise VgpuError(-1, "arithmetic_audit: bus names a bus index")
+    if isinstance(sides, str):
+        if sides not in ARITHMETIC_SIDES:
+            raise VgpuError(-1, "arithmetic_audit: sides is receives, sends or both (got %r)" % sides)
+        sides = ARITHMETIC_SIDES[sides]
+    if int(sides) < 0 or int(sides) >= 1 << 32:
+        raise VgpuError(-1, "arithmetic_audit: sides is 1 (receives), 2 (sends) or 3 (both)")
+    return ArithmeticAuditOpts(int(max_findings), 1 if is_global else 0, index, int(sides), 0)
+
+
+def arithmetic_audit_host(machine, main_matrices, preprocessed, max_findings=64, bus=None, sides="receives"):
+    """The arithmetic audit on the HOST (vgpu_arithmetic_audit_host: no device, one thread): main_matrices = one canonical matrix per chip,
+    preprocessed = [(chip index, matrix)], bus = None (global bus 0), a global bus index or (is_global, bus_index), sides = "receives", "sends"
+    or "both"; an ArithmeticReport back."""
+    return _audit_host("arithmetic", machine, main_matrices, preprocessed, _arithmetic_opts(max_findings, bus, sides))
+
+
 class TransitionAuditOpts(ctypes.Structure):  # vgpu_transition_audit_opts_t
     _fields_ = [("max_entries", ctypes.c_uint64), ("max_rows_per_entry", ctypes.c_uint32), ("chip_mask", ctypes.c_uint32), ("max_terms", ctypes.c_uint32),
                 ("min_gate_windows", ctypes.c_uint32), ("max_gates", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3)]
@@ -2354,7 +2451,7 @@ def coverage_audit_host(machine, main_matrices, preprocessed, deltas=None, max_c
     return _audit_host("coverage", machine, main_matrices, preprocessed, opts)
 
 
-_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, product=ProductReport, domain=DomainReport, memory=MemoryReport, program=ProgramReport, field=FieldReport,
+_AUDIT_REPORTS = dict(bus=BusReport, constraint=ConstraintReport, mutation=MutationReport, pair=PairReport, rank=RankReport, step=StepReport, invariant=InvariantReport, transition=TransitionReport, product=ProductReport, domain=DomainReport, memory=MemoryReport, program=ProgramReport, arithmetic=ArithmeticReport, field=FieldReport,
                       link=LinkReport, coverage=CoverageReport)
 
 
@@ -2644,6 +2741,12 @@ class Prover:
         witness's), fetch = None (the cpu) or (chip, pc_col, [field columns]), table = None (the program chip) or (chip, key_col, [word
         columns], mult_col); a ProgramReport back with the fetches and table rows that break the would-be program bus and the exact counters."""
         return self._audit("program", main, preprocessed, _program_opts(rom_len, max_findings, max_ranges, fetch, table))
+
+    def arithmetic_audit(self, main, preprocessed, max_findings=64, bus=None, sides="receives"):
+        """Whether the ALU records of this witness compute their opcode (vgpu_arithmetic_audit); the arguments of prove, bus = None (global
+        bus 0, the general bus), a global bus index or (is_global, bus_index), sides = "receives", "sends" or "both"; an ArithmeticReport back
+        with the records whose stored result is not what their opcode computes and the exact counters."""
+        return self._audit("arithmetic", main, preprocessed, _arithmetic_opts(max_findings, bus, sides))
 
     def transition_audit(self, main, preprocessed, max_entries=1024, max_rows_per_entry=4, max_terms=8, min_gate_windows=64, max_gates=256, chips=None):
         """Which affine-linear relations between a row and its successor this witness keeps, on every window or under a boolean gate, and at

@@ -38,6 +38,7 @@ SOURCES = [
     "kernels/domain_audit.hip",
     "kernels/memory_audit.hip",
     "kernels/program_audit.hip",
+    "kernels/arithmetic_audit.hip",
     "kernels/field_probe.hip",
     "kernels/lazy_probe.hip",
     "host/prover.cpp",

@@ -4,7 +4,7 @@
     python -m valida_amd.cli prove  PROGRAM PROOF_FILE  [ADVICE] [--stack-height N] [--max-cycles N] [--device D] [config flags]
     python -m valida_amd.cli verify PROGRAM PROOF_FILE  [ADVICE] [--device D] [config flags]
     python -m valida_amd.cli check  PROGRAM REPORT_FILE [ADVICE] [--stack-height N] [--max-cycles N] [--device D | --host] [--max-tuples N] [--max-records N]
-                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--products] [--domains] [--max-bits N] [--lookup-buses B[,B..]] [--memory] [--program] [--max-findings N] [--chips C[,C..]] [--deltas D[,D..]]
+                                                                [--constraints] [--max-constraints N] [--mutations] [--coverage] [--pairs] [--rank] [--fields] [--links] [--steps] [--step-sizes T[,T..]] [--invariants] [--transitions] [--min-gate-windows N] [--max-gates N] [--products] [--domains] [--max-bits N] [--lookup-buses B[,B..]] [--memory] [--program] [--arithmetic] [--sides receives|sends|both] [--max-findings N] [--chips C[,C..]] [--deltas D[,D..]]
     python -m valida_amd.coverage_merge OUT.json IN.json [IN.json ..]
 
 PROGRAM: raw machine code (24-byte little-endian records) or a little-endian ELF, read as load_executable_file reads it (elf/src/lib.rs:19-120).
@@ -133,9 +133,18 @@ check   the bus audit of the program's witness (vgpu_bus_audit: which LogUp tupl
         negative immediate mod p into the cpu row where the ROM holds p - |x|: counted apart, never a fault), and one summary line with the
         counters and the first ranges of words that never ran.  It judges the fetches against the table of THIS witness, not what the step did.
         Hard findings are definite faults: with --program, check exits 1 when there is one; wrapped operands never change the status.
+        --arithmetic adds the arithmetic audit of the same witness (vgpu_arithmetic_audit: every live record (opcode, x, y, z) of the general
+        bus recomputed in 32-bit integer arithmetic), on the same path (device or --host); --sides receives|sends|both selects the ALU chips'
+        receives (the default), the senders' records (the cpu's, and shift's delegations to mul and div), or both; --max-findings N lists the
+        first N of each list (default 64).  The JSON report gets one more key, "arithmetic" (ArithmeticReport.to_dict's object); stdout gets
+        one line per hard kind present, `div: 1 wrong result (row 2, DIV32: 100 / 7 = 15, expected 14)`, one line per soft kind (an SDIV
+        record by 2^k that holds the arithmetic shift: shift's delegation of SRA to div; an SHR record that holds the arithmetic shift: the
+        reference logs SRA rows as Shr32; counted apart, never a fault) and one summary line with the counters.  It judges each record alone
+        (whether senders and receivers agree is the bus audit's question).  Hard findings are definite faults: with --arithmetic, check exits
+        1 when there is one; soft findings never change the status.
 
 Config flags (--log-blowup, --queries, --pow-bits, --poseidon-mmcs, --constants) are verify_cli's and must match between prove and verify.
-Exit status: 0 on success (run / prove done, proof accepted, witness balanced, with --constraints every constraint satisfied, with --memory no memory finding and with --program no hard program finding), 1 otherwise (the reference always exits 0)."""
+Exit status: 0 on success (run / prove done, proof accepted, witness balanced, with --constraints every constraint satisfied, with --memory no memory finding, with --program no hard program finding and with --arithmetic no hard arithmetic finding), 1 otherwise (the reference always exits 0)."""
 import argparse
 import json
 import sys
@@ -486,10 +495,58 @@ def memory_lines(report):
     return lines
 
 
-def check_status(balanced, creport, mreport, preport=None):
-    """The exit status of `check`: 1 for an unbalanced bus, a failing constraint (with --constraints), a memory finding (with --memory) or a
-    hard program finding (with --program; wrapped operands never count)."""
-    return 0 if balanced and (creport is None or creport.satisfied) and (mreport is None or mreport.total_findings == 0) and (preport is None or preport.total_hard == 0) else 1
+def check_status(balanced, creport, mreport, preport=None, areport=None):
+    """The exit status of `check`: 1 for an unbalanced bus, a failing constraint (with --constraints), a memory finding (with --memory), a
+    hard program finding (with --program; wrapped operands never count) or a hard arithmetic finding (with --arithmetic; soft ones never count)."""
+    return 0 if balanced and (creport is None or creport.satisfied) and (mreport is None or mreport.total_findings == 0) and (preport is None or preport.total_hard == 0) and (
+        areport is None or areport.total_hard == 0) else 1
+
+
+ARITHMETIC_SYMBOLS = ("+", "-", "*", "/", "<", "<<", ">>", "&", "|", "^", "/s", "!=", "*hu", ">>s", "*hs", "<=", "==", "<s", "<=s")
+
+
+def arithmetic_words(f):
+    """(x, y, z) of a listed finding as integers; a malformed record's fields do not make words: None."""
+    if f["kind"] == "malformed":
+        return None
+    return tuple(int.from_bytes(bytes(f[k]), "big") for k in ("x", "y", "z"))
+
+
+def arithmetic_lines(report, basic=True):
+    """One line per hard kind of an arithmetic report (the count and the first listed finding of the kind), one per soft kind, then one
+    summary line with the counters.  basic: the chips are the BasicMachine's and go by their names."""
+    import valida_amd as va
+
+    def chip(f):
+        return va.CHIP_NAMES[f["chip"]] if basic else "chip %d" % f["chip"]
+
+    def what(f):
+        name = va.ARITHMETIC_OPCODES[f["opcode"] - 100]
+        where = "row %d%s, %s" % (f["row"], ", sent" if f["is_send"] else "", name)
+        if f["kind"] == "malformed":
+            return "%s: fields %s are not bytes" % (where, ", ".join(str(1 + j) for j in range(12) if f["mask"] >> j & 1))
+        x, y, z = arithmetic_words(f)
+        expr = "%d %s %d = %d" % (x, ARITHMETIC_SYMBOLS[f["opcode"] - 100], y, z)
+        if f["kind"] == "undefined":
+            return "%s: %s, %s" % (where, expr, ("division by zero", "signed overflow", "shift amount of 32 or more")[f["mask"] - 1])
+        return "%s: %s, expected %d" % (where, expr, f["expected"])
+
+    c, lines = report.counters, []
+    text = {"malformed": ("malformed record", "malformed records"), "undefined": ("undefined operation", "undefined operations"), "wrong_result": ("wrong result", "wrong results"),
+            "shift_quotient": ("signed quotient by a power of two holds the arithmetic shift", "signed quotients by a power of two hold the arithmetic shift"),
+            "arithmetic_shr": ("SHR32 record holds the arithmetic shift", "SHR32 records hold the arithmetic shift")}
+    for kinds, listed in ((va.ARITHMETIC_HARD_KINDS, report.hard), (va.ARITHMETIC_SOFT_KINDS, report.soft)):
+        for kind in kinds:
+            if not c[kind]:
+                continue
+            first = [f for f in listed if f["kind"] == kind]
+            head = "%d %s" % (c[kind], text[kind][c[kind] != 1])
+            lines.append("%s: %s (%s)" % (chip(first[0]), head, what(first[0])) if first else "alu: " + head)
+    ops = ", ".join("%s %d" % (name, n) for name, n in report.opcodes.items() if n)
+    lines.append("alu: %d live records in %d slots of %d entries, %d judged (%s), %d other, %d MULHS32 records where the sign matters, %d soft, %s" % (
+        c["live"], c["slots"], len(report.entries), c["judged"], ops or "none", c["other"], c["mulhs_sign_matters"], c["soft"],
+        "no finding" if not c["hard"] else "%d finding%s" % (c["hard"], "" if c["hard"] == 1 else "s")))
+    return lines
 
 
 PROGRAM_FIELD_NAMES = ("opcode", "operand a", "operand b", "operand c", "operand d", "operand e")
@@ -666,7 +723,10 @@ def main(argv=None):
                     "records, reads that do not return the last write to their address, reads of a non-zero value from an address nobody wrote; definite faults: check exits 1 on a finding)")
     ap.add_argument("--program", dest="program_audit", action="store_true", help="check: also the program audit (every cpu row's instruction held against the program ROM at its pc, the ROM's multiplicities against "
                     "the fetch counts: the reference's commented-out program bus replayed; check exits 1 on a hard finding, fetches that differ only by 2^32 in an immediate are listed apart)")
-    ap.add_argument("--max-findings", type=int, default=64, help="check --memory, --program: the findings listed (default 64, at most 2^20; the counts stay exact)")
+    ap.add_argument("--arithmetic", action="store_true", help="check: also the arithmetic audit (every live record of the general bus recomputed in 32-bit integer arithmetic: malformed "
+                    "records, undefined operations, wrong results; check exits 1 on a hard finding, the reference's two SRA conventions are listed apart)")
+    ap.add_argument("--sides", choices=("receives", "sends", "both"), default="receives", help="check --arithmetic: judge the ALU chips' receives (default), the senders' records, or both")
+    ap.add_argument("--max-findings", type=int, default=64, help="check --memory, --program, --arithmetic: the findings listed (default 64, at most 2^20; the counts stay exact)")
     ap.add_argument("--min-gate-windows", type=int, default=64, help="check --transitions: a gate that holds on fewer windows is counted but not audited (default 64)")
     ap.add_argument("--max-gates", type=int, default=256, help="check --transitions: the gates listed per chip, the ungated one included (default 256)")
     ap.add_argument("--step-sizes", default="1,-1,2", help="check --steps: 1 to 4 distinct step sizes, comma-separated integers mod p (as --step-sizes=1,-1,2)")
@@ -713,6 +773,7 @@ def main(argv=None):
                                                lookup_buses=parse_lookup_buses(args.lookup_buses)) if args.domains else None
                 memreport = va.memory_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_findings=args.max_findings) if args.memory else None
                 progreport = va.program_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), rom_len=w.program_len, max_findings=args.max_findings) if args.program_audit else None
+                arreport = va.arithmetic_audit_host(va.Machine.basic(), w.main_traces(), w.preprocessed(), max_findings=args.max_findings, sides=args.sides) if args.arithmetic else None
             else:
                 prover = va.Prover(va.Machine.basic(), va.poseidon_round_constants(source=args.constants), device=args.device or 0)
                 log = prover.upload_oplog(w.oplog())
@@ -733,6 +794,7 @@ def main(argv=None):
                 dreport = prover.domain_audit(main, prep, max_entries=1 << 20, chips=parse_chips(args.chips), max_bits=args.max_bits, lookup_buses=parse_lookup_buses(args.lookup_buses)) if args.domains else None
                 memreport = prover.memory_audit(main, prep, max_findings=args.max_findings) if args.memory else None
                 progreport = prover.program_audit(main, prep, rom_len=w.program_len, max_findings=args.max_findings) if args.program_audit else None
+                arreport = prover.arithmetic_audit(main, prep, max_findings=args.max_findings, sides=args.sides) if args.arithmetic else None
             text = report.to_json()
             if creport is not None:
                 text = json.dumps(dict(json.loads(text), constraints=creport.to_dict()))
@@ -762,6 +824,8 @@ def main(argv=None):
                 text = json.dumps(dict(json.loads(text), memory=memreport.to_dict()))
             if progreport is not None:
                 text = json.dumps(dict(json.loads(text), program=progreport.to_dict()))
+            if arreport is not None:
+                text = json.dumps(dict(json.loads(text), arithmetic=arreport.to_dict()))
             with open(args.action_file, "w") as f:
                 f.write(text + "\n")
             for line in report_lines(report, w.main_trace(0)) + (constraint_lines(creport, w.main_trace(0)) if creport is not None else []) + (mutation_lines(mreport) if mreport is not None else []) + (
@@ -770,9 +834,9 @@ def main(argv=None):
                     link_lines(lreport) if lreport is not None else []) + (step_lines(sreport) if sreport is not None else []) + (
                     invariant_lines(ireport) if ireport is not None else []) + (transition_lines(treport) if treport is not None else []) + (
                     product_lines(qreport) if qreport is not None else []) + (domain_lines(dreport) if dreport is not None else []) + (memory_lines(memreport) if memreport is not None else []) + (
-                    program_lines(progreport) if progreport is not None else []):
+                    program_lines(progreport) if progreport is not None else []) + (arithmetic_lines(arreport) if arreport is not None else []):
                 print(line)
-            return check_status(report.balanced, creport, memreport, progreport)
+            return check_status(report.balanced, creport, memreport, progreport, arreport)
         hash_kind = va.HASH_POSEIDON16 if args.poseidon_mmcs else va.HASH_KECCAK256
         rc = va.poseidon_round_constants(source=args.constants)
         prover = va.Prover(va.Machine.basic(), rc, device=args.device or 0, log_blowup=args.log_blowup, num_queries=args.queries, pow_bits=args.pow_bits,

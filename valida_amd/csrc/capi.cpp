@@ -83,6 +83,7 @@ struct vgpu_product_report : audit_report {};
 struct vgpu_domain_report : audit_report {};
 struct vgpu_memory_report : audit_report {};
 struct vgpu_program_report : audit_report {};
+struct vgpu_arithmetic_report : audit_report {};
 struct vgpu_comm { std::shared_ptr<Prover> owner; std::unique_ptr<Comm> comm; };  // owner first: the communicator dies before its context
 static_assert(sizeof(vgpu_cpu_op_t) == sizeof(vk::TgCpuOp) && sizeof(vgpu_mem_op_t) == sizeof(vk::TgMemOp) && sizeof(vgpu_alu_op_t) == sizeof(vk::TgAluOp),
               "C ABI log records and their device images must match");
@@ -1413,6 +1414,28 @@ uint64_t vgpu_program_report_len(const vgpu_program_report_t* r) { return report
 const uint32_t* vgpu_program_report_words(const vgpu_program_report_t* r) { return report_words(r); }
 void vgpu_program_report_timing(const vgpu_program_report_t* r, double out[3]) { report_timing(r, out, 3); }
 void vgpu_program_report_free(vgpu_program_report_t* r) { delete r; }
+
+// ---- arithmetic audit (host/arithmetic_audit.hpp) ----
+static_assert(sizeof(vgpu_arithmetic_audit_opts_t) == 20, "vgpu_arithmetic_audit_opts_t has no padding");
+static ArithmeticAuditOpts arithmetic_opts(const vgpu_arithmetic_audit_opts_t* o) {
+    ArithmeticAuditOpts r;  // a null pointer: the defaults (64 findings per list, global bus 0, the receives); a struct is taken as given
+    if (o) { r.max_findings = o->max_findings; r.bus_is_global = o->bus_is_global; r.bus_index = o->bus_index; r.sides = o->sides; r.reserved = o->reserved; }
+    return r;
+}
+int32_t vgpu_arithmetic_audit(vgpu_prover_t* p, const vgpu_trace_t* const* main, uint32_t n_main, const uint32_t* prep_chips, const vgpu_trace_t* const* prep,
+                              uint32_t n_prep, const vgpu_arithmetic_audit_opts_t* opts, vgpu_arithmetic_report_t** out) {
+    return audit_on_device(p, main, n_main, prep_chips, prep, n_prep, out, [&](auto& m, auto& pr) { return p->p->arithmetic_audit(m, pr, arithmetic_opts(opts)); });
+}
+int32_t vgpu_arithmetic_audit_host(const vgpu_machine_t* machine, const uint32_t* const* main, const uint64_t* heights, const uint64_t* widths, uint32_t n_main,
+                                   const uint32_t* prep_chips, const uint32_t* const* prep, const uint64_t* prep_heights, const uint64_t* prep_widths, uint32_t n_prep,
+                                   const vgpu_arithmetic_audit_opts_t* opts, vgpu_arithmetic_report_t** out) {
+    return audit_on_host<BusHostMatrix>(machine, main, heights, widths, n_main, prep_chips, prep, prep_heights, prep_widths, n_prep, out,
+                                        [&](auto&... a) { return arithmetic_audit_host(a..., arithmetic_opts(opts)); });
+}
+uint64_t vgpu_arithmetic_report_len(const vgpu_arithmetic_report_t* r) { return report_len(r); }
+const uint32_t* vgpu_arithmetic_report_words(const vgpu_arithmetic_report_t* r) { return report_words(r); }
+void vgpu_arithmetic_report_timing(const vgpu_arithmetic_report_t* r, double out[3]) { report_timing(r, out, 3); }
+void vgpu_arithmetic_report_free(vgpu_arithmetic_report_t* r) { delete r; }
 
 // ---- coverage audit (host/coverage_audit.hpp) ----
 static_assert(sizeof(vgpu_coverage_audit_opts_t) == 40, "vgpu_coverage_audit_opts_t has no padding");

@@ -28,7 +28,7 @@
 //             wrapped: the first max_findings WRAPPED_OPERAND rows; unfetched: the first max_ranges ranges [lo, hi), ascending.  Both limits
 //             default to 64, are at most 2^20, and 0 lists nothing while every count stays exact.
 // What it is not: it judges the fetches against the table of THIS witness only; not whether the opcode flags fit the opcode, not whether the
-// step did what the opcode says, not whether the preprocessed commitment is the verifier's.
+// step did what the opcode says (for the ALU results: host/arithmetic_audit.hpp), not whether the preprocessed commitment is the verifier's.
 // This header holds the options check, the plan, the report with its image "VPG1" and the host twin (plain C++, one thread, no limits beyond
 // the refusals).  The device pass is Prover::program_audit (prover_audits.cpp, kernels/program_audit.hip).
 #pragma once

@@ -22,6 +22,7 @@
 #include "domain_audit.hpp"
 #include "memory_audit.hpp"
 #include "program_audit.hpp"
+#include "arithmetic_audit.hpp"
 #include "pcs.hpp"
 
 namespace vhost {
@@ -189,6 +190,10 @@ class Prover {
     // preprocessed ROM (an LDS histogram of the pcs, one judged sweep over the fetches, one over the table) and the fetches and multiplicities
     // that break the would-be program bus; queued on the context like the other audits, scratch from the pool.
     ProgramReport program_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const ProgramAuditOpts& opts);
+    // Arithmetic audit of a witness (host/arithmetic_audit.hpp, kernels/arithmetic_audit.hip): the records of the general bus recomputed as 32-bit
+    // arithmetic (one judged sweep per entry into packed verdict words, two workgroup tables, count, scan, list) and the records whose stored
+    // result differs; queued on the context like the other audits, scratch from the pool.
+    ArithmeticReport arithmetic_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed, const ArithmeticAuditOpts& opts);
 
     // pcs.open_multi_batches: advances `ch` exactly as the reference's `&mut challenger` is advanced.
     PcsOpening open_multi_batches(const std::vector<OpenRound>& rounds, Challenger& ch);

@@ -1941,4 +1941,86 @@ ProgramReport Prover::program_audit(const std::vector<const DeviceTrace*>& main,
     return rep;
 }
 
+// ---- arithmetic audit (host/arithmetic_audit.hpp; kernels/arithmetic_audit.hip) -------------------------------------------------------------
+ArithmeticReport Prover::arithmetic_audit(const std::vector<const DeviceTrace*>& main, const std::vector<std::pair<int, const DeviceTrace*>>& preprocessed,
+                                          const ArithmeticAuditOpts& opts_in) {
+    const auto t_host = Clock::now();
+    const ArithmeticAuditOpts o = arithmetic_audit_checked_opts(opts_in);
+    const auto tr = audit_traces<BusShape>("arithmetic_audit", main, preprocessed);
+    std::vector<int> prep_slot;
+    BusPlan bus_plan;
+    const ArithmeticPlan plan = arithmetic_audit_plan(machine_, tr.ms, tr.prep_chips, tr.ps, prep_slot, o, &bus_plan);
+    ArithmeticReport rep;
+    arithmetic_audit_header(rep, plan, o);
+    const size_t NE = plan.entries.size();
+    const uint64_t n = plan.n_slots;
+    std::vector<uint32_t> block_base(NE, 0);
+    uint64_t nb = 0;  // the workgroups of all entries, in slot order
+    for (size_t e = 0; e < NE; e++) { block_base[e] = (uint32_t)nb; nb += (plan.entries[e].height + 255) / 256; }
+
+    DeviceCtx& c = *ctx_;
+    AuditPass pass(c, main.size() + preprocessed.size());
+    const size_t NC = machine_.airs.size();
+    const hipStream_t st = pass.stream;
+    size_t listed_hard = 0, listed_soft = 0;
+    audit_or_no_memory(st, [&] {
+        // only the chips with an entry are read
+        std::vector<const uint32_t*> mptr(NC, nullptr), pptr(NC, nullptr);
+        std::vector<uint64_t> mstride(NC, 0), pstride(NC, 0);
+        for (auto& e : plan.entries) {
+            const size_t i = e.chip;
+            if (mptr[i]) continue;
+            const vk::DMatView v = pass.working(main[i]);
+            mptr[i] = v.data; mstride[i] = v.stride;
+            if (const DeviceTrace* p = audit_prep(preprocessed, prep_slot, i)) { const vk::DMatView pv = pass.working(p); pptr[i] = pv.data; pstride[i] = pv.stride; }
+        }
+        c.check_launch("arithmetic_audit ingest");
+        DBuf desc(&c, bus_audit_descriptor(machine_, bus_plan, mptr, mstride, pptr, pstride));
+        // per entry its u64 totals, zeroed by one memset; the verdicts and the two workgroup tables are written whole by the judge
+        const size_t TOT_WORDS = 2 * (size_t)vk::AR_TOT * NE;
+        DBuf totals(&c, TOT_WORDS), verdict(&c, (size_t)n), tabs(&c, (size_t)(2 * nb));
+        unsigned long long* tot = (unsigned long long*)totals.data;
+        uint32_t* hard_tab = tabs.data;
+        uint32_t* soft_tab = tabs.data + nb;
+        pass.begin();
+        VG_HIP_CHECK(hipMemsetAsync(totals.data, 0, TOT_WORDS * 4, st));
+        for (size_t e = 0; e < NE; e++) {
+            const ArithmeticPlan::Entry& pe = plan.entries[e];
+            vk::launch_ar_judge(st, desc.data, pe.chip, pe.interaction, pe.height, (uint32_t)pe.first_slot, block_base[e], verdict.data, tot + e * vk::AR_TOT, hard_tab, soft_tab);
+        }
+        c.check_launch("arithmetic_audit judge");
+        std::vector<uint32_t> tw(TOT_WORDS, 0);
+        c.download_small(tw.data(), totals.data, TOT_WORDS * 4);
+        std::vector<unsigned long long> th(TOT_WORDS / 2);
+        for (size_t k = 0; k < th.size(); k++) th[k] = audit_u64(tw, k);
+        uint64_t n_hard = 0, n_soft = 0;
+        for (size_t e = 0; e < NE; e++) { n_hard += th[e * vk::AR_TOT + 3] + th[e * vk::AR_TOT + 4] + th[e * vk::AR_TOT + 5]; n_soft += th[e * vk::AR_TOT + 6] + th[e * vk::AR_TOT + 7]; }
+        listed_hard = (size_t)std::min<uint64_t>(n_hard, o.max_findings);
+        listed_soft = (size_t)std::min<uint64_t>(n_soft, o.max_findings);
+        std::vector<uint32_t> ow((listed_hard + listed_soft) * vk::AR_OUT);
+        if (!ow.empty()) {
+            DBuf out(&c, ow.size());
+            vk::launch_ar_scan(st, hard_tab, soft_tab, nb);
+            for (size_t e = 0; e < NE; e++) {
+                const ArithmeticPlan::Entry& pe = plan.entries[e];
+                const unsigned long long* t = th.data() + e * vk::AR_TOT;
+                if (!(t[3] + t[4] + t[5] + t[6] + t[7])) continue;  // an entry without a finding lists nothing
+                vk::launch_ar_list(st, desc.data, pe.chip, pe.interaction, pe.is_send, pe.height, (uint32_t)pe.first_slot, block_base[e], verdict.data, hard_tab, soft_tab,
+                                   (uint32_t)listed_hard, (uint32_t)listed_soft, out.data, out.data + listed_hard * vk::AR_OUT);
+            }
+            c.check_launch("arithmetic_audit list");
+            c.download_small(ow.data(), out.data, ow.size() * 4);
+        }
+        arithmetic_audit_from_device(rep, th.data(), vk::AR_TOT, ow.data(), listed_hard, listed_soft);
+        pass.end(rep);
+    }, [&] {
+        return std::string("arithmetic_audit: the device pool cannot give the pass its scratch: 4 bytes for each of the " + std::to_string(n) + " (entry, row) slots (the verdicts) = " +
+                           std::to_string(4 * n) + " bytes, " + std::to_string(8 * vk::AR_TOT) + " bytes of totals for each of the " + std::to_string(NE) + " entries, 8 bytes for each of the " +
+                           std::to_string(nb) + " workgroups (two tables) = " + std::to_string(8 * nb) + " bytes, 96 per listed finding (" + std::to_string(listed_hard + listed_soft) +
+                           "), plus the working-layout copies of uploaded traces");
+    });
+    rep.host_ms = ms_since(t_host);
+    return rep;
+}
+
 }  // namespace vhost

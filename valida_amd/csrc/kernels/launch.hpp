@@ -498,6 +498,17 @@ void launch_pg_judge(hipStream_t st, const PgArgs& a, uint32_t mode, unsigned lo
                      uint32_t max_wrapped, uint32_t* out_hard, uint32_t* out_wrap);
 void launch_pg_table(hipStream_t st, const PgArgs& a, uint32_t mode, const uint32_t* counts, unsigned long long* tot, uint32_t* tabs, uint32_t mult_base, uint32_t max_hard,
                      uint32_t max_ranges, uint32_t* out_hard, uint32_t* ranges);
+// arithmetic_audit.hip — the passes of the arithmetic audit (host/arithmetic_audit.hpp: contract; Prover::arithmetic_audit drives them).  desc:
+// the bus audit's descriptor (host/bus_audit.hpp).  An entry is (chip, interaction m) with `height` rows; its slots are first_slot + row and its
+// workgroups block_base + ceil(row / 256) in the two tables.  verdict: [slots] u32 (written whole); tot: per entry [AR_TOT] u64 (zeroed);
+// hard_tab, soft_tab: [workgroups of all entries] (written whole); out: [listed][AR_OUT] u32.
+constexpr uint32_t AR_TOT = 32, AR_OUT = 24;
+void launch_ar_judge(hipStream_t st, const uint32_t* desc, uint32_t chip, uint32_t m, uint64_t height, uint32_t first_slot, uint32_t block_base, uint32_t* verdict,
+                     unsigned long long* tot, uint32_t* hard_tab, uint32_t* soft_tab);
+// both tables become their own exclusive prefixes (the memory audit's one-workgroup scan)
+void launch_ar_scan(hipStream_t st, uint32_t* hard_tab, uint32_t* soft_tab, uint64_t n_blocks);
+void launch_ar_list(hipStream_t st, const uint32_t* desc, uint32_t chip, uint32_t m, uint32_t is_send, uint64_t height, uint32_t first_slot, uint32_t block_base,
+                    const uint32_t* verdict, const uint32_t* hard_pre, const uint32_t* soft_pre, uint32_t max_hard, uint32_t max_soft, uint32_t* out_hard, uint32_t* out_soft);
 // field_audit.hip — the passes of the field audit (host/field_audit.hpp: contract; Prover::field_audit drives them), per chip.  One wave per
 // trace row, one wave per workgroup, T rows per workgroup one after the other, NB workgroups.  A SLOT of a chip is (interaction, field) in
 // order, NS of them.  totals: u64 [0] live records, [1] floating fields, [2] rows with a floating field, [3 + m] live rows of interaction m,
